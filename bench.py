@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — env-steps/s of N parallel SoftPendulum-v0 on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is one env.step() of every env of the job: 4096 envs x 50 elements per GPU
 (BASELINE.json configs[1]; with N GPUs the batch is 4096*N envs sharded contiguously,
@@ -9,6 +9,15 @@ configs[3] at N=8 — weak scaling), i.e. per GPU 4096 x 400 PositionVerlet subs
 one kernel launch, plus (N>1) one packed RCCL all-gather of the per-env outputs.
 Inputs (state, pre-staged float32 actions) are resident in HBM when the timed region
 starts.  Rank 0 prints ONE JSON line.
+
+A plain run measures the headline only: set-up, pre-heat and warm-up, the K timed steps, the
+outputs of the last of them under --dump-outputs, the line.  Everything else the line can carry
+(`secondary`, `pcie_inclusive`, `policy_in_loop`, `single_env`, `cpu_baseline` with
+`parity_vs_oracle`, `sustained`) runs only under `--full`, after the headline figures are taken;
+in a plain run `cpu_baseline` is null and the other keys are absent.  `--dump-outputs DIR` writes
+what the last timed env.step returned (obs, reward, terminated, truncated over every env of the
+job) as DIR/<name>.npy; inputs are seeded, so two builds run with the same arguments can be
+compared output for output.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches itself:
 the parent starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD
@@ -34,17 +43,17 @@ power-controller transient: 0.30 -> 0.35-0.37 ms, gone 20 ms later), before it h
 steps a scratch batch of the same shape with zero actions until the HIP-event kernel time is
 stable (groups of ~6 ms of kernel time, three groups within 0.5 %, after 120 and within 600 ms of
 kernel time); the measured batch is untouched by it, so the timed window stays inside one episode.  `steps`/`warmup` echo the
-arguments; as many consecutive windows of K steps as fit one episode together with the warm-up
-(120 steps; at most five) are timed, each bracketed like the contract says, and `value` /
-`ms_per_step` are the MEDIAN window's (all windows are listed under `windows`): on some boxes the
-power controller pulls the clock back for ~20 ms every ~55 ms, and one 6 ms window can fall
-entirely inside or outside such a dip.
+arguments; the K steps are timed as one window, bracketed like the contract says.  `--windows R`
+times R consecutive windows of K steps instead (`--windows 0`: as many as fit one episode together
+with the warm-up, 120 steps, at most five), and `value` / `ms_per_step` are then the MEDIAN window's
+(all windows are listed under `windows`): on some boxes the power controller pulls the clock back
+for ~20 ms every ~55 ms, and one 6 ms window can fall entirely inside or outside such a dip.
 
 Staleness: profiles/valu_counts.json and hbm_traffic.json entries carry the source hash of the
 library they were measured on (softrod_source_hash); when it differs from the loaded library's,
 `roofline.frac` / `traffic` are null and `frac_withheld` says why.
 
-cpu_baseline: the repo's fp64 C oracle (a port/restatement, NOT PyElastica — see
+cpu_baseline (--full): the repo's fp64 C oracle (a port/restatement, NOT PyElastica — see
 oracle/softrod_oracle.c) timed on this box's host cores with OpenMP over rods, rank 0,
 N=1 only, on a bounded sample of the same workload: the SAME 4096 rods (SURVEY §8(d) /
 BASELINE.md §3), as many env.steps as fit ~10 s (at least 2), plus one rod on one thread for
@@ -52,7 +61,7 @@ BASELINE.md §3), as many env.steps as fit ~10 s (at least 2), plus one rod on o
 also the OpenMP thread count.  `cpu_baseline.parity_vs_oracle`: max |d obs| / |obs| of
 the HIP path against that oracle after 1 / 3 / 100 env.steps on the first 16 envs of the batch.
 
-secondary (N=1, default): after the headline windows the same process measures BASELINE
+secondary (N=1, --full): after the headline windows the same process measures BASELINE
 configs[2] (OctoArmSingle-v0, 100 elements x 4096 envs) and configs[4]'s per-GPU share
 (OctoFlat-v0 x 1024 envs), 10 timed steps each on the warm clock, and reports them under
 `secondary` with their own roofline blocks (hash-matched tables); the headline keys are untouched.
@@ -67,7 +76,7 @@ windows once more over transport "p2p" in a child process of its own, bounded by
 or a fall-back of the experimental transport cannot cost the headline measurement: it is out already).
 The trial's figures go to stderr as `bench.py: p2p_trial: {...}` and to gpurun_out/p2p_trial_N<world>.json.
 
-sustained (default; round 5; N > 1: every rank on its own GPU, no exchange, rank 0's figure in the line):
+sustained (--full; round 5; N > 1: every rank on its own GPU, no exchange, rank 0's figure in the line):
 after everything else ONE more leg keeps the GPU under continuous load
 for >= 8 s — ~27 000 env.steps of the headline workload with device-side NEXT_STEP auto-reset (episodes
 end every 125 steps and restart from staged draws without a host round trip) — so that an outside
@@ -78,7 +87,8 @@ closed RL loop on the device — observations -> a 2 x 64 tanh MLP (torch, the s
 synchronisation) -> actions -> softrod_step, with device auto-reset — i.e. what examples/
 soft_pendulum_3d/train_ppo.py's rollout costs per env.step when the policy lives next to the envs.
 
-methodology_version 5 (round 5: `secondary` gains the libm-mode SoftPendulum entry, `sustained`,
+methodology_version 6: one timed window of K steps by default (the K steps of the arguments are the
+steps timed), every add-on behind --full.  5 (round 5: `secondary` gains the libm-mode SoftPendulum entry, `sustained`,
 `policy_in_loop`; the headline windows are those of version 4).  3 = round 3: clock pre-heat + median of up to five windows;
 figures of rounds 1-2 (one window, no pre-heat) are not like for like.  `single_window` in the
 line is window 0 alone, whatever the window count.
@@ -102,7 +112,7 @@ N_SIMD = 1024                # 256 CUs x 4 SIMDs
 CLOCK_HZ = 2.4e9             # MI355X_MICROARCH.md peak engine clock
 CYCLES_PER_FP64_WAVE_INSTR = 4.0   # wave64 fp64 op: 16 lanes per clock per SIMD
 VALU_PEAK_GINSTR = N_SIMD * CLOCK_HZ / CYCLES_PER_FP64_WAVE_INSTR / 1e9   # 614.4
-METHODOLOGY_VERSION = 5
+METHODOLOGY_VERSION = 6
 AMAX = {"SoftPendulum-v0": 22.0, "SoftPendulum3D-v0": 1.0, "OctoArmSingle-v0": 6.0,
         "OctoFlat-v0": 22.0, "SoftArmTracking-v0": 1.0, "OctoArmPush-v0": 1.0, "OctoArmPush-v1": 1.0, "OctoArmPullWeight-v0": 1.0,
         "OctoCrawl-v0": 1.0, "OctoArmTwo-v0": 1.0, "OctoReach-v0": 1.0}
@@ -301,9 +311,9 @@ def parse_args(argv=None):
                          "like the reference's muscle arms (octopus/arm_push_env.py:160-179) — the per-lane "
                          "material-table instantiation of the step kernel")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="N=1 headline run: skip the two secondary workloads (BASELINE configs[2], configs[4]'s share)")
+                    help="--full: skip the secondary workloads (BASELINE configs[2], configs[4]'s share, ...)")
     ap.add_argument("--no-sustained", action="store_true",
-                    help="N=1 headline run: skip the closing >= 8 s continuous-load leg")
+                    help="--full: skip the closing >= 8 s continuous-load leg")
     ap.add_argument("--p2p-trial", action="store_true",
                     help="N>1 with the default transport: AFTER the line is printed, run the same windows once more over "
                          "the experimental transport p2p in child processes (bounded by 90 s; figures on stderr).  "
@@ -315,9 +325,17 @@ def parse_args(argv=None):
                     help="N > 1: how the packed rows reach the other ranks.  rccl (default, BASELINE's north_star): "
                          "one all_gather_into_tensor per step; p2p: every rank copies its rows into its block of "
                          "every peer's buffer (IPC-mapped, xGMI point to point), no collective call per step")
-    ap.add_argument("--windows", type=int, default=0,
-                    help="timed windows of --steps steps each (value = the median window); 0 (default): as many as "
-                         "fit one SoftPendulum episode together with the warm-up (120 steps), at most 5, at least 1")
+    ap.add_argument("--windows", type=int, default=1,
+                    help="timed windows of --steps steps each (value = the median window); 1 (default): the --steps "
+                         "steps are the timed steps; 0: as many as fit one SoftPendulum episode together with the "
+                         "warm-up (120 steps), at most 5, at least 1")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the add-ons: secondary workloads, pcie_inclusive, "
+                         "policy_in_loop, single_env, cpu_baseline with parity_vs_oracle, and the sustained leg "
+                         "(N > 1: every rank's sustained leg); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed env.step returned (obs, reward, "
+                         "terminated, truncated over all envs of the job) as DIR/<name>.npy in float32 / float64")
     ap.add_argument("--preheat", type=float, default=600.0,
                     help="cap of the un-timed pre-heat on a scratch batch, in ms of kernel time (0 = none); it "
                          "ends earlier once the kernel time has been stable for three groups after 120 ms")
@@ -1012,6 +1030,34 @@ def guarded(fn, *a, **kw):
         return {"error": repr(exc)}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outputs, seed: int = 0):
+    """`--dump-outputs DIR`: the arrays the last timed env.step returned to its caller, over every env of the job
+    (gathered rows included), as DIR/<name>.npy — float64 stays float64, everything else (float32 observations,
+    bool flags as 0 / 1) is written as float32.  Above DUMP_MAX_BYTES in all, the same fixed, seeded sample of env
+    rows is taken from every array and its row indices go to DIR/env_index.npy.  Returns {name: shape}."""
+    import numpy as np
+
+    arrays = {}
+    for name, t in outputs.items():
+        a = t.detach().cpu().numpy()
+        arrays[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes for a in arrays.values()) / max(n, 1)
+    if row_bytes * n > DUMP_MAX_BYTES:
+        k = int(DUMP_MAX_BYTES // (row_bytes + 8))
+        idx = np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def single_env_latency(gsa, np, steps: int = 60, warmup: int = 5):
     """BASELINE configs[0]'s shape on the GPU: ONE SoftPendulum-v0 env through the drop-in Gymnasium
     surface (`make(id)`, NumPy action in, NumPy observation out, a host synchronisation every step) —
@@ -1260,6 +1306,9 @@ def main(argv=None, script=None) -> int:
     n_bad = int((~torch.isfinite(obs).all(dim=1)).sum().item())
     # what the last step returned, over ALL envs (gathered rows included): lets two runs be compared
     obs_checksum = float(torch.nan_to_num(obs.double()).sum().item()) + float(torch.nan_to_num(rew.double()).sum().item())
+    if args.dump_outputs and rank == 0:
+        shapes = dump_outputs(args.dump_outputs, {"obs": obs, "reward": rew, "terminated": term, "truncated": trunc})
+        sys.stderr.write(f"bench.py: outputs of the last timed step written to {args.dump_outputs}: {json.dumps(shapes)}\n")
 
     # N > 1: what every rank measured (its step-kernel time; the rest of its step is the exchange)
     per_rank = None
@@ -1357,7 +1406,7 @@ def main(argv=None, script=None) -> int:
     if scratch is not None:
         scratch.close()
         scratch = None
-    if (distributed and world > 1 and args.env == "SoftPendulum-v0" and hip and not args.no_sustained
+    if (args.full and distributed and world > 1 and args.env == "SoftPendulum-v0" and hip and not args.no_sustained
             and not args.trial_child and args.math_mode == "fast" and args.scaling == "weak"
             and args.envs_per_gpu in (None, ENVS_PER_GPU) and args.n_elems is None):
         # N > 1: EVERY rank keeps its GPU under continuous load for >= 8 s on a shard-sized batch of its own
@@ -1371,7 +1420,7 @@ def main(argv=None, script=None) -> int:
                                                 "its own shard-sized batch with no exchange (their figures: stderr, "
                                                 "`bench.py: sustained rank k: {...}`); not a whole-job figure")
     if rank == 0 and world == 1 and not distributed:
-        full = (args.env == "SoftPendulum-v0" and hip and not args.no_secondary and args.n_elems is None
+        full = (args.full and args.env == "SoftPendulum-v0" and hip and not args.no_secondary and args.n_elems is None
                 and args.envs_per_gpu in (None, ENVS_PER_GPU) and args.math_mode == "fast")
         if full:
             line["secondary"] = [guarded(secondary_workload, gsa, _capi, torch, local_rank, math_mode, lib_hash, **spec)
@@ -1379,7 +1428,7 @@ def main(argv=None, script=None) -> int:
             line["pcie_inclusive"] = guarded(pcie_inclusive, gsa, torch, local_rank, math_mode, n_local)
             line["policy_in_loop"] = guarded(policy_in_loop, gsa, torch, local_rank, math_mode, n_local)
             line["single_env"] = guarded(single_env_latency, gsa, np)
-        if not args.no_cpu_baseline and args.env == "SoftPendulum-v0" and hip:
+        if args.full and not args.no_cpu_baseline and args.env == "SoftPendulum-v0" and hip:
             line["cpu_baseline"] = guarded(cpu_baseline, cfg, usable_cpus(), n_rods=ENVS_PER_GPU)
             line["cpu_baseline"]["parity_vs_oracle"] = guarded(parity_vs_oracle, gsa, torch, local_rank, math_mode, cfg)
         else:

@@ -39,7 +39,8 @@ def _p2p_trial(stderr):
 
 
 def test_single_process_line_has_the_contract_fields(oracle_built):
-    p = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--envs-per-gpu", "4", "--no-cpu-baseline"])
+    p = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--envs-per-gpu", "4", "--no-cpu-baseline",
+              "--windows", "0"])
     assert p.returncode == 0, p.stderr[-2000:]
     (line,) = _json_lines(p.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
@@ -51,6 +52,78 @@ def test_single_process_line_has_the_contract_fields(oracle_built):
     assert line["value"] == sorted(line["windows"]["value"])[2]                       # the median window
     assert line["roofline"]["frac"] is None and line["roofline"]["frac_withheld"]     # not the HIP library: no pricing
     assert line["roofline"]["bound"] == "fp64_valu" and "frac" in line["roofline"] and "traffic" in line["roofline"]
+
+
+def test_plain_run_times_exactly_the_steps_asked_for(oracle_built):
+    """`--steps K` is the number of timed steps: one window of K, `ms_per_step` its time per step; the add-ons
+    are --full's, so a plain line carries none of them."""
+    p = _run(["--gpus", "1", "--steps", "7", "--warmup", "2", "--envs-per-gpu", "4"])
+    assert p.returncode == 0, p.stderr[-2000:]
+    (line,) = _json_lines(p.stdout)
+    assert line["steps"] == 7 and line["warmup"] == 2
+    assert line["windows"]["count"] == 1 and len(line["windows"]["kernel_ms_each"]) == 7
+    assert line["ms_per_step"] == line["windows"]["ms_per_step"][0] > 0
+    assert line["value"] == line["windows"]["value"][0]
+    assert line["cpu_baseline"] is None
+    for k in ("secondary", "pcie_inclusive", "policy_in_loop", "single_env", "sustained"):
+        assert k not in line, k
+
+
+def test_dump_outputs_writes_the_last_timed_step(oracle_built, tmp_path):
+    """`--dump-outputs DIR`: the arrays the last timed env.step returned, float32 / float64, identical from run
+    to run, the same from two ranks as from one process stepping all their envs."""
+    import numpy as np
+
+    def dumped(d):
+        return {n: np.load(d / f"{n}.npy") for n in ("obs", "reward", "terminated", "truncated")}
+
+    a = ["--steps", "4", "--warmup", "1"]
+    runs = {}
+    for tag, extra in (("one", ["--gpus", "1", "--envs-per-gpu", "8"]), ("again", ["--gpus", "1", "--envs-per-gpu", "8"]),
+                       ("two", ["--gpus", "2", "--envs-per-gpu", "4"])):
+        p = _run(extra + a + ["--dump-outputs", str(tmp_path / tag)])
+        assert p.returncode == 0, p.stderr[-2000:]
+        (line,) = _json_lines(p.stdout)
+        runs[tag] = (line, dumped(tmp_path / tag))
+    line, out = runs["one"]
+    assert out["obs"].dtype == np.float32 and out["obs"].shape == (8, 4)
+    assert out["reward"].dtype == np.float64 and out["reward"].shape == (8,)
+    assert out["terminated"].dtype == out["truncated"].dtype == np.float32
+    assert not (tmp_path / "one" / "env_index.npy").exists()
+    assert float(out["obs"].astype(np.float64).sum() + out["reward"].sum()) == pytest.approx(
+        line["config"]["last_step_checksum"], rel=1e-12, abs=1e-12)
+    for tag in ("again", "two"):
+        for n, x in out.items():
+            np.testing.assert_array_equal(runs[tag][1][n], x, err_msg=f"{tag}: {n}")
+
+
+def test_dump_outputs_samples_rows_above_the_cap(tmp_path, monkeypatch):
+    """Above the size cap the same seeded rows are taken from every array, their indices in env_index.npy."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    n = 1000
+    obs = torch.arange(n * 3, dtype=torch.float32).reshape(n, 3)
+    rew = torch.arange(n, dtype=torch.float64)
+    flags = torch.arange(n) % 2 == 0
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4000)
+    outs = {"obs": obs, "reward": rew, "terminated": flags}
+    shapes = bench.dump_outputs(tmp_path / "a", outs)
+    bench.dump_outputs(tmp_path / "b", outs)
+    idx = np.load(tmp_path / "a" / "env_index.npy")
+    k = len(idx)
+    assert 0 < k < n and shapes["obs"] == [k, 3] and idx.dtype == np.float64
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in ("obs.npy", "reward.npy", "terminated.npy", "env_index.npy")) <= 4000
+    rows = idx.astype(np.int64)
+    assert (np.diff(rows) > 0).all()
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "obs.npy"), obs.numpy()[rows])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "reward.npy"), rew.numpy()[rows])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "terminated.npy"), flags.numpy()[rows].astype(np.float32))
+    for f in ("obs.npy", "reward.npy", "terminated.npy", "env_index.npy"):
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
 
 
 def test_gpus_2_launches_itself_and_prints_one_line(oracle_built):

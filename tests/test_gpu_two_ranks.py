@@ -62,9 +62,9 @@ def _check_pair(two, one, total, steps):
 
 def test_bench_two_ranks_softpendulum(hip_lib):
     """configs[3]'s shape at world 2: 2 x 2048 envs against 1 x 4096."""
-    a = ("--steps", "12", "--warmup", "2")
+    a = ("--steps", "12", "--warmup", "2", "--windows", "0")
     two = _bench(TWO_ON_ONE, "--gpus", "2", "--envs-per-gpu", "2048", "--p2p-trial", *a)
-    one = _bench({}, "--gpus", "1", "--envs-per-gpu", "4096", *a)
+    one = _bench({}, "--gpus", "1", "--envs-per-gpu", "4096", "--full", *a)
     _check_pair(two, one, 4096, 12)
     assert two["windows"]["count"] == one["windows"]["count"] == 5
     assert one["roofline"]["frac"] is None or 0.2 < one["roofline"]["frac"] < 1.0
@@ -86,10 +86,10 @@ def test_bench_two_ranks_softpendulum(hip_lib):
 
 
 def test_bench_two_ranks_default_sizes_keep_every_gpu_busy(hip_lib):
-    """`python bench.py --gpus 2 --steps K --warmup W` at the DEFAULT batch (2 x 4096 envs: the driver's command):
-    after the windows every rank runs the >= 2 s `sustained` leg on its own GPU with no exchange (what the driver's
+    """`python bench.py --gpus 2 --steps K --warmup W --full` at the DEFAULT batch (2 x 4096 envs): after the
+    windows every rank runs the >= 2 s `sustained` leg on its own GPU with no exchange (what the driver's
     GPU-busy samples see); rank 0's figure is in the line, every rank's on stderr; no p2p trial unless asked for."""
-    two = _bench(TWO_ON_ONE, "--gpus", "2", "--steps", "10", "--warmup", "2")
+    two = _bench(TWO_ON_ONE, "--gpus", "2", "--steps", "10", "--warmup", "2", "--full")
     assert two["n_gpus"] == 2 and two["config"]["envs_total"] == 8192 and two["config"]["transport"] == "rccl"
     su = two["sustained"]
     assert su["seconds"] >= 2.0 and su["value"] > 0 and "rank 0" in su["note"], su
@@ -263,18 +263,19 @@ print("P2P-GEN-OK")
 
 
 def test_driver_line_carries_cpu_baseline_and_parity_vs_oracle(hip_lib):
-    """`python bench.py --steps 20 --warmup 5` as the driver runs it at N = 1: one JSON line with the
+    """`python bench.py --steps 20 --warmup 5 --windows 0 --full` at N = 1: one JSON line with the
     contract's keys, `roofline`, `secondary`, `pcie_inclusive`, and `cpu_baseline` on the 4096 rods
     with BASELINE.md §3's parity figures (HIP vs the oracle after 1 / 3 / 100 env.steps) inside 1e-5."""
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "20", "--warmup", "5"], env=env,
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "20", "--warmup", "5", "--windows", "0",
+                          "--full"], env=env,
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     (line,) = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
     assert line["metric"] == "env_steps_per_sec" and line["n_gpus"] == 1 and line["dtype"] == "f64"
-    assert line["methodology_version"] == 5 and line["windows"]["count"] == 5
+    assert line["methodology_version"] == 6 and line["windows"]["count"] == 5
     assert line["value"] == sorted(line["windows"]["value"])[2] and line["single_window"]["value"] == line["windows"]["value"][0]
     cb = line["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "4096 rods" in cb["sample"]

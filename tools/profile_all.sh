@@ -28,7 +28,7 @@ declare -A ARGS=(
 )
 NAMES=${*:-SoftPendulum-v0 SoftPendulum3D-v0 OctoArmSingle-v0 OctoArmSingle-v0_n100 OctoArmSingle-v0_taper OctoFlat-v0 SoftArmTracking-v0 OctoArmPush-v1 SoftPendulum-v0_libm OctoArmPullWeight-v0 OctoCrawl-v0}
 for NAME in $NAMES; do
-  A="--no-cpu-baseline --no-secondary ${ARGS[$NAME]}"
+  A="--no-cpu-baseline --no-secondary --windows 0 ${ARGS[$NAME]}"
   OUT=$ROOT/gpurun_out/prof_${TAG}_$NAME
   rm -rf "$OUT"; mkdir -p "$OUT"
   timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace --output-format csv -- \

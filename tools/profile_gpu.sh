@@ -8,9 +8,9 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-# bench.py's own defaults (20 warm-up + 100 timed steps): the profile is of the SAME command
+# 20 warm-up + up to five windows of 20 timed steps (--windows 0), then the --full add-ons: the profile is of the SAME command
 # --no-sustained: the sustained leg starts rocm-smi as a child; no child process under a profiler preload
-ARGS="--no-cpu-baseline --no-sustained $*"
+ARGS="--full --no-cpu-baseline --no-sustained --windows 0 $*"
 
 timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace --output-format csv -- \
     python3 "$ROOT/bench.py" $ARGS > "$OUT/bench_trace.log" 2>&1
