@@ -27,9 +27,7 @@ struct softrod_handle {
     size_t init_stride = 18;  // doubles of reset staging per env
     int window_refresh = 0;   // > 0: the rod runs on two overlapping wave windows (softrod_window.hpp),
                               // halo refreshed every so many substeps
-    bool octo_one_env_per_block = false;  // A/B switch SOFTROD_OCTO_ONE_ENV_PER_BLOCK, read once in softrod_create
     bool window_paired = true;            // A/B switch SOFTROD_WINDOW_PAIRED=0: one rod per workgroup with s_barrier
-    bool octo_one_wave = false;           // A/B switch SOFTROD_OCTO_ONE_WAVE: softrod_octo1w.hpp (one wave per env, two slots per lane)
     std::string tier;                     // softrod_kernel_tier
     RodParams P{};
     StatePtrs S{};
@@ -306,20 +304,17 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
         hipLaunchKernelGGL((softrod_octo_step_kernel<FEATS, MAXW>), grid, block, 0, st, h->P, h->S,     \
                            actions, obs, reward, term, trunc, n_sub, epilogue, pack)
         // the reference shape (two waves per env): four envs per workgroup, partner waves on one SIMD
-        if (zup && h->nw == 2 && h->octo_one_wave && h->P.n_arm * h->P.seg == 2 * kLanes && !(h->P.seg & 1)) {
-            hipLaunchKernelGGL((softrod_octo1w_step_kernel<SOFTROD_FEATURES_OCTO_FLAT | kFeatPlaneZup>),
-                               dim3((unsigned)h->cfg.n_envs), dim3(kLanes), 0, st, h->P, h->S,
-                               actions, obs, reward, term, trunc, n_sub, epilogue, pack);
-        } else
-        if (zup && h->nw == 2 && !h->octo_one_env_per_block) {
+        if (zup && h->nw == 2) {
             hipLaunchKernelGGL((softrod_octo_step_kernel<SOFTROD_FEATURES_OCTO_FLAT | kFeatPlaneZup, 2, 4>),
                                dim3((unsigned)((h->cfg.n_envs + 3) / 4)), dim3(kLanes * 8), 0, st, h->P, h->S,
                                actions, obs, reward, term, trunc, n_sub, epilogue, pack);
-        } else
-        if (zup) { if (h->nw <= 2) SR_OCTO(SOFTROD_FEATURES_OCTO_FLAT | kFeatPlaneZup, 2);
-                   else SR_OCTO(SOFTROD_FEATURES_OCTO_FLAT | kFeatPlaneZup, 8); }
-        else     { if (h->nw <= 2) SR_OCTO(SOFTROD_FEATURES_OCTO_FLAT, 2);
-                   else SR_OCTO(SOFTROD_FEATURES_OCTO_FLAT, 8); }
+        } else if (zup) {
+            if (h->nw <= 2) SR_OCTO(SOFTROD_FEATURES_OCTO_FLAT | kFeatPlaneZup, 2);
+            else SR_OCTO(SOFTROD_FEATURES_OCTO_FLAT | kFeatPlaneZup, 8);
+        } else {
+            if (h->nw <= 2) SR_OCTO(SOFTROD_FEATURES_OCTO_FLAT, 2);
+            else SR_OCTO(SOFTROD_FEATURES_OCTO_FLAT, 8);
+        }
 #undef SR_OCTO
     } else if (h->window_refresh > 0 && epilogue) {
         // substeps on two overlapping one-node-per-lane windows, then reward / observation by the
@@ -851,12 +846,8 @@ int softrod_create(const softrod_config* cfg, int device, softrod_handle** out) 
     const char* dbg = std::getenv("SOFTROD_DEBUG_SWITCHES");
     const bool debug_switches = dbg && dbg[0] == '1';
     auto debug_env = [&](const char* name) -> const char* { return debug_switches ? std::getenv(name) : nullptr; };
-    if (const char* one = debug_env("SOFTROD_OCTO_ONE_ENV_PER_BLOCK"))
-        h->octo_one_env_per_block = one[0] == '1';
     if (const char* one = debug_env("SOFTROD_WINDOW_PAIRED"))              // softrod_window.hpp
         h->window_paired = one[0] != '0';
-    if (const char* one = debug_env("SOFTROD_OCTO_ONE_WAVE"))              // softrod_octo1w.hpp
-        h->octo_one_wave = one[0] == '1';
     {   // two-window form: ArmSingle with the e_z contact, 64..102 elements
         const int halo = kLanes - (cfg->n_elem + 2) / 2;     // the narrower of the two halos
         const char* off = debug_env("SOFTROD_NO_WINDOW");
@@ -1691,9 +1682,7 @@ const char* softrod_kernel_tier(softrod_handle* h) {
     } else if (is_octo(h) && is_pull(h)) {
         t = "softrod_octo_step_kernel<ArmPullWeight,1 wave,1 env/wg,taper>";
     } else if (is_octo(h)) {
-        if (zup && h->nw == 2 && h->octo_one_wave && h->P.n_arm * h->P.seg == 2 * kLanes && !(h->P.seg & 1))
-            t = "softrod_octo1w_step_kernel<zup,1 wave,1 env/wg>";
-        else if (zup && h->nw == 2 && !h->octo_one_env_per_block)
+        if (zup && h->nw == 2)
             t = "softrod_octo_step_kernel<zup,2 waves,4 envs/wg>";
         else
             t = std::string("softrod_octo_step_kernel<") + (zup ? "zup," : "general plane,") +

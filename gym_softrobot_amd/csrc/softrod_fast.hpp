@@ -136,24 +136,6 @@ __device__ __forceinline__ double theta_over_sin(double y, bool valid_lane) {
     } else {
         if (!wave_any_of(valid, !(y < 2.5e-3))) return theta_over_sin_series<6>(y);
         if (!wave_any_of(valid, !(y < 0.04))) return theta_over_sin_series<12>(y);
-#ifdef SOFTROD_DIAG_THETA_LOOP      // round 5's tier, for the A/B of tools/octo_ab.sh (variant "thetaloop")
-        {
-            const double y0 = y;
-            int k = 0;
-            while (wave_any_of(valid, !(y < 0.15)) && k < 12) {
-                const double om = fmax(1.0 - y, 1.0e-300);
-                y = 0.5 * y * fast_rcp(1.0 + om * fast_rsqrt(om));
-                ++k;
-            }
-            double g = theta_over_sin_series<20>(y);
-            if (k > 0) {
-                const double a = fmax(y * (1.0 - y), 1.0e-300), b = fmax(y0 * (1.0 - y0), 1.0e-300);
-                g *= (double)(1 << k) * (a * fast_rsqrt(a)) * fast_rsqrt(b);
-                g = (y0 < 1.0e-30) ? 1.0 : g;
-            }
-            return g;
-        }
-#endif
         if (!wave_any_of(valid, !(y < 0.15))) return theta_over_sin_series<20>(y);
     }
     // Beyond: two half-angle steps, unconditionally — y <= 1 means sin^2(theta/8) <= sin^2(pi/8) = 0.1465 < 0.15, so two always
@@ -201,11 +183,7 @@ __device__ __forceinline__ double cold_literal() {
                  : "i"((int)(unsigned)(BITS & 0xffffffffull)), "i"((int)(unsigned)(BITS >> 32)));
     return __hiloint2double(hi, lo);
 }
-#ifdef SOFTROD_DIAG_HOIST_LITERALS      // A/B (tools/octo_ab.sh "hoistlit"): plain literals, the compiler's placement
-#define SOFTROD_COLD_LIT(x) ((double)(x))
-#else
 #define SOFTROD_COLD_LIT(x) cold_literal<__builtin_bit_cast(unsigned long long, (double)(x))>()
-#endif
 
 // exp(x0), exp(x2) for any x: exp(x) = 2^n exp(r), n = rint(x log2 e), r = x - n ln 2 with ln 2 in two parts (fdlibm's split:
 // n ln2_hi is exact for |n| < 2^20), |r| <= ln 2 / 2 = 0.347, degree-13 Taylor (remainder r^14 / 14! < 5e-18), v_ldexp_f64.
@@ -513,7 +491,7 @@ __device__ __forceinline__ void dynamic_n(const RodParams& P, const ConstN<EPL>&
                 Fg[s][c] = f[s][c] + C.gm[s][c];     // (a per-lane constant: no select, no scalar operand)
             }
         }
-        if constexpr (SOFTROD_OCTO_CONTACT_LDS && F != kRuntimeFeatures && (F & SOFTROD_FEAT_OCTO_HEAD) != 0 && (F & kFeatPlaneZup) != 0)
+        if constexpr (F != kRuntimeFeatures && (F & SOFTROD_FEAT_OCTO_HEAD) != 0 && (F & kFeatPlaneZup) != 0)
             plane_contact_n<EPL, true, true, TAPER>(contact_params_lds(P), P, lane, C, L, xn, vn, len, Fg, tq, fc);
         else if (has<F>(P, kFeatPlaneZup))
             plane_contact_n<EPL, true, true, TAPER>(contact_params(P), P, lane, C, L, xn, vn, len, Fg, tq, fc);
@@ -848,7 +826,7 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
             // what it returns past lane 63, and the element after the last node has no stiffness either
             // way: results are unchanged.  (The 3-D loops carry the same mask, general_substeps, and so
             // do OctoFlat's ghost slots, softrod_octo.hpp.)
-            if (lane * EPL <= P.n_elem + (SOFTROD_PLANAR_EXEC_MASK == 2 ? 64 : 0)) {     // (2: the same code with no lane masked, an A/B control)
+            if (lane * EPL <= P.n_elem) {
 #endif
                 planar_kinematic_n<EPL>(P.half_dt, K.hq_hdt, C, K, Z);
                 {   // four copies of the loop, one per priority level (ProgressPriority explains; here

@@ -160,16 +160,6 @@ struct StatePtrs {
 // ---------------------------------------------------------------------------------
 // cross-lane: full-wave shift by one lane (GFX9 DPP wave_shl / wave_shr)
 // ---------------------------------------------------------------------------------
-#ifdef SOFTROD_USE_BPERMUTE
-__device__ __forceinline__ double from_next(double x) {
-    double y = __shfl_down(x, 1);
-    return (threadIdx.x & 63) == 63 ? 0.0 : y;
-}
-__device__ __forceinline__ double from_prev(double x) {
-    double y = __shfl_up(x, 1);
-    return (threadIdx.x & 63) == 0 ? 0.0 : y;
-}
-#else
 // lane k receives lane k+1's value; lane 63 receives 0.
 __device__ __forceinline__ double from_next(double x) {
     int lo = __double2loint(x), hi = __double2hiint(x);
@@ -184,7 +174,6 @@ __device__ __forceinline__ double from_prev(double x) {
     hi = __builtin_amdgcn_mov_dpp(hi, 0x138, 0xf, 0xf, true);
     return __hiloint2double(hi, lo);
 }
-#endif
 
 __device__ __forceinline__ double wave_sum(double x) {
 #pragma unroll
@@ -480,13 +469,10 @@ __device__ __forceinline__ void laplace_filter_rates_n(const RodParams& P, int l
 // its reflections go to LDS once; each entry then reads its 13 taps.  Per field: 13 FMAs and
 // 13 LDS reads instead of 6 x (4 DPP moves + 3 fp64 ops); the block is one wavefront, so
 // the barrier between the writes and the reads costs nothing.  Needs N >= 6.
-#ifndef SOFTROD_FILTER_V_LDS
-#define SOFTROD_FILTER_V_LDS 0      // how many of the three v fields take the LDS stencil as well (from v_z down); -1: omega_3 on DPP too
-#endif
 template <int EPL>
 __device__ __forceinline__ void laplace_filter_rates_lds7(const RodParams& P, int lane, LaneN<EPL>& L) {
-    constexpr int M = 6, W = kLanes * EPL, KV = SOFTROD_FILTER_V_LDS, NL = 3 + KV, ND = 3 - KV;
-    __shared__ double lds[NL][W + 2 * M];
+    constexpr int M = 6, W = kLanes * EPL;
+    __shared__ double lds[3][W + 2 * M];
     const int n = P.n_elem;
     // c_j for j = 0..6: C(12, 6+j) / 4096 with alternating sign
     constexpr double c[M + 1] = {924.0 / 4096.0, -792.0 / 4096.0, 495.0 / 4096.0, -220.0 / 4096.0,
@@ -511,8 +497,8 @@ __device__ __forceinline__ void laplace_filter_rates_lds7(const RodParams& P, in
             r[c3][s] = L.v[s][c3]; r[3 + c3][s] = L.w[s][c3];
         }
     }
-    // LDS row k holds field lfield(k): the omega fields, then v_z, v_y; the other v fields keep DPP
-    auto lfield = [](int k) { return k < 3 ? 3 + k : 5 - k; };      // 3, 4, 5, 2, 1
+    // LDS row k holds field lfield(k) = omega_k; the v fields keep DPP
+    auto lfield = [](int k) { return 3 + k; };
     // pass 1 in registers: the fields that go to LDS first, the others while those writes are on
     // their way (no measurable difference to "all six, then the writes")
     auto pass1 = [&](int fld) {
@@ -523,10 +509,10 @@ __device__ __forceinline__ void laplace_filter_rates_lds7(const RodParams& P, in
         for (int s = 0; s < EPL; ++s) f1[fld][s] = ((-nx[s] - pv[s]) + 2.0 * r[fld][s]) * q[fld / 3][s];
     };
 #pragma unroll
-    for (int k = 0; k < NL; ++k) pass1(lfield(k));
+    for (int k = 0; k < 3; ++k) pass1(lfield(k));
     // stage f_1 and its odd reflections
 #pragma unroll
-    for (int k = 0; k < NL; ++k) {
+    for (int k = 0; k < 3; ++k) {
         const int fld = lfield(k);
         const int N = (fld < 3) ? n : n - 1;
 #pragma unroll
@@ -537,18 +523,18 @@ __device__ __forceinline__ void laplace_filter_rates_lds7(const RodParams& P, in
             if (idx >= N - M && idx <= N - 1) lds[k][M + 2 * N - idx] = -f1[fld][s];
         }
     }
-    // register (DPP) field k: the v fields, then omega_3 (KV = -1: only two omega fields in LDS)
-    auto dfield = [](int k) { return k < 3 ? k : 8 - k; };       // 0, 1, 2, 5
+    // register (DPP) field k: v_k
+    auto dfield = [](int k) { return k; };
 #pragma unroll
-    for (int k = 0; k < ND; ++k) pass1(dfield(k));
+    for (int k = 0; k < 3; ++k) pass1(dfield(k));
     __syncthreads();
-    // The remaining six passes: in registers (DPP) for the first ND v fields, as the 13 taps out of
-    // LDS for the others.  Interleaved — the taps of an LDS field are requested before the DPP
+    // The remaining six passes: in registers (DPP) for the v fields, as the 13 taps out of LDS for
+    // the omega fields.  Interleaved — the taps of an LDS field are requested before the DPP
     // passes of a register field and summed after them, so that the LDS round trip runs under VALU
     // work of the same wave.
     double tap[M + 1][EPL], tpm[M + 1][EPL];
 #pragma unroll
-    for (int k = 0; k < NL; ++k) {
+    for (int k = 0; k < 3; ++k) {
         const int lf = lfield(k);
 #pragma unroll
         for (int s = 0; s < EPL; ++s) {
@@ -558,7 +544,7 @@ __device__ __forceinline__ void laplace_filter_rates_lds7(const RodParams& P, in
             for (int j = 1; j <= M; ++j) { tap[j][s] = row[M + j]; tpm[j][s] = row[M - j]; }
         }
 #pragma unroll
-        for (int kd = k; kd < ND; kd += NL) {       // (more register fields than LDS fields: several per turn)
+        for (int kd = k; kd < 3; kd += 3) {       // (one trip; as a loop, the form the shipped code is compiled from)
             const int fld = dfield(kd);
             double f[EPL], nx[EPL], pv[EPL];
 #pragma unroll
@@ -572,8 +558,7 @@ __device__ __forceinline__ void laplace_filter_rates_lds7(const RodParams& P, in
 #pragma unroll
             for (int s = 0; s < EPL; ++s) {
                 const int idx = slot_local(P, lane * EPL + s);
-                if (fld < 3) L.v[s][fld] = (idx <= n) ? r[fld][s] - f[s] : L.v[s][fld];
-                else L.w[s][fld - 3] = (idx < n) ? r[fld][s] - f[s] : L.w[s][fld - 3];
+                L.v[s][fld] = (idx <= n) ? r[fld][s] - f[s] : L.v[s][fld];
             }
         }
 #pragma unroll
@@ -584,8 +569,7 @@ __device__ __forceinline__ void laplace_filter_rates_lds7(const RodParams& P, in
             // (a select: outside the interior the taps read LDS words nobody wrote)
             const double out = r[lf][s] - (inner[lf / 3][s] ? acc : 0.0);
             const int idx = slot_local(P, lane * EPL + s);
-            if (lf < 3) L.v[s][lf] = (idx <= n) ? out : L.v[s][lf];
-            else L.w[s][lf - 3] = (idx < n) ? out : L.w[s][lf - 3];
+            L.w[s][lf - 3] = (idx < n) ? out : L.w[s][lf - 3];
         }
     }
     __syncthreads();     // the next substep overwrites the staging rows
@@ -669,9 +653,6 @@ namespace softrod {
 // contact constants therefore live in LDS and are read where they are used — LDS reads issue
 // beside the VALU, v_readlane issues ON it.  stage: once per workgroup before the first substep
 // (a barrier follows in the caller); fetch: per substep.
-#ifndef SOFTROD_OCTO_CONTACT_LDS
-#define SOFTROD_OCTO_CONTACT_LDS 1
-#endif
 // (one function owns the array, so that every access keeps its LDS address space: handed out as a
 // pointer it became a generic one, flat loads with a vector address per constant)
 // (and ONE function, not two instantiations of a template: each would own an array of its own)
@@ -1868,5 +1849,4 @@ softrod_autoreset_kernel(const RodParams P, const StatePtrs S, float* __restrict
 
 #include "softrod_fast.hpp"
 #include "softrod_octo.hpp"
-#include "softrod_octo1w.hpp"
 #include "softrod_window.hpp"

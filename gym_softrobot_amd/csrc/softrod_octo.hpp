@@ -187,13 +187,10 @@ __device__ __forceinline__ int octo_obs_dim(const RodParams& P) {
 // other's joint loads the other is the one running, so the wait costs no SIMD time, and the
 // rendezvous becomes a flag in LDS (release / acquire at workgroup scope) instead of a
 // workgroup-wide s_barrier that would couple four unrelated envs.
-// SOFTROD_OCTO_PRIO: a wave's issue priority until it has posted its joint loads of the substep; 0
-// after.  The partner that has NOT posted is the one the SIMD serves first, so the wave that runs
+// A wave issues at priority 1 until it has posted its joint loads of the substep, at 0 after
+// (s_setprio).  The partner that has NOT posted is the one the SIMD serves first, so the wave that runs
 // ahead (the arbiter favours the older wave) finds the partner's flag set when it gets to the
 // rendezvous instead of sleeping on it: 11.72 -> 11.57 ms (profiles/README.md, r2k).
-#ifndef SOFTROD_OCTO_PRIO
-#define SOFTROD_OCTO_PRIO 1
-#endif
 // The muscle-arm instantiations (taper table, three muscle layers, suckers on top of the rod, joint and head code) want ~330
 // registers: at two waves per SIMD (256) they park 217 of them in scratch and the loop waits on it — 12 GB of HBM traffic per
 // env.step of 4096 OctoArmPullWeight envs, VALU busy 0.37.  ONE wave per SIMD (512 registers, no spills in the loop) is
@@ -235,7 +232,7 @@ softrod_octo_step_kernel(const RodParams P, const StatePtrs S, const float* __re
     const int n = P.n_elem, nk = P.n_action;
     const int r = tid & (P.seg - 1), arm = tid >> P.seg_shift;
     const bool arm_ok = arm < P.n_arm;
-    if constexpr (SOFTROD_OCTO_CONTACT_LDS && (F & kFeatPlaneZup) != 0) stage_contact_params(P);   // (barriers follow)
+    if constexpr ((F & kFeatPlaneZup) != 0) stage_contact_params(P);   // (barriers follow)
     if (tid < 2 * MAXW * 4) (&xch[0][0][0])[tid] = 0.0;   // rows of absent waves read as zero loads
     if constexpr (EPB == 1) __syncthreads();     // the staged tables are there before any wave reads them (EPB > 1: below)
     if (EPB > 1 && tid < 2 * MAXW) (&flag_[es][0][0])[tid] = 0;
@@ -350,20 +347,9 @@ softrod_octo_step_kernel(const RodParams P, const StatePtrs S, const float* __re
 #ifndef SOFTROD_OCTO_DIAG
 #define SOFTROD_OCTO_DIAG 0
 #endif
-// SOFTROD_OCTO_BASE_MASK (A/B switch, default 0 = off; bit 1: the joint evaluation, bit 2: the head's step run
-// with EXEC restricted to the base lanes, 4 of 64 — only they consume the head's state inside the loop; the head
-// is broadcast from lane 0 after the loop).  The idea: the instruction count is unchanged (a wave instruction
-// costs its issue slot whatever its mask) but masked lanes do not switch, and this kernel runs against the
-// board's power limit.  MEASURED AND NOT ADOPTED (round 5, profiles/README.md "OctoFlat budget"): 9.26-9.29 ms
-// against 9.31-9.34 ms per launch on one box (-0.5 %, inside the box-to-box spread), and with BOTH bits set the
-// one-arm shape (OctoFlatLite-v0, one wave per env) aborts on the GPU while either bit alone passes - a
-// code-generation hazard nobody needs for half a per cent.
-#ifndef SOFTROD_OCTO_BASE_MASK
-#define SOFTROD_OCTO_BASE_MASK 0
-#endif
     auto joints = [&](double (&f)[1][3], double (&tq)[1][3], const LaneN<1>& Lc, const double (&xn)[1][3]) {
         double part[3] = {0.0, 0.0, 0.0};
-        if ((SOFTROD_OCTO_DIAG & 1) == 0 && (!(SOFTROD_OCTO_BASE_MASK & 1) || base)) {
+        if ((SOFTROD_OCTO_DIAG & 1) == 0) {
         // FixedJoint2Rigid.apply_forces (joint.py:48-123): spring + normal damping between the
         // arm's node 0 and the point head_radius along the arm's direction from the head axis.
         // The head's d2 lies in the plane (constrain_values), so the direction has no z part.
@@ -426,9 +412,7 @@ softrod_octo_step_kernel(const RodParams P, const StatePtrs S, const float* __re
             if constexpr (EPB > 1)
                 __hip_atomic_store(&flag_[es][parity][wave], posted + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
-#if SOFTROD_OCTO_PRIO
         if constexpr (EPB > 1) __builtin_amdgcn_s_setprio(0);     // posted: yield to the partner that has not
-#endif
     };
     // RigidBodyBase.update_accelerations + the rate update under
     // BodyBoundaryCondition.compute_constrain_rates (constraint.py:60-85): with
@@ -451,7 +435,6 @@ softrod_octo_step_kernel(const RodParams P, const StatePtrs S, const float* __re
     auto head_step = [&]() {
         if constexpr ((SOFTROD_OCTO_DIAG & 2) != 0) return;
         if constexpr (kMuscleArm) { if (P.head_fixed) return; }      // OneEndFixedBC: the head stays what the reset made it
-        if constexpr ((SOFTROD_OCTO_BASE_MASK & 2) != 0) { if (!base) return; }
         double tot[3];
 #pragma unroll
         for (int i = 0; i < 3; ++i) tot[i] = (MAXW == 2) ? pend[0][i] + pend[MAXW == 2 ? 1 : 0][i] : pend[0][i];
@@ -519,9 +502,7 @@ softrod_octo_step_kernel(const RodParams P, const StatePtrs S, const float* __re
         head_normalize(H);                       // hk = dt/2 and zero loads: the head's first half step
         head_step();
         for (int s = 0; s < n_sub; ++s) {
-#if SOFTROD_OCTO_PRIO
-            if constexpr (EPB > 1) __builtin_amdgcn_s_setprio(SOFTROD_OCTO_PRIO);
-#endif
+            if constexpr (EPB > 1) __builtin_amdgcn_s_setprio(1);
             dynamic_n<F, 1, kMusclesCompiled<F>>(Pk, C, B, tid, L, joints);
             const bool last = (s == n_sub - 1);
             const double h = last ? P.half_dt : P.dt;
@@ -531,14 +512,6 @@ softrod_octo_step_kernel(const RodParams P, const StatePtrs S, const float* __re
             head_step();
         }
         time = clock_after(P, S, time, n_sub);
-    }
-    if constexpr ((SOFTROD_OCTO_BASE_MASK & 2) != 0) {
-        // only the base lanes stepped the head inside the loop: everybody gets lane 0's for the epilogue
-        // (all base lanes hold the same bits: the same operands in the same order)
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { H.x[i] = __shfl(H.x[i], 0); H.v[i] = __shfl(H.v[i], 0); H.w[i] = __shfl(H.w[i], 0); }
-#pragma unroll
-        for (int i = 0; i < 9; ++i) H.Q[i] = __shfl(H.Q[i], 0);
     }
     if (live) {
         store_lane<1, F>(S, NR, row, lane, L);

@@ -67,9 +67,6 @@ __device__ __forceinline__ void window_store(const StatePtrs& S, size_t N, int r
 // barrier that would couple four unrelated rods: exchange k writes buffer k & 1 and raises the
 // wave's counter to k + 1; the partner cannot be more than one exchange ahead (it waits for this
 // wave's counter before it reads), so buffer k & 1 is free again by the time exchange k + 2 writes it.
-#ifndef SOFTROD_WINDOW_PRIO
-#define SOFTROD_WINDOW_PRIO 1
-#endif
 template <unsigned F, int RPB = 1>
 __global__ void __launch_bounds__(2 * kLanes * RPB, SOFTROD_CONTACT_WAVES)
 softrod_step_window_kernel(const RodParams P, const StatePtrs S, const float* __restrict__ actions,
@@ -206,7 +203,6 @@ softrod_step_window_kernel(const RodParams P, const StatePtrs S, const float* __
         kinematic_n<1>(P.half_dt, C, L);
         int since = 0;
         for (int s = 0; s < n_sub; ++s) {
-#if SOFTROD_WINDOW_PRIO
             // The two windows of a rod share a SIMD (RPB = 4).  The arbiter serves the older wave
             // first, so one window would run ahead to the rendezvous and sleep while the other
             // finishes ALONE, at a lone wave's issue rate.  A wave's priority falls as it advances
@@ -217,7 +213,6 @@ softrod_step_window_kernel(const RodParams P, const StatePtrs S, const float* __
                 else if (since == 1) __builtin_amdgcn_s_setprio(1);
                 else __builtin_amdgcn_s_setprio(0);
             }
-#endif
             dynamic_n<F, 1>(Pk, C, B, gi, L);
             const bool last = (s == n_sub - 1);
             kinematic_n<1>(last ? P.half_dt : P.dt, C, L);

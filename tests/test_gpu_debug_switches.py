@@ -1,6 +1,6 @@
 """Product-library hygiene (VERDICT r4 "next" #7):
 
-* the A/B switches of the measurement builds (SOFTROD_OCTO_ONE_WAVE, SOFTROD_NO_WINDOW, ...) change the
+* the A/B switches of the measurement builds (SOFTROD_NO_WINDOW, ...) change the
   kernel tier ONLY together with SOFTROD_DEBUG_SWITCHES=1 — a stray variable in a product process does
   nothing (softrod_kernel_tier, ABI v15, reports what softrod_create selected);
 * softrod_autoreset_enable frees what it allocated when it fails mid-way and can be retried.
@@ -19,7 +19,7 @@ def torch_gpu():
     return torch
 
 
-def test_stray_switches_do_not_change_the_kernel_tier(torch_gpu, hip_lib, monkeypatch):
+def test_switches_change_the_kernel_tier_only_behind_the_gate(torch_gpu, hip_lib, monkeypatch):
     from gym_softrobot_amd import _capi
     from gym_softrobot_amd.backend import HipRodBackend
 
@@ -40,8 +40,8 @@ def test_stray_switches_do_not_change_the_kernel_tier(torch_gpu, hip_lib, monkey
         assert be.kernel_tier() == plain[name]
         be.close()
     monkeypatch.setenv("SOFTROD_DEBUG_SWITCHES", "1")                 # with the gate they are honoured
-    be = HipRodBackend(octo, device=0)
-    assert "octo1w" in be.kernel_tier()
+    be = HipRodBackend(octo, device=0)                                # the retired OctoFlat switches stay retired
+    assert be.kernel_tier() == "softrod_octo_step_kernel<zup,2 waves,4 envs/wg>"
     be.close()
     be = HipRodBackend(arm, device=0)
     assert "window" not in be.kernel_tier() and "epl=2" in be.kernel_tier()

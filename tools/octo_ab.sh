@@ -3,33 +3,24 @@
 # the GPU box — their timing and VALU busy fraction on the configs[4] share (1024 envs):
 #   tools/octo_ab.sh build                      (here: hipcc cross-compiles)
 #   tools/octo_ab.sh run <tag>                  (on the box, via gpurun) -> gpurun_out/octo_ab_<tag>.txt
-# Variants: r4 = the shipped kernel, basemask = joints and head step under the base-lane EXEC mask,
-# diagN = SOFTROD_OCTO_DIAG=N (timing only: results are wrong by construction); round 6: r6 = the shipped kernel,
-# thetaloop = round 5's large-angle tier of theta/sin(theta), waves3 = the kernel capped at 168 registers (what a ninth,
-# coupling wave per workgroup would leave each arm wave: three waves on one SIMD).  Every run is bounded by
+# Variants: r4 = the shipped kernel, diagN = SOFTROD_OCTO_DIAG=N (timing only: results are wrong by construction);
+# round 6: r6 = the shipped kernel, waves3 = the kernel capped at 168 registers (what a ninth, coupling wave per
+# workgroup would leave each arm wave: three waves on one SIMD).  Every run is bounded by
 # `timeout`: a diagnostic build that breaks the rendezvous must not hold the box.
 set -u
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 declare -A FLAGS=(
   [r4]=""
-  [basemask]="-DSOFTROD_OCTO_BASE_MASK=1"
   [diag4]="-DSOFTROD_OCTO_DIAG=4"
   [diag8]="-DSOFTROD_OCTO_DIAG=8"
   [diag12]="-DSOFTROD_OCTO_DIAG=12"
   [diag1]="-DSOFTROD_OCTO_DIAG=1"
   [diag2]="-DSOFTROD_OCTO_DIAG=2"
   [diag7]="-DSOFTROD_OCTO_DIAG=7"
-  [nolds]="-DSOFTROD_OCTO_CONTACT_LDS=0"
-  [diag7_nolds]="-DSOFTROD_OCTO_DIAG=7 -DSOFTROD_OCTO_CONTACT_LDS=0"
-  [nomaskbase]="-DSOFTROD_OCTO_BASE_MASK=0"
-  [maskjoints]="-DSOFTROD_OCTO_BASE_MASK=1"
-  [maskhead]="-DSOFTROD_OCTO_BASE_MASK=2"
   [r6]=""
-  [thetaloop]="-DSOFTROD_DIAG_THETA_LOOP"
   [waves3]="-DSOFTROD_OCTO_WAVES=3"
-  [hoistlit]="-DSOFTROD_DIAG_HOIST_LITERALS"
 )
-NAMES=${OCTO_AB_VARIANTS:-r4 basemask diag4 diag8 diag12 diag1 diag2 diag7}
+NAMES=${OCTO_AB_VARIANTS:-r4 diag4 diag8 diag12 diag1 diag2 diag7}
 if [ "${1:-}" = build ]; then
   mkdir -p "$ROOT/variants"
   for n in $NAMES; do
