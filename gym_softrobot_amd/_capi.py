@@ -10,7 +10,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 # softrod_feature (include/softrod.h)
 FEAT_GRAVITY = 1 << 0
@@ -145,7 +145,7 @@ class SoftrodConfig(C.Structure):
         ("arm_target", C.c_double * 3),
         ("n_suckers", C.c_int32),
         ("sucker_index", C.c_int32 * 4),
-        ("reserved2", C.c_int32),
+        ("early_termination", C.c_int32),
         ("sucker_reduction_ratio", C.c_double),
         ("n_muscles", C.c_int32),
         ("muscle_kind", C.c_int32 * 4),
@@ -441,11 +441,13 @@ def arm_push_config(
     recording_fps: int = 40,
     mode: str = "discrete",
     math_mode: int = MATH_FAST,
+    early_termination: bool = False,
 ) -> SoftrodConfig:
     """`softrod_config_arm_push`: ArmPushEnv.__init__ (octopus/arm_push_env.py:65-139) and `_build`
     (:158-224): a 40-element arm of length 0.2, density 700, E = 1e4, G = E / 1.5, tapered 12:1
     (arm_push_radii -> softrod_set_radius_profile), AnalyticalLinearDamper(0.05 * 2 * 1e2), one
-    ControllableFixConstraint at index 0 and ApplyMuscles over create_es_muscle_layers.  No gravity, no plane."""
+    ControllableFixConstraint at index 0 and ApplyMuscles over create_es_muscle_layers.  No gravity, no plane.
+    `early_termination`: config_early_termination, the Hamiltonian cut-off of step() (:310-313, 441-456)."""
     if mode not in ("discrete", "continuous"):
         raise NotImplementedError(f"The mode {mode} is not available.")            # arm_push_env.py:97
     cfg = SoftrodConfig()
@@ -465,6 +467,7 @@ def arm_push_config(
     # _build registers dampen() BEFORE constrain() (:180-195; tests/golden/ref_muscle_build_records.json "order"):
     # under the registration-order rule the damper runs first here (the other builds register constrain() first)
     cfg.damp_before_constrain = 1
+    cfg.early_termination = int(bool(early_termination))
     muscle_defaults(cfg)
     return cfg
 
@@ -476,13 +479,14 @@ def arm_pull_weight_config(
     recording_fps: int = 40,
     mode: str = "continuous",
     math_mode: int = MATH_FAST,
+    early_termination: bool = False,
 ) -> SoftrodConfig:
     """`softrod_config_arm_pull_weight`: ArmPullWeightEnv (octopus/arm_push_env.py:516-618) — ArmPushEnv with
     time_step 2.5e-5 (:518), damper 0.05 * 2 * 5e2 (:549), a rigid Cylinder "weight" (:552-567) held by
     BodyBoundaryCondition (:569-575) and joined to the arm's node 0 by FixedJoint2Rigid(k=1e6, nu=1e-2, kt=1, angle=0,
     radius=0.015) (:577-589), the sucker at reduction_ratio 0.9 (:591-599)."""
     cfg = arm_push_config(n_envs, final_time=final_time, time_step=2.5e-5, recording_fps=recording_fps, mode=mode,
-                          math_mode=math_mode)
+                          math_mode=math_mode, early_termination=early_termination)
     cfg.features = FEATURES_ARM_PULL_WEIGHT
     cfg.env_kind = ENV_ARM_PULL_WEIGHT
     cfg.damping_constant = 0.05 * 2 * 5e2
@@ -713,6 +717,11 @@ def config_obs_dim(cfg: "SoftrodConfig") -> int:
     return obs_dim(cfg.env_kind)
 
 
+def config_rods_per_env(cfg: "SoftrodConfig") -> int:
+    """Rods per env of softrod_rod_energies: n_arm for OctoFlat and the muscle octopus, else 1."""
+    return int(cfg.n_arm) if int(cfg.env_kind) == ENV_OCTO_FLAT or int(cfg.env_kind) in MUSCLE_OCTOPUS_ENVS else 1
+
+
 class SoftrodError(RuntimeError):
     pass
 
@@ -759,6 +768,7 @@ _EXPORTS = {
     "softrod_exchange_close": (C.c_int, [C.c_int, _VP]),
     "softrod_exchange_free": (C.c_int, [C.c_int, _VP]),
     "softrod_observe": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "softrod_rod_energies": (C.c_int, [_VP, _VP, _VP]),
     "softrod_substeps": (C.c_int, [_VP, _VP, C.c_int, _VP]),
     "softrod_state_view_get": (C.c_int, [_VP, C.POINTER(SoftrodStateView)]),
     "softrod_set_timing": (C.c_int, [_VP, C.c_int]),

@@ -259,6 +259,23 @@ class HipRodBackend:
         )
         return self.obs, self.reward, self.terminated, self.truncated
 
+    supports_early_termination = True     # softrod_config.early_termination runs in the step kernels' epilogue
+
+    def rod_energies(self) -> torch.Tensor:
+        """softrod_rod_energies: (n_envs, rods_per_env, 4) float64 device tensor — translational, rotational,
+        bending, shear energy of every rod at PyElastica's instant (the mid-substep strains of the last force
+        evaluation with the end-of-step rates; the state itself right after a reset).  Overwritten by the next call."""
+        if getattr(self, "_energies", None) is None:
+            self._energies = torch.empty((self.n_envs, _capi.config_rods_per_env(self.cfg), 4), dtype=torch.float64,
+                                         device=self.device)
+        check(self._lib.softrod_rod_energies(self._h, self._energies.data_ptr(), self._stream()), self._h)
+        return self._energies
+
+    def time_limit(self) -> torch.Tensor:
+        """early_termination handles: the last step's time-limit flag per env (row 0 of softrod_state_view.env_aux)
+        as a bool device tensor — info["TimeLimit.truncated"], which `truncated` no longer is."""
+        return self.state()["env_aux"][0] != 0.0
+
     def step_packed(self, actions, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """softrod_step_packed: (n_envs, packed_width(obs_dim)) float32 words per env, into
         `out` if given (the overlapped multi-GPU path alternates two buffers)."""
@@ -362,6 +379,7 @@ class HipRodBackend:
         ns = n * (int(self.cfg.n_arm) if self.is_mocto else 1)      # SuckerControllers: per env, per arm of the muscle octopus
         if v.env_aux:
             extra["env_aux"] = torch.as_tensor(_DevArray(v.env_aux, (8, n), "<f8", self), device=self.device)
+        if v.prev_kappa:
             extra["prev_kappa"] = torch.as_tensor(
                 _DevArray(v.prev_kappa, (n, int(self.cfg.n_arm) * (int(self.cfg.n_elem) - 1)), "<f4", self), device=self.device)
         if v.muscle_activation:

@@ -235,6 +235,7 @@ void fill_params(const softrod_config& c, RodParams& P) {
     for (int i = 0; i < 3; ++i) P.arm_target[i] = c.arm_target[i];
     P.n_suckers = c.n_suckers;
     for (int j = 0; j < SOFTROD_MAX_SUCKERS; ++j) P.sucker_index[j] = c.sucker_index[j];
+    if (c.early_termination) P.features |= kFeatEarlyTerm;
     P.sucker_ratio0 = c.sucker_reduction_ratio;
     // COOMM muscle layers
     P.n_muscles = (c.features & SOFTROD_FEAT_COOMM_MUSCLES) ? c.n_muscles : 0;
@@ -285,10 +286,19 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
         if (!push && h->tapered)
             return fail(h, SOFTROD_EINVAL, "a tapered muscle rod outside SOFTROD_ENV_ARM_PUSH runs under SOFTROD_MATH_LIBM only");
     }
+    if (h->cfg.early_termination && h->cfg.math_mode == SOFTROD_MATH_FAST && !(is_octo(h) && is_pull(h)) &&
+        !(h->tapered && h->cfg.features == SOFTROD_FEATURES_ARM_PUSH && h->cfg.env_kind == SOFTROD_ENV_ARM_PUSH))
+        // only the instantiations FOR the flag evaluate it (kFeatEarlyTerm): never let another kernel ignore it
+        return fail(h, SOFTROD_EINVAL, "early_termination (SOFTROD_MATH_FAST) runs on the tapered SOFTROD_FEATURES_ARM_PUSH arm "
+                                       "and on SOFTROD_ENV_ARM_PULL_WEIGHT only; other feature mixes: SOFTROD_MATH_LIBM");
     const bool timing = h->timed < (int)h->ev_start.size();
     if (timing) SR_HIP(h, hipEventRecord(h->ev_start[h->timed], st));
     const bool zup = (h->P.features & kFeatPlaneZup) != 0;
     if (is_octo(h) && is_pull(h)) {
+        if (h->cfg.early_termination)
+            hipLaunchKernelGGL((softrod_octo_step_kernel<SOFTROD_FEATURES_ARM_PULL_WEIGHT | kFeatEarlyTerm, 2, 1>), grid, block,
+                               0, st, h->P, h->S, actions, obs, reward, term, trunc, n_sub, epilogue, pack);
+        else
         hipLaunchKernelGGL((softrod_octo_step_kernel<SOFTROD_FEATURES_ARM_PULL_WEIGHT, 2, 1>), grid, block, 0, st, h->P, h->S,
                            actions, obs, reward, term, trunc, n_sub, epilogue, pack);
     } else if (is_mocto(h)) {
@@ -365,6 +375,8 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
                 SR_LAUNCH_TAPER(SOFTROD_FEATURES_ARM_SINGLE | kFeatPlaneZup, SOFTROD_ENV_ARM_SINGLE);
             else if (f == kFeaturesTaperedSuckerArm && e == SOFTROD_ENV_NONE)
                 SR_LAUNCH_TAPER(kFeaturesTaperedSuckerArm, SOFTROD_ENV_NONE);
+            else if (f == SOFTROD_FEATURES_ARM_PUSH && e == SOFTROD_ENV_ARM_PUSH && h->cfg.early_termination)
+                SR_LAUNCH_TAPER(SOFTROD_FEATURES_ARM_PUSH | kFeatEarlyTerm, SOFTROD_ENV_ARM_PUSH);
             else if (f == SOFTROD_FEATURES_ARM_PUSH && e == SOFTROD_ENV_ARM_PUSH)     // OctoArmPush-v0 / -v1
                 SR_LAUNCH_TAPER(SOFTROD_FEATURES_ARM_PUSH, SOFTROD_ENV_ARM_PUSH);
             else
@@ -373,8 +385,11 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
         } else if (h->epl == 2) SR_DISPATCH(2); else SR_DISPATCH(1);
 #undef SR_DISPATCH
 #undef SR_LAUNCH
+    } else if (h->cfg.early_termination) {
+        hipLaunchKernelGGL(softrod_step_libm_kernel<true>, grid, block, 0, st, h->P, h->S,
+                           actions, obs, reward, term, trunc, aux, n_sub, epilogue, pack);
     } else
-        hipLaunchKernelGGL(softrod_step_libm_kernel, grid, block, 0, st, h->P, h->S,
+        hipLaunchKernelGGL(softrod_step_libm_kernel<false>, grid, block, 0, st, h->P, h->S,
                            actions, obs, reward, term, trunc, aux, n_sub, epilogue, pack);
     SR_HIP(h, hipGetLastError());
     if (timing) {
@@ -817,6 +832,11 @@ int softrod_create(const softrod_config* cfg, int device, softrod_handle** out) 
     }
     if ((cfg->features & SOFTROD_FEAT_LAPLACE_FILTER) && (cfg->filter_order < 1 || cfg->n_elem < 3))
         return fail(nullptr, SOFTROD_EINVAL, "LaplaceDissipationFilter needs filter_order >= 1");
+    if (cfg->early_termination != 0 && cfg->early_termination != 1)
+        return fail(nullptr, SOFTROD_EINVAL, "early_termination is 0 or 1");
+    if (cfg->early_termination && cfg->env_kind != SOFTROD_ENV_ARM_PUSH && cfg->env_kind != SOFTROD_ENV_ARM_PULL_WEIGHT)
+        return fail(nullptr, SOFTROD_EINVAL,
+                    "early_termination (ArmPushEnv's Hamiltonian cut-off) exists for SOFTROD_ENV_ARM_PUSH / ARM_PULL_WEIGHT only");
     {
         const unsigned bcs = cfg->features & (SOFTROD_FEAT_PENDULUM_BC | SOFTROD_FEAT_FIXED_BC |
                                               SOFTROD_FEAT_MOVING_BASE_BC);
@@ -918,6 +938,10 @@ int softrod_create(const softrod_config* cfg, int device, softrod_handle** out) 
     h->S.sucker = h->d_sucker;
     alloc((void**)&h->d_sucker_idx, (size_t)SOFTROD_MAX_SUCKERS * NS * sizeof(int));
     h->S.sucker_idx = h->d_sucker_idx;
+    if (cfg->early_termination) {     // row 0: the step's time-limit flag (softrod_state_view.env_aux)
+        alloc((void**)&h->d_aux, (size_t)8 * N * sizeof(double));
+        h->S.aux = h->d_aux;
+    }
     if (mocto) {
         alloc((void**)&h->d_aux, (size_t)8 * N * sizeof(double));
         alloc((void**)&h->d_prev_kappa, N * (size_t)cfg->n_arm * (size_t)(cfg->n_elem - 1) * sizeof(float));
@@ -1594,6 +1618,23 @@ int softrod_observe(softrod_handle* h, const float* prev_action, float* obs, voi
     else
         hipLaunchKernelGGL(softrod_observe_kernel<1>, grid, block, 0, (hipStream_t)stream, h->P, h->S,
                            prev_action, obs);
+    SR_HIP(h, hipGetLastError());
+    return SOFTROD_OK;
+}
+
+int softrod_rod_energies(softrod_handle* h, double* out, void* stream) {
+    if (!h || !out) return fail(h, SOFTROD_EINVAL, "null argument");
+    SR_ON_DEVICE(h);
+    const bool arms = is_flat(h) || is_mocto(h);
+    const int rods = arms ? h->cfg.n_arm : 1;
+    const int lane_stride = kLanes * h->epl * h->nw, arm_stride = arms ? h->P.seg : 0;
+    const dim3 grid((unsigned)(h->cfg.n_envs * rods)), block(kLanes);
+    if (h->epl == 2)
+        hipLaunchKernelGGL(softrod_rod_energies_kernel<2>, grid, block, 0, (hipStream_t)stream, h->P, h->S, rods,
+                           lane_stride, arm_stride, out);
+    else
+        hipLaunchKernelGGL(softrod_rod_energies_kernel<1>, grid, block, 0, (hipStream_t)stream, h->P, h->S, rods,
+                           lane_stride, arm_stride, out);
     SR_HIP(h, hipGetLastError());
     return SOFTROD_OK;
 }

@@ -747,6 +747,7 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
     const size_t N = (size_t)P.n_envs;
     if (epilogue && S.skip && S.skip[rod]) {   // reset by the auto-reset pass of this env.step
         if (lane == 0) S.skip[rod] = 0;
+        if (lane == 0 && early_term_on<F>(P)) S.aux[rod] = 0.0;   // no time limit on a restart
         return;
     }
 
@@ -895,7 +896,7 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
     if (lane == 0) S.time[rod] = time;
     SR_PHASE(4);
     if (epilogue)
-        env_epilogue_n<E, EPL>(P, S, N, rod, lane, C, L, time, A, obs, reward, terminated, truncated, aux, pack);
+        env_epilogue_n<E, EPL, F>(P, S, N, rod, lane, C, L, time, A, obs, reward, terminated, truncated, aux, pack);
     SR_PHASE(5);
 }
 

@@ -56,6 +56,10 @@ constexpr unsigned kFeaturesTaperedSuckerArm = SOFTROD_FEAT_ANALYTICAL_DAMPER | 
 // Internal pseudo-feature (never in softrod_config.features): the contact plane's normal is
 // exactly e_z, set by the host in RodParams.features and in the template mask.
 constexpr unsigned kFeatPlaneZup = 1u << 30;
+// Internal pseudo-feature: softrod_config.early_termination (ArmPushEnv's Hamiltonian cut-off, set by the host in
+// RodParams.features and in the template mask of the instantiations that carry it, so that the default ones compile
+// none of it)
+constexpr unsigned kFeatEarlyTerm = 1u << 29;
 constexpr int kRuntimeEnv = -1;
 // The fast kernel carries the COOMM muscle layers (softrod_muscle.hpp) in the instantiations compiled FOR a feature
 // set that has them: OctoArmPush (SOFTROD_FEATURES_ARM_PUSH) and the clamped / free muscle rod of the known-answer
@@ -185,6 +189,14 @@ template <unsigned F>
 __device__ __forceinline__ bool has(const RodParams& P, unsigned bit) {
     if constexpr (F == kRuntimeFeatures) return (P.features & bit) != 0;
     else return (F & bit) != 0;
+}
+// kFeatEarlyTerm is compiled into the instantiations FOR it only: the fast ones whose mask carries it and the LIBM
+// kernel's ET instantiation (RT = true: it reads the run-time mask); launch_step refuses a flagged handle any other
+// kernel would step
+template <unsigned F, bool RT = false>
+__device__ __forceinline__ bool early_term_on(const RodParams& P) {
+    if constexpr (F != kRuntimeFeatures) return (F & kFeatEarlyTerm) != 0;
+    else return RT && (P.features & kFeatEarlyTerm) != 0;
 }
 template <int E>
 __device__ __forceinline__ int env_of(const RodParams& P) {
@@ -932,7 +944,146 @@ __device__ __forceinline__ void env_observe_n(const RodParams& P, const StatePtr
     }
 }
 
-template <int E, int EPL>
+// ---------------------------------------------------------------------------------
+// The rod's four energies (softrod_rod_energies; ArmPushEnv.cal_desired_Hamiltonian,
+// octopus/arm_push_env.py:446-456).  THE FORMS are our recollection of pyelastica 1.0.0's
+// compute_{translational,rotational,bending,shear}_energy (not on disk):
+//   translational  1/2 sum_i m_i |v_i|^2
+//   rotational     1/2 sum_e omega_e . (J_e omega_e) / e_e
+//   bending        1/2 sum_k (kappa_k - kappa^_k) . B_k (kappa_k - kappa^_k) D^_k
+//   shear          1/2 sum_e sigma_e . S_e sigma_e l^_e
+// THE INSTANT is PyElastica's: sigma, kappa and the dilatation e are the caches of the last
+// force evaluation, i.e. of the mid-substep configuration x - dt/2 v, R(dt/2 omega)^T Q (then
+// the boundary condition's constrain_values), while v and omega are the end-of-step rates
+// (diagnostics.mid_substep_configuration).  time == 0 (a reset, no substep yet): the state as
+// it stands.  The rod starts at lane 0 of the wave (slot j = lane * EPL + s is node / element
+// j); `mat` is the tapered rod's material table (indexed by j) or nullptr (uniform: RodParams);
+// `B` the boundary condition's targets (`bc` false: constrain_values is a no-op).  Out of
+// the substep path: libm acos / sin / cos.  -> E[4] = translational, rotational, bending, shear
+// (the same in every lane).
+// ---------------------------------------------------------------------------------
+template <int EPL>
+__device__ __forceinline__ void rod_energies_n(const RodParams& P, const double* __restrict__ mat, const BcTargets& B,
+                                               bool bc, int lane, const LaneN<EPL>& L, double time, double (&E)[4]) {
+    const int n = P.n_elem;
+    const bool mid = time != 0.0;
+    const double h = P.half_dt;
+    double x[EPL][3], Q[EPL][9];
+#pragma unroll
+    for (int s = 0; s < EPL; ++s) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) x[s][c] = mid ? L.x[s][c] - h * L.v[s][c] : L.x[s][c];
+        // Q_mid = R^T Q with R the (transposed-Rodrigues) kinematic rotation of diagnostics.half_step_rotation
+        const double* w = L.w[s];
+        const double th = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+        const double ia = 1.0 / (th + P.eps_rot_axis);
+        const double a0 = w[0] * ia, a1 = w[1] * ia, a2 = w[2] * ia;
+        const double up = sin(th * h), usq = 1.0 - cos(th * h);
+        double R[9];
+        R[0] = 1.0 - usq * (a1 * a1 + a2 * a2);
+        R[4] = 1.0 - usq * (a0 * a0 + a2 * a2);
+        R[8] = 1.0 - usq * (a0 * a0 + a1 * a1);
+        R[1] = up * a2 + usq * a0 * a1;
+        R[3] = -up * a2 + usq * a0 * a1;
+        R[2] = -up * a1 + usq * a0 * a2;
+        R[6] = up * a1 + usq * a0 * a2;
+        R[5] = up * a0 + usq * a1 * a2;
+        R[7] = -up * a0 + usq * a1 * a2;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int l = 0; l < 3; ++l)
+                Q[s][3 * i + l] = mid ? R[i] * L.Q[s][l] + R[3 + i] * L.Q[s][3 + l] + R[6 + i] * L.Q[s][6 + l]
+                                      : L.Q[s][3 * i + l];
+    }
+    if (mid && bc && lane == 0) {   // constrain_values on node 0 / element 0 (constrain_values_host)
+        if (P.features & SOFTROD_FEAT_PENDULUM_BC) {
+            x[0][1] = B.pos[1]; x[0][2] = B.pos[2];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { Q[0][j] = B.Q[j]; Q[0][6 + j] = B.Q[6 + j]; }
+        }
+        if (P.features & (SOFTROD_FEAT_FIXED_BC | SOFTROD_FEAT_MOVING_BASE_BC)) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) x[0][j] = B.pos[j];
+#pragma unroll
+            for (int j = 0; j < 9; ++j) Q[0][j] = B.Q[j];
+        }
+    }
+    double xn[EPL][3], Qn[EPL][9];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double a[EPL], o[EPL];
+#pragma unroll
+        for (int s = 0; s < EPL; ++s) a[s] = x[s][c];
+        shift_next<EPL>(a, o);
+#pragma unroll
+        for (int s = 0; s < EPL; ++s) xn[s][c] = o[s];
+    }
+#pragma unroll
+    for (int c = 0; c < 9; ++c) {
+        double a[EPL], o[EPL];
+#pragma unroll
+        for (int s = 0; s < EPL; ++s) a[s] = Q[s][c];
+        shift_next<EPL>(a, o);
+#pragma unroll
+        for (int s = 0; s < EPL; ++s) Qn[s][c] = o[s];
+    }
+    const bool rest_kappa = (P.features & SOFTROD_FEAT_REST_KAPPA_ACTION) != 0;
+    double et = 0.0, er = 0.0, eb = 0.0, es = 0.0;
+#pragma unroll
+    for (int s = 0; s < EPL; ++s) {
+        const int j = lane * EPL + s;
+        if (j <= n) {
+            const double m = mat ? mat[(size_t)kMatMass * kLanes + j]
+                                 : ((j == 0 || j == n) ? 0.5 * P.mass_node : P.mass_node);
+            et += m * (L.v[s][0] * L.v[s][0] + L.v[s][1] * L.v[s][1] + L.v[s][2] * L.v[s][2]);
+        }
+        if (j < n) {
+            const double J0 = mat ? mat[(size_t)kMatJ0 * kLanes + j] : P.J[0];
+            const double J1 = mat ? J0 : P.J[1];
+            const double J2 = mat ? mat[(size_t)kMatJ2 * kLanes + j] : P.J[2];
+            const double S0 = mat ? mat[(size_t)kMatShear01 * kLanes + j] : P.shear[0];
+            const double S1 = mat ? S0 : P.shear[1];
+            const double S2 = mat ? mat[(size_t)kMatShear2 * kLanes + j] : P.shear[2];
+            const double d0 = xn[s][0] - x[s][0], d1 = xn[s][1] - x[s][1], d2 = xn[s][2] - x[s][2];
+            const double l = sqrt(d0 * d0 + d1 * d1 + d2 * d2) + P.eps_length;
+            const double e = l / P.rest_len;
+            const double t0 = d0 / l, t1 = d1 / l, t2 = d2 / l;
+            const double s0 = e * (Q[s][0] * t0 + Q[s][1] * t1 + Q[s][2] * t2);
+            const double s1 = e * (Q[s][3] * t0 + Q[s][4] * t1 + Q[s][5] * t2);
+            const double s2 = e * (Q[s][6] * t0 + Q[s][7] * t1 + Q[s][8] * t2) - 1.0;
+            const double* w = L.w[s];
+            er += (J0 * w[0] * w[0] + J1 * w[1] * w[1] + J2 * w[2] * w[2]) / e;
+            es += (S0 * s0 * s0 + S1 * s1 * s1 + S2 * s2 * s2) * P.rest_len;
+        }
+        if (j < n - 1) {
+            const double B0 = mat ? mat[(size_t)kMatBend01 * kLanes + j] : P.bend[0];
+            const double B1 = mat ? B0 : P.bend[1];
+            const double B2 = mat ? mat[(size_t)kMatBend2 * kLanes + j] : P.bend[2];
+            // kappa = -log(Q_{k+1} Q_k^T) / D^  (_inv_rotate, as rod_strains)
+            double R[9];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int l = 0; l < 3; ++l)
+                    R[3 * i + l] = Qn[s][3 * i] * Q[s][3 * l] + Qn[s][3 * i + 1] * Q[s][3 * l + 1] +
+                                   Qn[s][3 * i + 2] * Q[s][3 * l + 2];
+            const double tr = R[0] + R[4] + R[8];
+            const double theta = acos(fmin(fmax(0.5 * tr - 0.5 - P.acos_shift, -1.0), 1.0));
+            const double f = -0.5 * theta / sin(theta + P.eps_sin) / P.rest_vor;
+            const double k0 = (R[7] - R[5]) * f - (rest_kappa ? L.rk[s][0] : 0.0);
+            const double k1 = (R[2] - R[6]) * f - (rest_kappa ? L.rk[s][1] : 0.0);
+            const double k2 = (R[3] - R[1]) * f - (rest_kappa ? L.rk[s][2] : 0.0);
+            eb += (B0 * k0 * k0 + B1 * k1 * k1 + B2 * k2 * k2) * P.rest_vor;
+        }
+    }
+    E[0] = 0.5 * wave_sum(et);
+    E[1] = 0.5 * wave_sum(er);
+    E[2] = 0.5 * wave_sum(eb);
+    E[3] = 0.5 * wave_sum(es);
+}
+
+template <int E, int EPL, unsigned F = kRuntimeFeatures, bool RT = false>
 __device__ __forceinline__ void env_epilogue_n(const RodParams& P, const StatePtrs& S, size_t N, int rod,
                                                int lane, const ConstN<EPL>& C, const LaneN<EPL>& L,
                                                double time, const EnvAction& A, float* __restrict__ obs,
@@ -1019,16 +1170,28 @@ __device__ __forceinline__ void env_epilogue_n(const RodParams& P, const StatePt
         const int od = 2 * (P.n_elem + 1) + 2;
         float* o = out_row(obs, rod, od, pack);
         const bool nan_obs = push_get_state_n<EPL>(P, lane, L, A.a, o, true);
+        // config_early_termination (:310-313): check_early_termination -> H < cutoff_error = 1e-7 (:441-456)
+        const bool early = early_term_on<F, RT>(P);
+        double H = 0.0;
+        if (early) {
+            double en[4];
+            BcTargets none;                                                    // the sucker's constrain_values is a no-op
+            rod_energies_n<EPL>(P, S.mat, none, false, lane, L, time, en);
+            H = (en[0] + en[1]) + (en[3] + en[2]);
+        }
         if (lane == 0) {
             const double p0 = S.ctrl[(size_t)0 * N + rod], p1 = S.ctrl[(size_t)1 * N + rod];   // prev_cm_pos (prologue)
             double forward = 0.0, survive = 0.0;
-            bool term = false;
-            if (nan_state) { term = true; survive = -20.0; }
+            bool term = false, trunc = false;
+            if (early) { term = H < 1e-7; trunc = term; survive = -10.0; }   // (NaN H: False)
+            else if (nan_state) { term = true; survive = -20.0; }
             else forward = sqrt(com[0] * com[0] + com[1] * com[1]) - sqrt(p0 * p0 + p1 * p1);
+            const bool timelimit = time > P.final_time;
             double rw = forward + survive;
             if (isnan(rw)) { term = true; rw = -20.0; }
             if (nan_obs) { term = true; rw = -20.0; }
-            emit_scalars(o, od, pack, rod, rw, term, time > P.final_time, reward, terminated, truncated, S.needs_reset);
+            emit_scalars(o, od, pack, rod, rw, term, trunc || timelimit, reward, terminated, truncated, S.needs_reset);
+            if (early) S.aux[rod] = timelimit ? 1.0 : 0.0;   // info["TimeLimit.truncated"] (:325-329)
         }
     } else if (env == SOFTROD_ENV_ARM_SINGLE) {
         double pw = 0.0;
@@ -1605,6 +1768,8 @@ __device__ __forceinline__ void libm_dynamic_step(const RodParams& P, const Libm
 #ifndef SOFTROD_LIBM_WAVES
 #define SOFTROD_LIBM_WAVES 1
 #endif
+// ET: the instantiation for an early-termination handle (the default one compiles none of it)
+template <bool ET>
 __global__ void __launch_bounds__(kLanes, SOFTROD_LIBM_WAVES)
 softrod_step_libm_kernel(const RodParams P, const StatePtrs S, const float* __restrict__ actions,
                          float* __restrict__ obs, double* __restrict__ reward,
@@ -1615,6 +1780,7 @@ softrod_step_libm_kernel(const RodParams P, const StatePtrs S, const float* __re
     const size_t N = (size_t)P.n_envs;
     if (epilogue && S.skip && S.skip[rod]) {   // reset by the auto-reset pass of this env.step
         if (lane == 0) S.skip[rod] = 0;
+        if (ET && lane == 0) S.aux[rod] = 0.0;   // no time limit on a restart
         return;
     }
 
@@ -1649,8 +1815,8 @@ softrod_step_libm_kernel(const RodParams P, const StatePtrs S, const float* __re
     store_lane<1, kRuntimeFeatures>(S, N, rod, lane, L);
     if (lane == 0) S.time[rod] = time;
     if (epilogue)
-        env_epilogue_n<kRuntimeEnv, 1>(P, S, N, rod, lane, C, L, time, A, obs, reward, terminated, truncated,
-                                       aux, pack);
+        env_epilogue_n<kRuntimeEnv, 1, kRuntimeFeatures, ET>(P, S, N, rod, lane, C, L, time, A, obs, reward, terminated,
+                                                             truncated, aux, pack);
 }
 
 // Reset: expand the host-computed straight-rod description of each masked rod
@@ -1842,6 +2008,54 @@ softrod_autoreset_kernel(const RodParams P, const StatePtrs S, float* __restrict
         if (aux && P.env_kind == SOFTROD_ENV_SOFTPENDULUM3D) aux[rod] = (double)o[8];
         S.skip[rod] = 1;
         S.q_consumed[rod] = k + 1;
+    }
+}
+
+// softrod_rod_energies: one wave per rod — env blockIdx.x / rods, arm blockIdx.x % rods, its slots
+// a * arm_stride .. a * arm_stride + n_elem of the env's row (`lane_stride` wide: the layouts of
+// softrod_state_view) — so every arm's sums are a plain wave reduction.  Slots past the rod are
+// never read.  out: [n_envs][rods][4].
+template <int EPL>
+__global__ void __launch_bounds__(kLanes)
+softrod_rod_energies_kernel(const RodParams P, const StatePtrs S, const int rods, const int lane_stride,
+                            const int arm_stride, double* __restrict__ out) {
+    const int rod = blockIdx.x, env = rod / rods, arm = rod - env * rods;
+    const int lane = threadIdx.x;
+    const size_t N = (size_t)P.n_envs, W = (size_t)lane_stride;
+    const size_t base = (size_t)env * W + (size_t)arm * (size_t)arm_stride;
+    const bool rk = (P.features & SOFTROD_FEAT_REST_KAPPA_ACTION) != 0;
+    LaneN<EPL> L;
+#pragma unroll
+    for (int s = 0; s < EPL; ++s) {
+        const int j = lane * EPL + s;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { L.x[s][c] = L.v[s][c] = L.w[s][c] = L.rk[s][c] = 0.0; }
+#pragma unroll
+        for (int c = 0; c < 9; ++c) L.Q[s][c] = 0.0;
+        if (j <= P.n_elem) {
+            const size_t i = base + (size_t)j;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                L.x[s][c] = S.pos[c * N * W + i];
+                L.v[s][c] = S.vel[c * N * W + i];
+                L.w[s][c] = S.omg[c * N * W + i];
+                if (rk) L.rk[s][c] = S.rkap[c * N * W + i];
+            }
+#pragma unroll
+            for (int c = 0; c < 9; ++c) L.Q[s][c] = S.dir[c * N * W + i];
+        }
+    }
+    BcTargets B;
+    const bool bc = (P.features & (SOFTROD_FEAT_PENDULUM_BC | SOFTROD_FEAT_FIXED_BC | SOFTROD_FEAT_MOVING_BASE_BC)) != 0;
+    if (bc) {
+        load_bc(S, N, env, B);
+        if (P.features & SOFTROD_FEAT_MOVING_BASE_BC) { B.pos[0] = S.ctrl[env]; B.pos[1] = S.ctrl[N + env]; }
+    }
+    double E[4];
+    rod_energies_n<EPL>(P, S.mat, B, bc, lane, L, S.time[env], E);
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) out[(size_t)rod * 4 + i] = E[i];
     }
 }
 

@@ -255,6 +255,7 @@ softrod_octo_step_kernel(const RodParams P, const StatePtrs S, const float* __re
         if constexpr (EPB == 1) {
             __syncthreads();                   // every thread has read the flag
             if (tid == 0 && !mocto) S.skip[env] = 0;       // (mocto: the epilogue kernel clears it)
+            if (tid == 0 && early_term_on<F>(P)) S.aux[env] = 0.0;   // no time limit on a restart
             return;
         }
         live = false;
@@ -529,7 +530,7 @@ softrod_octo_step_kernel(const RodParams P, const StatePtrs S, const float* __re
     if constexpr (kMusclesCompiled<F>) {
         // ArmPullWeightEnv.step = ArmPushEnv.step after the loop (arm_push_env.py:288-347) on the arm alone
         if (live)
-            env_epilogue_n<kRuntimeEnv, 1>(P, S, NR, row, lane, C, L, time, A, obs, reward, terminated, truncated, nullptr, pack);
+            env_epilogue_n<kRuntimeEnv, 1, F>(P, S, NR, row, lane, C, L, time, A, obs, reward, terminated, truncated, nullptr, pack);
         return;
     }
 

@@ -95,6 +95,53 @@ def rod_strains(x: np.ndarray, Q: np.ndarray, rest_length: float, base_radius,
             "radius": radius, "sigma": sigma, "kappa": kappa, "tangents": tangents}
 
 
+def rod_material_host(cfg, radius=None) -> Dict[str, np.ndarray]:
+    """What CosseratRod.straight_rod derives for the energies, as the kernels hold it (RodParams for a uniform rod,
+    the softrod_set_radius_profile table for a tapered one): nodal masses (n+1,) with half masses at the ends,
+    J (3, n) and the shear diagonal (3, n) per element, the bend diagonal (3, n-1) on the Voronoi vertices
+    (rest-length-weighted average of the two elements), the rest lengths.  radius: per-element radii or None."""
+    n = int(cfg.n_elem)
+    rl = float(cfg.base_length) / n
+    r = np.full(n, float(cfg.base_radius)) if radius is None else np.asarray(radius, np.float64).reshape(n)
+    A = np.pi * r * r
+    I1 = A * A / (4.0 * np.pi)
+    I = np.stack([I1, I1, 2.0 * I1])
+    J = I * (float(cfg.density) * rl)
+    shear = np.stack([float(cfg.alpha_c) * float(cfg.shear_modulus) * A] * 2 + [float(cfg.youngs_modulus) * A])
+    B = np.stack([float(cfg.youngs_modulus) * I[0], float(cfg.youngs_modulus) * I[1], float(cfg.shear_modulus) * I[2]])
+    bend = (B[:, 1:] * rl + B[:, :-1] * rl) / (rl + rl)
+    half = 0.5 * float(cfg.density) * (np.pi * r * r * rl)
+    mass = np.zeros(n + 1)
+    mass[:-1] += half
+    mass[1:] += half
+    return {"mass": mass, "J": J, "shear": shear, "bend": bend, "rest_length": rl, "rest_voronoi": 0.5 * (rl + rl)}
+
+
+def rod_energies_host(x, v, Q, w, time: float, cfg, material, rest_kappa=None, fixed_pos=None, fixed_dir=None,
+                      base_xy=None) -> np.ndarray:
+    """NumPy twin of softrod_rod_energies for one rod: [translational, rotational, bending, shear].
+
+    The instant is PyElastica's (module docstring): the strains of the mid-substep configuration
+    (mid_substep_configuration, then constrain_values_host), the end-of-step rates; time == 0 (a reset) uses
+    the state as it stands.  The forms are our recollection of pyelastica 1.0.0's compute_*_energy (not on
+    disk): 1/2 sum m|v|^2, 1/2 sum w.(J w)/e, 1/2 sum dk.B dk D^ with dk = kappa - rest_kappa, 1/2 sum s.S s l^.
+    material: rod_material_host(...); rest_kappa (3, n-1) or None (zero)."""
+    x, Q = np.array(x, np.float64), np.array(Q, np.float64)
+    v, w = np.asarray(v, np.float64), np.asarray(w, np.float64)
+    if time != 0.0:
+        x, Q = mid_substep_configuration(x, v, Q, w, float(cfg.dt), float(cfg.eps_rot_axis))
+        if fixed_pos is not None:
+            constrain_values_host(int(cfg.features), x, Q, fixed_pos, fixed_dir, base_xy)
+    rl = material["rest_length"]
+    s = rod_strains(x, Q, rl, 1.0, float(cfg.acos_shift), float(cfg.eps_sin))
+    dk = s["kappa"] if rest_kappa is None else s["kappa"] - rest_kappa
+    trans = 0.5 * (material["mass"] * (v * v).sum(0)).sum()
+    rot = 0.5 * ((material["J"] * w * w).sum(0) / s["dilatation"]).sum()
+    bend = 0.5 * ((material["bend"] * dk * dk).sum(0) * material["rest_voronoi"]).sum()
+    shear = 0.5 * ((material["shear"] * s["sigma"] * s["sigma"]).sum(0) * rl).sum()
+    return np.array([trans, rot, bend, shear])
+
+
 class RodRecorder:
     """Collects RodCallBack's fields for `env_indices` of a batch; one dict of lists per env,
     keyed like the reference's `rod_parameters_dict`."""

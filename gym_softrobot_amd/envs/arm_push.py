@@ -9,6 +9,13 @@ relaxes (:254-267) — an inchworm; "continuous" mode (v1): (sucker location, tr
 (:268-271).  Observation: x-positions, x-velocities, the previous action (one-hot in v0) (:225-245);
 reward: the change of the centre of mass's distance from the origin, -20 on NaN (:288-333).
 
+`config_early_termination=True` (:310-313, 441-456): every step reports terminated = truncated = (H < 1e-7) with
+H the rod's translational + rotational + shear + bending energy (`rod_energies()`, at PyElastica's instant: the
+mid-substep strains of the last force evaluation, the end-of-step rates), reward -10 (no forward reward, no
+_isnan_check), then the time limit, the NaN-reward and NaN-observation checks as usual; info["TimeLimit.truncated"]
+stays the time limit alone.  Decided in the step kernel's epilogue, so device auto-reset, step_packed and captured
+policy steps carry it.  The energy forms are recalled (pyelastica 1.0.0 is not on disk).
+
 WHAT IS AND IS NOT PINNED.  Everything in arm_push_env.py (geometry, wiring, set_action, get_state,
 reward) is pinned against the EXECUTED reference file (tools/make_env_golden.py,
 tests/golden/ref_arm_push.npz).  The muscle force model lives in COOMM (git pin uv.lock:173-175), which
@@ -58,11 +65,11 @@ class VecArmPushEnv(VecRodEnvBase):
     ):
         """`muscle_kwargs`: the recalled COOMM constructor behaviour of `_capi.es_muscle_layers`
         (init_angle_rotates, tm_sign) — switches for the day the muscle fixtures exist."""
-        if config_early_termination:
-            raise NotImplementedError("config_early_termination (the Hamiltonian cut-off of arm_push_env.py:311-314, "
-                                      "389-404) is not built: the default (False) only")
-        cfg = self._config(num_envs, final_time=final_time, time_step=time_step,
-                           recording_fps=recording_fps, mode=mode, math_mode=math_mode)
+        if config_early_termination and backend is not None and not getattr(backend, "supports_early_termination", False):
+            raise NotImplementedError(f"{type(backend).__name__} cannot honour config_early_termination (the Hamiltonian "
+                                      "cut-off of arm_push_env.py:310-313, 441-456)")
+        cfg = self._config(num_envs, final_time=final_time, time_step=time_step, recording_fps=recording_fps,
+                           mode=mode, math_mode=math_mode, early_termination=config_early_termination)
         super().__init__(num_envs, cfg, render_mode=render_mode, config_generate_video=config_generate_video,
                          device=device, numpy_output=numpy_output, autoreset=autoreset, backend=backend)
         self.final_time = final_time
@@ -72,7 +79,7 @@ class VecArmPushEnv(VecRodEnvBase):
         self.step_skip = int(1.0 / (recording_fps * time_step))
         self.n_elem = 40                                # :88
         self.mode = int(cfg.arm_push_mode)
-        self.config_early_termination = False
+        self.config_early_termination = bool(config_early_termination)
         if self.mode == 0:
             self.single_action_space = Discrete(2)      # :101
         radius_mean = _capi.arm_push_radii(self.n_elem)

@@ -351,7 +351,10 @@ class VecRodEnvBase:
         self._top_up_tick()
         if getattr(self, "_dev_time", None) is None:
             self._dev_time = self.backend.state()["time"]
-        infos = {"time": self._out(self._dev_time), "TimeLimit.truncated": self._out(trunc.view(torch.bool))}
+        # TimeLimit.truncated is the time limit alone; with ArmPush's early termination `truncated` carries the
+        # cut-off as well, and the epilogue writes the time-limit flag on its own (backend.time_limit)
+        tl = self.backend.time_limit() if getattr(self.cfg, "early_termination", 0) else trunc.view(torch.bool)
+        infos = {"time": self._out(self._dev_time), "TimeLimit.truncated": self._out(tl)}
         return (self._out(obs), self._out(reward), self._out(term.view(torch.bool)),
                 self._out(trunc.view(torch.bool)), infos)
 
@@ -398,6 +401,16 @@ class VecRodEnvBase:
             self._out(trunc.view(torch.bool)),
             infos,
         )
+
+    def rod_energies(self):
+        """(N, rods_per_env, 4) float64: translational, rotational, bending and shear energy of every rod
+        (PyElastica's compute_*_energy, our recollection of pyelastica 1.0.0: include/softrod.h
+        softrod_rod_energies).  THE INSTANT is the reference's: the strains (sigma, kappa, dilatation) of the
+        mid-substep configuration of the last substep, where its force evaluation cached them, with the
+        end-of-step velocities; right after a reset, the reset state.  OctoFlat / the muscle octopus: one row
+        per arm (rigid bodies have none).  A device tensor overwritten by the next call (NumPy with
+        numpy_output=True)."""
+        return self._out(self.backend.rod_energies())
 
     def capture_policy_step(self, policy):
         """One HIP graph for `actions = policy(obs); step(actions)` — the launch-bound tail of an on-device

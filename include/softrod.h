@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define SOFTROD_ABI_VERSION 16
+#define SOFTROD_ABI_VERSION 17
 
 /* error codes */
 #define SOFTROD_OK 0
@@ -260,7 +260,13 @@ typedef struct softrod_config {
     /* ---- ControllableFixConstraint (octopus/controllable_constraint.py:24-69) ---- */
     int32_t n_suckers;        /* constraints of this kind registered on the rod (0..4)      */
     int32_t sucker_index[4];  /* SuckerController.index of each (node AND element index)    */
-    int32_t reserved2;
+    int32_t early_termination; /* ArmPushEnv(config_early_termination=True) (arm_push_env.py:310-313, 441-456):
+                                 1 = every step ends with terminated = truncated = (H < 1e-7), survive reward -10,
+                                 no forward reward and no _isnan_check; H = translational + rotational + shear +
+                                 bending energy at the instant softrod_rod_energies describes.  0 or 1; 1 only
+                                 with SOFTROD_ENV_ARM_PUSH / SOFTROD_ENV_ARM_PULL_WEIGHT.  The time-limit flag of
+                                 the step (info["TimeLimit.truncated"], :325-329) then lands in row 0 of
+                                 softrod_state_view.env_aux (was reserved2: same layout)                  */
     double sucker_reduction_ratio; /* initial reduction_ratio of every sucker (1.0, :11); the
                                  controllers are on after finalize (arm_push_env.py:222)  */
     /* ---- SOFTROD_FEAT_COOMM_MUSCLES (octopus/build.py:295-338; COOMM itself NOT on disk: every field below
@@ -385,7 +391,9 @@ typedef struct softrod_state_view {
                          for a uniform rod.  Read-only for the caller.                     */
     /* ---- the muscle octopus envs (SOFTROD_ENV_CRAWL / _ARM_TWO / _REACH); NULL otherwise.  Their sucker_ratio /
      *      sucker_index rows are [SOFTROD_MAX_SUCKERS][n_envs * n_arm] (arm a of env e at e * n_arm + a) ---- */
-    double* env_aux;  /* [8][n_envs]  rows 0-2 the env's target (crawl_env.py:172, arm_two_env.py:160: (5, 0);
+    double* env_aux;  /* [8][n_envs]  ArmPush / ArmPullWeight with early_termination = 1: row 0 is the last step's
+                         time-limit flag (1.0 when time > final_time, arm_push_env.py:325-329; 0.0 after an auto-reset);
+                         NULL for the other single rods.  The muscle octopus envs: rows 0-2 the env's target (crawl_env.py:172, arm_two_env.py:160: (5, 0);
                          reach_env.py:141-143: np_random.random(3) * sum(rest_lengths)), rows 3-4 the head's x, y before
                          the step (`xposbefore`, crawl_env.py:248), row 5 the episode's own final_time (0: the config's).  (rod.kappa[0] of get_state, crawl_env.py:178,
                          is row 0 of `kappa`: what the last substep's force evaluation cached; zeros after a reset)  */
@@ -629,6 +637,24 @@ int softrod_exchange_free(int device, void* dev_ptr);
  * float32, or NULL = the resident copy of the last stepped action.          */
 int softrod_observe(softrod_handle* h, const float* prev_action, float* obs,
                     void* stream);
+
+/* Replaces: CosseratRod.compute_translational_energy, compute_rotational_energy,
+ * compute_bending_energy and compute_shear_energy (pyelastica 1.0.0; called by
+ * octopus/arm_push_env.py:446-456 cal_desired_Hamiltonian, and in commented-out code by
+ * flat_env.py:336-338, crawl_env.py:269-272, arm_two_env.py:284-287) of every rod of
+ * every env.  out: device [n_envs][rods_per_env][4] float64 in the order translational,
+ * rotational, bending, shear; rods_per_env = n_arm for OctoFlat and the muscle octopus,
+ * else 1 (rigid bodies have none here).  Asynchronous on `stream`, like softrod_observe.
+ * THE INSTANT: the reference's sigma / kappa / dilatation are the caches of the last force
+ * evaluation, at the mid-substep configuration x - dt/2 v, R(dt/2 omega)^T Q followed by the
+ * boundary condition's constrain_values; v and omega are the end-of-step rates.  An env
+ * whose time is 0 (just reset) is evaluated at its state as it stands.
+ * THE FORMS (recalled from pyelastica 1.0.0, which is not on disk):
+ *   translational  1/2 sum_i m_i |v_i|^2
+ *   rotational     1/2 sum_e omega_e . (J_e omega_e) / e_e          e_e the dilatation
+ *   bending        1/2 sum_k (kappa_k - kappa^_k) . B_k (kappa_k - kappa^_k) D^_k
+ *   shear          1/2 sum_e sigma_e . S_e sigma_e  l^_e           (rest sigma 0)  */
+int softrod_rod_energies(softrod_handle* h, double* out, void* stream);
 
 /* Run `n` bare PositionVerlet substeps with fixed per-env forcing inputs and no
  * env epilogue (the inner loop of soft_pendulum.py:183-184 alone); `actions`
