@@ -442,16 +442,21 @@ def arm_push_config(
     mode: str = "discrete",
     math_mode: int = MATH_FAST,
     early_termination: bool = False,
+    n_elems: int = 40,
 ) -> SoftrodConfig:
     """`softrod_config_arm_push`: ArmPushEnv.__init__ (octopus/arm_push_env.py:65-139) and `_build`
     (:158-224): a 40-element arm of length 0.2, density 700, E = 1e4, G = E / 1.5, tapered 12:1
     (arm_push_radii -> softrod_set_radius_profile), AnalyticalLinearDamper(0.05 * 2 * 1e2), one
     ControllableFixConstraint at index 0 and ApplyMuscles over create_es_muscle_layers.  No gravity, no plane.
-    `early_termination`: config_early_termination, the Hamiltonian cut-off of step() (:310-313, 441-456)."""
+    `early_termination`: config_early_termination, the Hamiltonian cut-off of step() (:310-313, 441-456).
+    `n_elems`: the arm's element count (self.n_elem, :88), 2..126; above 63 the arm runs two elements per lane
+    under MATH_FAST only."""
     if mode not in ("discrete", "continuous"):
         raise NotImplementedError(f"The mode {mode} is not available.")            # arm_push_env.py:97
+    if not 2 <= int(n_elems) <= 126:
+        raise ValueError(f"n_elems must lie in 2..126, got {n_elems}")
     cfg = SoftrodConfig()
-    _common(cfg, n_envs, final_time, time_step, recording_fps, 40, math_mode)
+    _common(cfg, n_envs, final_time, time_step, recording_fps, int(n_elems), math_mode)
     cfg.features = FEATURES_ARM_PUSH
     cfg.env_kind = ENV_ARM_PUSH
     cfg.arm_push_mode = 0 if mode == "discrete" else 1

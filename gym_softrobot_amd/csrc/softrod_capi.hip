@@ -39,13 +39,13 @@ struct softrod_handle {
     RodParams* d_params = nullptr;  // device copy of P
     StatePtrs* d_state = nullptr;   // device copy of S (re-uploaded whenever S changes)
     double* d_time_tab = nullptr;   // clock after k env.steps from a reset (clock_after, softrod_fast.hpp)
-    double* d_mat = nullptr;        // [kMatRows][64] material table of a tapered rod
+    double* d_mat = nullptr;        // [kMatRows][64 * epl] material table of a tapered rod
     double* d_sucker = nullptr;     // [SOFTROD_MAX_SUCKERS][N]
     int* d_sucker_idx = nullptr;    // [SOFTROD_MAX_SUCKERS][N]
     double* d_aux = nullptr;        // [8][N] the muscle octopus envs' target and xposbefore
     float* d_prev_kappa = nullptr;  // [N][n_arm * (n_elem - 1)] ArmTwoEnv._prev_kappa
     double* d_mact = nullptr;       // [SOFTROD_MAX_MUSCLES][N][64] muscle activations (SOFTROD_FEAT_COOMM_MUSCLES)
-    double* d_mtab = nullptr;       // [SOFTROD_MAX_MUSCLES][4][64] ratio_position x, y, z, strength
+    double* d_mtab = nullptr;       // [SOFTROD_MAX_MUSCLES][4][64 * epl] ratio_position x, y, z, strength
     bool muscles_set = false;
     unsigned* d_ticket = nullptr;   // softrod_scatter_rows: blocks that have finished storing (tagged form)
     bool tapered = false;
@@ -363,7 +363,15 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
             else                                                                                    \
                 SR_LAUNCH(kRuntimeFeatures, kRuntimeEnv, EPL);                                      \
         } while (0)
-        if (h->tapered) {    // per-lane material constants (TAPER = true), one slot per lane
+        if (h->tapered && h->epl == 2) {    // the ArmPush arm of 64..126 elements, two slots per lane
+            // (softrod_set_radius_profile tapers no other two-slot handle)
+            if (h->cfg.early_termination)
+                hipLaunchKernelGGL((softrod_step_fast_kernel<SOFTROD_FEATURES_ARM_PUSH | kFeatEarlyTerm, SOFTROD_ENV_ARM_PUSH, 2, true>),
+                                   grid, block, 0, st, h->P, h->S, actions, obs, reward, term, trunc, aux, n_sub, epilogue, pack);
+            else
+                hipLaunchKernelGGL((softrod_step_fast_kernel<SOFTROD_FEATURES_ARM_PUSH, SOFTROD_ENV_ARM_PUSH, 2, true>),
+                                   grid, block, 0, st, h->P, h->S, actions, obs, reward, term, trunc, aux, n_sub, epilogue, pack);
+        } else if (h->tapered) {    // per-lane material constants (TAPER = true), one slot per lane
 #define SR_LAUNCH_TAPER(FEATS, ENV)                                                                 \
             hipLaunchKernelGGL((softrod_step_fast_kernel<FEATS, ENV, 1, true>), grid, block, 0, st, h->P, h->S, \
                                actions, obs, reward, term, trunc, aux, n_sub, epilogue, pack)
@@ -733,8 +741,11 @@ int softrod_create(const softrod_config* cfg, int device, softrod_handle** out) 
     if (cfg->env_kind < SOFTROD_ENV_NONE || cfg->env_kind > SOFTROD_ENV_REACH)
         return fail(nullptr, SOFTROD_EINVAL, "unknown env_kind");
     if (cfg->features & SOFTROD_FEAT_COOMM_MUSCLES) {
+        // two slots per lane (64..126 elements): the tapered ArmPush arm's own instantiations only
+        const bool two_slot_push = cfg->features == SOFTROD_FEATURES_ARM_PUSH && cfg->env_kind == SOFTROD_ENV_ARM_PUSH &&
+                                   cfg->math_mode == SOFTROD_MATH_FAST;
         if (cfg->n_muscles < 1 || cfg->n_muscles > SOFTROD_MAX_MUSCLES || cfg->muscle_fl_degree < 0 ||
-            cfg->muscle_fl_degree >= SOFTROD_MAX_FL_COEF || cfg->n_elem > kLanes - 1 ||
+            cfg->muscle_fl_degree >= SOFTROD_MAX_FL_COEF || (cfg->n_elem > kLanes - 1 && !two_slot_push) ||
             ((cfg->features & SOFTROD_FEAT_OCTO_HEAD) && cfg->env_kind != SOFTROD_ENV_ARM_PULL_WEIGHT && !mocto_kind(cfg->env_kind)))
             return fail(nullptr, SOFTROD_EINVAL,
                         "COOMM muscles: 1 <= n_muscles <= 4, 0 <= muscle_fl_degree <= 7, one rod of up to 63 elements per env");
@@ -957,7 +968,7 @@ int softrod_create(const softrod_config* cfg, int device, softrod_handle** out) 
     }
     if (cfg->features & SOFTROD_FEAT_COOMM_MUSCLES) {
         alloc((void**)&h->d_mact, (size_t)SOFTROD_MAX_MUSCLES * rowb);
-        alloc((void**)&h->d_mtab, (size_t)SOFTROD_MAX_MUSCLES * 4 * kLanes * sizeof(double));
+        alloc((void**)&h->d_mtab, (size_t)SOFTROD_MAX_MUSCLES * 4 * kLanes * h->epl * sizeof(double));
         h->S.mact = h->d_mact;
         h->S.mtab = h->d_mtab;
     }
@@ -1324,15 +1335,19 @@ int softrod_set_spline_table(softrod_handle* h, const double* breaks, const doub
 // kernels' per-lane material table.  Mirrors straight_rod() of oracle/softrod_oracle.c.
 int softrod_set_radius_profile(softrod_handle* h, const double* radius) {
     if (!h || !radius) return fail(h, SOFTROD_EINVAL, "null argument");
-    if ((is_octo(h) && !is_pull(h) && !is_mocto(h)) || h->epl != 1 || h->window_refresh > 0)
-        return fail(h, SOFTROD_EINVAL, "tapered rods: one rod of up to 63 elements per env, or the muscle octopus' arms");
+    // two slots per lane: the ArmPush arm only (its two-slot instantiations in launch_step)
+    const bool two_slot_push = h->epl == 2 && h->cfg.features == SOFTROD_FEATURES_ARM_PUSH &&
+                               h->cfg.env_kind == SOFTROD_ENV_ARM_PUSH && h->cfg.math_mode == SOFTROD_MATH_FAST;
+    if ((is_octo(h) && !is_pull(h) && !is_mocto(h)) || (h->epl != 1 && !two_slot_push) || h->window_refresh > 0)
+        return fail(h, SOFTROD_EINVAL, "tapered rods: one rod of up to 63 elements per env (126 for the ArmPush arm), "
+                                       "or the muscle octopus' arms");
     if (h->was_reset) return fail(h, SOFTROD_EINVAL, "softrod_set_radius_profile must precede the first reset");
     const softrod_config& c = h->cfg;
     const int n = c.n_elem;
     for (int k = 0; k < n; ++k)
         if (!(radius[k] > 0.0)) return fail(h, SOFTROD_EINVAL, "radii must be positive");
     SR_ON_DEVICE(h);
-    constexpr int W = kLanes;
+    const int W = kLanes * h->epl;
     // the muscle octopus: every arm is this rod, `seg` slots apart — the table is built for one arm's slots and repeated
     const int period = is_mocto(h) ? h->P.seg : W;
     const double ddt = c.damper_time_step > 0.0 ? c.damper_time_step : c.dt;
@@ -1393,7 +1408,7 @@ int softrod_set_muscle_layers(softrod_handle* h, const double* ratio_position, c
     if (!h || !ratio_position || !strength) return fail(h, SOFTROD_EINVAL, "null argument");
     if (!(h->cfg.features & SOFTROD_FEAT_COOMM_MUSCLES)) return fail(h, SOFTROD_EINVAL, "this handle has no COOMM muscles");
     const int n = h->cfg.n_elem, M = h->cfg.n_muscles;
-    constexpr int W = kLanes;
+    const int W = kLanes * h->epl;
     std::vector<double> T((size_t)SOFTROD_MAX_MUSCLES * 4 * W, 0.0);
     for (int m = 0; m < M; ++m)
         for (int k = 0; k < n; ++k) {
@@ -1742,7 +1757,7 @@ const char* softrod_kernel_tier(softrod_handle* h) {
         else if (f == SOFTROD_FEATURES_ARM_SINGLE && e == SOFTROD_ENV_ARM_SINGLE && zup) spec = "ArmSingle";
         else if (f == SOFTROD_FEATURES_SOFT_ARM && e == SOFTROD_ENV_SOFT_ARM) spec = "SoftArm";
         else if (f == kFeaturesMuscleRod && e == SOFTROD_ENV_NONE) spec = "muscle rod";
-        t = std::string("softrod_step_fast_kernel<") + spec + ",epl=" + std::to_string(h->tapered ? 1 : h->epl) +
+        t = std::string("softrod_step_fast_kernel<") + spec + ",epl=" + std::to_string(h->epl) +
             (h->tapered ? ",taper>" : ">");
     } else
         t = "softrod_step_libm_kernel";

@@ -1034,17 +1034,17 @@ __device__ __forceinline__ void rod_energies_n(const RodParams& P, const double*
     for (int s = 0; s < EPL; ++s) {
         const int j = lane * EPL + s;
         if (j <= n) {
-            const double m = mat ? mat[(size_t)kMatMass * kLanes + j]
+            const double m = mat ? mat[(size_t)kMatMass * kLanes * EPL + j]
                                  : ((j == 0 || j == n) ? 0.5 * P.mass_node : P.mass_node);
             et += m * (L.v[s][0] * L.v[s][0] + L.v[s][1] * L.v[s][1] + L.v[s][2] * L.v[s][2]);
         }
         if (j < n) {
-            const double J0 = mat ? mat[(size_t)kMatJ0 * kLanes + j] : P.J[0];
+            const double J0 = mat ? mat[(size_t)kMatJ0 * kLanes * EPL + j] : P.J[0];
             const double J1 = mat ? J0 : P.J[1];
-            const double J2 = mat ? mat[(size_t)kMatJ2 * kLanes + j] : P.J[2];
-            const double S0 = mat ? mat[(size_t)kMatShear01 * kLanes + j] : P.shear[0];
+            const double J2 = mat ? mat[(size_t)kMatJ2 * kLanes * EPL + j] : P.J[2];
+            const double S0 = mat ? mat[(size_t)kMatShear01 * kLanes * EPL + j] : P.shear[0];
             const double S1 = mat ? S0 : P.shear[1];
-            const double S2 = mat ? mat[(size_t)kMatShear2 * kLanes + j] : P.shear[2];
+            const double S2 = mat ? mat[(size_t)kMatShear2 * kLanes * EPL + j] : P.shear[2];
             const double d0 = xn[s][0] - x[s][0], d1 = xn[s][1] - x[s][1], d2 = xn[s][2] - x[s][2];
             const double l = sqrt(d0 * d0 + d1 * d1 + d2 * d2) + P.eps_length;
             const double e = l / P.rest_len;
@@ -1057,9 +1057,9 @@ __device__ __forceinline__ void rod_energies_n(const RodParams& P, const double*
             es += (S0 * s0 * s0 + S1 * s1 * s1 + S2 * s2 * s2) * P.rest_len;
         }
         if (j < n - 1) {
-            const double B0 = mat ? mat[(size_t)kMatBend01 * kLanes + j] : P.bend[0];
+            const double B0 = mat ? mat[(size_t)kMatBend01 * kLanes * EPL + j] : P.bend[0];
             const double B1 = mat ? B0 : P.bend[1];
-            const double B2 = mat ? mat[(size_t)kMatBend2 * kLanes + j] : P.bend[2];
+            const double B2 = mat ? mat[(size_t)kMatBend2 * kLanes * EPL + j] : P.bend[2];
             // kappa = -log(Q_{k+1} Q_k^T) / D^  (_inv_rotate, as rod_strains)
             double R[9];
 #pragma unroll

@@ -62,14 +62,17 @@ class VecArmPushEnv(VecRodEnvBase):
         autoreset: bool = False,
         backend=None,
         muscle_kwargs: Optional[dict] = None,
+        n_elems: int = 40,
     ):
         """`muscle_kwargs`: the recalled COOMM constructor behaviour of `_capi.es_muscle_layers`
-        (init_angle_rotates, tm_sign) — switches for the day the muscle fixtures exist."""
+        (init_angle_rotates, tm_sign) — switches for the day the muscle fixtures exist.
+        `n_elems`: the arm's element count (the reference's self.n_elem, :88), 2..126; above 63 elements the
+        arm runs on the two-slot-per-lane kernel (MATH_FAST only)."""
         if config_early_termination and backend is not None and not getattr(backend, "supports_early_termination", False):
             raise NotImplementedError(f"{type(backend).__name__} cannot honour config_early_termination (the Hamiltonian "
                                       "cut-off of arm_push_env.py:310-313, 441-456)")
         cfg = self._config(num_envs, final_time=final_time, time_step=time_step, recording_fps=recording_fps,
-                           mode=mode, math_mode=math_mode, early_termination=config_early_termination)
+                           mode=mode, math_mode=math_mode, early_termination=config_early_termination, n_elems=n_elems)
         super().__init__(num_envs, cfg, render_mode=render_mode, config_generate_video=config_generate_video,
                          device=device, numpy_output=numpy_output, autoreset=autoreset, backend=backend)
         self.final_time = final_time
@@ -77,7 +80,7 @@ class VecArmPushEnv(VecRodEnvBase):
         self.total_steps = int(self.final_time / self.time_step)
         self.recording_fps = recording_fps
         self.step_skip = int(1.0 / (recording_fps * time_step))
-        self.n_elem = 40                                # :88
+        self.n_elem = int(cfg.n_elem)                   # :88
         self.mode = int(cfg.arm_push_mode)
         self.config_early_termination = bool(config_early_termination)
         if self.mode == 0:
@@ -123,11 +126,14 @@ class VecArmPullWeightEnv(VecArmPushEnv):
     def __init__(self, num_envs: int, **kwargs):
         if "time_step" in kwargs:        # `super().__init__(time_step=2.5e-5, **kwargs)` (:518) would raise the same
             raise TypeError("__init__() got multiple values for keyword argument 'time_step'")
+        if kwargs.get("n_elems", 40) != 40:
+            raise ValueError("OctoArmPullWeight runs its 40-element arm on the rigid-body kernel's 32-slot arm pitch: "
+                             f"n_elems must be 40, got {kwargs['n_elems']}")
         super().__init__(num_envs, time_step=2.5e-5, **kwargs)
 
     @staticmethod
-    def _config(num_envs, *, time_step, **kw):
-        assert time_step == 2.5e-5
+    def _config(num_envs, *, time_step, n_elems, **kw):
+        assert time_step == 2.5e-5 and n_elems == 40
         return _capi.arm_pull_weight_config(num_envs, **kw)
 
 
@@ -151,19 +157,20 @@ class ArmPushEnv(_GymEnv):
         device: int = 0,
         math_mode: int = _capi.MATH_FAST,
         backend=None,
+        n_elems: int = 40,
     ):
         super().__init__()
         if render_mode not in {None, *self.metadata["render_modes"]}:
             raise ValueError(f"Unsupported render mode: {render_mode}")
         self.render_mode = render_mode
         self._vec = self._make_vec(final_time, time_step, recording_fps, mode, config_generate_video,
-                                   config_early_termination, device, math_mode, backend)
+                                   config_early_termination, device, math_mode, backend, n_elems)
         self.final_time = final_time
         self.time_step = time_step
         self.total_steps = self._vec.total_steps
         self.recording_fps = recording_fps
         self.step_skip = self._vec.step_skip
-        self.n_elem = 40
+        self.n_elem = self._vec.n_elem
         self.mode = self._vec.mode
         if self.mode == 0:
             self.action_space = Discrete(2)
@@ -179,10 +186,10 @@ class ArmPushEnv(_GymEnv):
 
     @staticmethod
     def _make_vec(final_time, time_step, recording_fps, mode, config_generate_video, config_early_termination,
-                  device, math_mode, backend):
+                  device, math_mode, backend, n_elems):
         return VecArmPushEnv(1, final_time, time_step, recording_fps, mode, config_generate_video,
                              config_early_termination, None, device=device, math_mode=math_mode,
-                             numpy_output=True, backend=backend)
+                             numpy_output=True, backend=backend, n_elems=n_elems)
 
     def reset(self, *, seed: Optional[int] = None, options: Optional[dict] = None):
         super().reset(seed=seed)
@@ -234,8 +241,8 @@ class ArmPullWeightEnv(ArmPushEnv):
 
     @staticmethod
     def _make_vec(final_time, time_step, recording_fps, mode, config_generate_video, config_early_termination,
-                  device, math_mode, backend):
+                  device, math_mode, backend, n_elems):
         return VecArmPullWeightEnv(1, final_time=final_time, recording_fps=recording_fps, mode=mode,
                                    config_generate_video=config_generate_video,
                                    config_early_termination=config_early_termination, render_mode=None, device=device,
-                                   math_mode=math_mode, numpy_output=True, backend=backend)
+                                   math_mode=math_mode, numpy_output=True, backend=backend, n_elems=n_elems)

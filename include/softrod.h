@@ -439,7 +439,8 @@ int softrod_set_spline_table(softrod_handle* h, const double* breaks, const doub
  * the contact radius) then varies along the rod: the library keeps them as per-lane rows
  * (softrod_state_view.material) instead of kernel-argument scalars and runs its general
  * instantiation.  radius: host [n_elem] float64.  Call before the first reset; rods of up to
- * 63 elements; not with SOFTROD_FEAT_OCTO_HEAD.                                            */
+ * 63 elements, or up to 126 for SOFTROD_FEATURES_ARM_PUSH with SOFTROD_ENV_ARM_PUSH under
+ * SOFTROD_MATH_FAST (two slots per lane); not with SOFTROD_FEAT_OCTO_HEAD.                  */
 #define SOFTROD_MATERIAL_ROWS 16
 int softrod_set_radius_profile(softrod_handle* h, const double* radius);
 
@@ -453,7 +454,8 @@ int softrod_set_radius_profile(softrod_handle* h, const double* radius);
  * strength:       host [n_muscles][n_elem] float64 = max_muscle_stress * rest_muscle_area, SIGNED (a transverse
  *                 muscle extends the arm: negative).
  * Needed before the first softrod_step / softrod_substeps of a handle with SOFTROD_FEAT_COOMM_MUSCLES; rods of
- * up to 63 elements, one rod per env.                                                                     */
+ * up to 63 elements (126 for SOFTROD_FEATURES_ARM_PUSH with SOFTROD_ENV_ARM_PUSH under SOFTROD_MATH_FAST), one
+ * rod per env.                                                                                            */
 int softrod_set_muscle_layers(softrod_handle* h, const double* ratio_position, const double* strength);
 
 /* Same for ArmPullWeightEnv (octopus/arm_push_env.py:516-618; registered as OctoArmPullWeight-v0 with mode
