@@ -727,6 +727,35 @@ def config_rods_per_env(cfg: "SoftrodConfig") -> int:
     return int(cfg.n_arm) if int(cfg.env_kind) == ENV_OCTO_FLAT or int(cfg.env_kind) in MUSCLE_OCTOPUS_ENVS else 1
 
 
+# softrod_set_env_material: the envs whose rods may carry per-env (E, G, rho, nu), with their own feature sets
+ENV_MATERIAL_ENVS = {ENV_SOFTPENDULUM: "FEATURES_SOFTPENDULUM", ENV_SOFTPENDULUM3D: "FEATURES_SOFTPENDULUM3D",
+                     ENV_ARM_SINGLE: "FEATURES_ARM_SINGLE"}
+
+
+def env_material_refusal(cfg: "SoftrodConfig", tapered: bool = False):
+    """Why softrod_set_env_material would refuse a handle of `cfg` (None: it would not).  The same scope as the
+    C-ABI's check: uniform rods of up to 63 elements of SoftPendulum, SoftPendulum3D and OctoArmSingle."""
+    kind = int(cfg.env_kind)
+    if kind not in ENV_MATERIAL_ENVS or int(cfg.features) != globals()[ENV_MATERIAL_ENVS[kind]]:
+        return "per-env material: SoftPendulum, SoftPendulum3D and OctoArmSingle with their own feature sets only"
+    if kind == ENV_ARM_SINGLE and tuple(cfg.plane_normal) != (0.0, 0.0, 1.0):
+        return "per-env material: OctoArmSingle on a contact plane with normal e_z only"
+    if tapered:
+        return "per-env material: not for a tapered rod"
+    if int(cfg.n_elem) > 63:
+        return "per-env material: rods of up to 63 elements only"
+    if int(cfg.early_termination):
+        return "per-env material: not with early_termination"
+    return None
+
+
+def env_material_defaults(cfg: "SoftrodConfig") -> "np.ndarray":
+    """(4,) float64: the config's own youngs_modulus, shear_modulus, density, damping_constant."""
+    import numpy as np
+
+    return np.array([cfg.youngs_modulus, cfg.shear_modulus, cfg.density, cfg.damping_constant], np.float64)
+
+
 class SoftrodError(RuntimeError):
     pass
 
@@ -774,6 +803,7 @@ _EXPORTS = {
     "softrod_exchange_free": (C.c_int, [C.c_int, _VP]),
     "softrod_observe": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_rod_energies": (C.c_int, [_VP, _VP, _VP]),
+    "softrod_set_env_material": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_substeps": (C.c_int, [_VP, _VP, C.c_int, _VP]),
     "softrod_state_view_get": (C.c_int, [_VP, C.POINTER(SoftrodStateView)]),
     "softrod_set_timing": (C.c_int, [_VP, C.c_int]),

@@ -121,6 +121,26 @@ class HipRodBackend:
         check(self._lib.softrod_set_muscle_layers(self._h, rp.ctypes.data, st.ctypes.data), self._h)
         self._tables["muscle_layers"] = rp.tobytes() + st.tobytes()
 
+    def set_env_material(self, material, mask: Optional[np.ndarray] = None) -> None:
+        """softrod_set_env_material: per-env (E, G, rho, nu), host (n_envs, 4) float64; only rows with mask != 0
+        change.  Takes effect at the next launch on the current stream; persists through resets."""
+        why = _capi.env_material_refusal(self.cfg, tapered="radius_profile" in self._tables)
+        if why is not None:
+            raise NotImplementedError(why)
+        m = np.ascontiguousarray(material, dtype=np.float64).reshape(self.n_envs, 4)
+        k = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.n_envs)
+        check(self._lib.softrod_set_env_material(self._h, m.ctypes.data, None if k is None else k.ctypes.data,
+                                                 self._stream()), self._h)
+        cur = self.env_material()
+        self._env_material = np.where(k[:, None] != 0, m, cur) if k is not None else m.copy()
+
+    def env_material(self) -> np.ndarray:
+        """(n_envs, 4) float64 host copy of every env's (E, G, rho, nu): the config's until set_env_material."""
+        cur = getattr(self, "_env_material", None)
+        if cur is None:
+            return np.tile(_capi.env_material_defaults(self.cfg), (self.n_envs, 1))
+        return cur.copy()
+
     def reset(self, theta0: np.ndarray, mask: Optional[np.ndarray] = None) -> None:
         th = np.ascontiguousarray(theta0, dtype=np.float64).reshape(self.n_envs)
         m = None
@@ -441,6 +461,8 @@ class HipRodBackend:
         st = self.state()
         torch.cuda.synchronize(self.device)
         snap = {k: st[k].cpu().clone() for k in self._snapshot_keys()}
+        if getattr(self, "_env_material", None) is not None:        # per-env material (set_env_material)
+            snap["env_material"] = torch.from_numpy(self._env_material.copy())
         snap["config_fingerprint"] = torch.frombuffer(bytearray(self.config_fingerprint()), dtype=torch.uint8).clone()
         return snap
 
@@ -458,6 +480,11 @@ class HipRodBackend:
             if tuple(snap[k].shape) != tuple(st[k].shape):
                 raise ValueError(f"snapshot field {k!r} has shape {tuple(snap[k].shape)}, expected {tuple(st[k].shape)}")
             st[k].copy_(snap[k].to(self.device))
+        # the material the snapshot was taken under; no key: the config's own values
+        if "env_material" in snap:
+            self.set_env_material(snap["env_material"].numpy())
+        elif getattr(self, "_env_material", None) is not None:
+            self.set_env_material(np.tile(_capi.env_material_defaults(self.cfg), (self.n_envs, 1)))
         torch.cuda.synchronize(self.device)
 
     def rod_snapshot(self, env_indices) -> Dict[str, np.ndarray]:

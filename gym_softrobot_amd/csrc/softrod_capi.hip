@@ -76,6 +76,10 @@ struct softrod_handle {
     hipEvent_t ev_status = nullptr;
     bool status_pending = false;
     hipEvent_t ev_queue = nullptr;  // guards reuse of h_queue / h_produced
+    // per-env material (softrod_set_env_material): nullptr until the first call
+    EnvMaterial* d_env_mat = nullptr;  // [N]
+    EnvMaterial* h_env_mat = nullptr;  // pinned [N]: every row as last uploaded (the staging buffer)
+    hipEvent_t ev_env_mat = nullptr;   // guards reuse of h_env_mat
     std::string err;
 };
 
@@ -256,6 +260,42 @@ bool is_pull(const softrod_handle* h) { return h->cfg.env_kind == SOFTROD_ENV_AR
 // the muscle octopus envs (softrod_mocto.hpp): FlatEnv's host API (arm frames + target), the muscle arm's tables
 bool mocto_kind(int e) { return e == SOFTROD_ENV_CRAWL || e == SOFTROD_ENV_ARM_TWO || e == SOFTROD_ENV_REACH; }
 bool is_mocto(const softrod_handle* h) { return mocto_kind(h->cfg.env_kind); }
+// softrod_set_env_material's scope: a uniform one-slot rod of SoftPendulum, SoftPendulum3D or OctoArmSingle with the
+// env's own feature set (the three kFeatEnvMaterial instantiations; the LIBM kernel reads the table at run time).
+// nullptr: in scope; else why not.
+const char* env_material_refusal(const softrod_handle* h) {
+    const unsigned f = h->cfg.features;
+    const int e = h->cfg.env_kind;
+    const bool zup = (h->P.features & kFeatPlaneZup) != 0;
+    if (is_octo(h) || is_mocto(h)) return "per-env material: not for OctoFlat or the muscle octopus envs";
+    if (f & SOFTROD_FEAT_COOMM_MUSCLES) return "per-env material: not for the muscle envs";
+    if (e == SOFTROD_ENV_SOFT_ARM) return "per-env material: not for SoftArmTracking (its muscle torque scale depends on E)";
+    if (h->tapered) return "per-env material: not for a tapered rod (softrod_set_radius_profile)";
+    if (h->epl != 1 || h->window_refresh > 0)
+        return "per-env material: rods of up to 63 elements only (not the two-slot or windowed long rods)";
+    const bool known = (f == SOFTROD_FEATURES_SOFTPENDULUM && e == SOFTROD_ENV_SOFTPENDULUM) ||
+                       (f == SOFTROD_FEATURES_SOFTPENDULUM3D && e == SOFTROD_ENV_SOFTPENDULUM3D) ||
+                       (f == SOFTROD_FEATURES_ARM_SINGLE && e == SOFTROD_ENV_ARM_SINGLE && zup);
+    if (!known || h->cfg.early_termination)
+        return "per-env material: SoftPendulum, SoftPendulum3D and OctoArmSingle with their own feature sets only";
+    return nullptr;
+}
+// One row of the per-env table: fill_params itself on the config with this env's (E, G, rho, nu).
+void env_material_row(const softrod_config& c, const double m[4], EnvMaterial& R) {
+    softrod_config ci = c;
+    ci.youngs_modulus = m[0];
+    ci.shear_modulus = m[1];
+    ci.density = m[2];
+    ci.damping_constant = m[3];
+    RodParams Q;
+    fill_params(ci, Q);
+    std::memset(&R, 0, sizeof(R));
+    for (int i = 0; i < 3; ++i) {
+        R.J[i] = Q.J[i]; R.invJ[i] = Q.invJ[i]; R.shear[i] = Q.shear[i]; R.bend[i] = Q.bend[i];
+        R.damp_r[i] = Q.damp_r[i]; R.damp_logr[i] = Q.damp_logr[i];
+    }
+    R.mass_node = Q.mass_node; R.mass_total = Q.mass_total; R.damp_t = Q.damp_t;
+}
 
 int launch_step(softrod_handle* h, const float* actions, float* obs, double* reward,
                 uint8_t* term, uint8_t* trunc, double* aux, int n_sub, int epilogue, int pack,
@@ -291,6 +331,9 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
         // only the instantiations FOR the flag evaluate it (kFeatEarlyTerm): never let another kernel ignore it
         return fail(h, SOFTROD_EINVAL, "early_termination (SOFTROD_MATH_FAST) runs on the tapered SOFTROD_FEATURES_ARM_PUSH arm "
                                        "and on SOFTROD_ENV_ARM_PULL_WEIGHT only; other feature mixes: SOFTROD_MATH_LIBM");
+    if (h->d_env_mat) {   // never let a kernel that ignores the per-env table step this handle
+        if (const char* why = env_material_refusal(h)) return fail(h, SOFTROD_EINVAL, why);
+    }
     const bool timing = h->timed < (int)h->ev_start.size();
     if (timing) SR_HIP(h, hipEventRecord(h->ev_start[h->timed], st));
     const bool zup = (h->P.features & kFeatPlaneZup) != 0;
@@ -390,7 +433,16 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
             else
                 SR_LAUNCH_TAPER(kRuntimeFeatures, kRuntimeEnv);
 #undef SR_LAUNCH_TAPER
-        } else if (h->epl == 2) SR_DISPATCH(2); else SR_DISPATCH(1);
+        } else if (h->epl == 2) SR_DISPATCH(2);
+        else if (h->d_env_mat) {   // per-env material: the instantiations FOR it (kFeatEnvMaterial; env_material_refusal
+                                   // has admitted exactly these three)
+            if (e == SOFTROD_ENV_SOFTPENDULUM)
+                SR_LAUNCH(SOFTROD_FEATURES_SOFTPENDULUM | kFeatEnvMaterial, SOFTROD_ENV_SOFTPENDULUM, 1);
+            else if (e == SOFTROD_ENV_SOFTPENDULUM3D)
+                SR_LAUNCH(SOFTROD_FEATURES_SOFTPENDULUM3D | kFeatEnvMaterial, SOFTROD_ENV_SOFTPENDULUM3D, 1);
+            else
+                SR_LAUNCH(SOFTROD_FEATURES_ARM_SINGLE | kFeatPlaneZup | kFeatEnvMaterial, SOFTROD_ENV_ARM_SINGLE, 1);
+        } else SR_DISPATCH(1);
 #undef SR_DISPATCH
 #undef SR_LAUNCH
     } else if (h->cfg.early_termination) {
@@ -1404,6 +1456,42 @@ int softrod_set_radius_profile(softrod_handle* h, const double* radius) {
     return SOFTROD_OK;
 }
 
+int softrod_set_env_material(softrod_handle* h, const double* material, const uint8_t* mask, void* stream) {
+    if (!h || !material) return fail(h, SOFTROD_EINVAL, "null argument");
+    if (const char* why = env_material_refusal(h)) return fail(h, SOFTROD_EINVAL, why);
+    const size_t N = (size_t)h->cfg.n_envs;
+    for (size_t i = 0; i < N; ++i) {
+        if (mask && !mask[i]) continue;
+        const double* m = material + 4 * i;
+        if (!(std::isfinite(m[0]) && std::isfinite(m[1]) && std::isfinite(m[2]) && std::isfinite(m[3])))
+            return fail(h, SOFTROD_EINVAL, "per-env material: env " + std::to_string(i) + " has a non-finite value");
+        if (!(m[0] > 0.0 && m[1] > 0.0 && m[2] > 0.0 && m[3] >= 0.0))
+            return fail(h, SOFTROD_EINVAL, "per-env material: env " + std::to_string(i) +
+                                               " needs E, G, density > 0 and damping constant >= 0");
+    }
+    SR_ON_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (!h->d_env_mat) {   // every row starts at the config's own constants
+        SR_HIP(h, hipMalloc((void**)&h->d_env_mat, N * sizeof(EnvMaterial)));
+        SR_HIP(h, hipHostMalloc((void**)&h->h_env_mat, N * sizeof(EnvMaterial), hipHostMallocDefault));
+        SR_HIP(h, hipEventCreateWithFlags(&h->ev_env_mat, hipEventDisableTiming));
+        const softrod_config& c = h->cfg;
+        const double m0[4] = {c.youngs_modulus, c.shear_modulus, c.density, c.damping_constant};
+        EnvMaterial R0;
+        env_material_row(c, m0, R0);
+        for (size_t i = 0; i < N; ++i) h->h_env_mat[i] = R0;
+        h->S.env_mat = h->d_env_mat;
+        SR_HIP(h, hipMemcpy(h->d_state, &h->S, sizeof(StatePtrs), hipMemcpyHostToDevice));
+    } else {
+        SR_HIP(h, hipEventSynchronize(h->ev_env_mat));   // the previous upload has left the staging buffer
+    }
+    for (size_t i = 0; i < N; ++i)
+        if (!mask || mask[i]) env_material_row(h->cfg, material + 4 * i, h->h_env_mat[i]);
+    SR_HIP(h, hipMemcpyAsync(h->d_env_mat, h->h_env_mat, N * sizeof(EnvMaterial), hipMemcpyHostToDevice, st));
+    SR_HIP(h, hipEventRecord(h->ev_env_mat, st));
+    return SOFTROD_OK;
+}
+
 int softrod_set_muscle_layers(softrod_handle* h, const double* ratio_position, const double* strength) {
     if (!h || !ratio_position || !strength) return fail(h, SOFTROD_EINVAL, "null argument");
     if (!(h->cfg.features & SOFTROD_FEAT_COOMM_MUSCLES)) return fail(h, SOFTROD_EINVAL, "this handle has no COOMM muscles");
@@ -1761,6 +1849,7 @@ const char* softrod_kernel_tier(softrod_handle* h) {
             (h->tapered ? ",taper>" : ">");
     } else
         t = "softrod_step_libm_kernel";
+    if (h->d_env_mat) t += ",env material";
     h->tier = t;
     return h->tier.c_str();
 }
@@ -1771,9 +1860,11 @@ int softrod_destroy(softrod_handle* h) {
     (void)hipDeviceSynchronize();
     autoreset_release(h);
     void* bufs[] = {h->S.pos, h->S.vel, h->S.dir, h->S.omg, h->S.tan, h->S.time, h->S.bc,
-                    h->S.ctrl, h->S.kap, h->S.rkap, h->S.envmem, h->S.prev_action, h->S.head, h->d_params, h->d_state, h->d_time_tab, h->d_mat, h->d_sucker, h->d_sucker_idx, h->d_aux, h->d_prev_kappa, h->d_mact, h->d_mtab, h->d_basis, h->d_spline, h->d_init, h->d_mask, h->d_ticket};
+                    h->S.ctrl, h->S.kap, h->S.rkap, h->S.envmem, h->S.prev_action, h->S.head, h->d_params, h->d_state, h->d_time_tab, h->d_mat, h->d_sucker, h->d_sucker_idx, h->d_aux, h->d_prev_kappa, h->d_mact, h->d_mtab, h->d_basis, h->d_spline, h->d_init, h->d_mask, h->d_ticket, h->d_env_mat};
     for (void* p : bufs) (void)hipFree(p);
     if (h->h_init) (void)hipHostFree(h->h_init);
+    if (h->h_env_mat) (void)hipHostFree(h->h_env_mat);
+    if (h->ev_env_mat) (void)hipEventDestroy(h->ev_env_mat);
     if (h->h_mask) (void)hipHostFree(h->h_mask);
     for (hipEvent_t e : h->ev_start) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->ev_stop) (void)hipEventDestroy(e);

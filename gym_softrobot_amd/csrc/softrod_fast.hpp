@@ -320,6 +320,8 @@ template <unsigned F, int EPL, bool TAPER = false, class Connections = NoConnect
 __device__ __forceinline__ void dynamic_n(const RodParams& P, const ConstN<EPL>& C, const BcTargets& B,
                                           int lane, LaneN<EPL>& L, Connections&& connect = Connections()) {
     const int n = P.n_elem;
+    // material constants from C (build_const_m): per lane for a tapered rod, the env's row for kFeatEnvMaterial
+    constexpr bool MC = TAPER || kEnvMaterial<F>;
     double xn[EPL][3], vn[EPL][3], d[EPL][3];
     double len[EPL], il[EPL], e[EPL], ie[EPL];
     double qt[EPL][3], np[EPL][3], cs[EPL][3], f[EPL][3], tq[EPL][3];
@@ -453,7 +455,7 @@ __device__ __forceinline__ void dynamic_n(const RodParams& P, const ConstN<EPL>&
         const double num = fma(d[s][2], vn[s][2] - L.v[s][2],
                                fma(d[s][1], vn[s][1] - L.v[s][1], d[s][0] * (vn[s][0] - L.v[s][0])));
         const double sdil = num * il[s] * il[s];
-        const double j01 = (TAPER ? C.j01[s] : P.J[0]) * ie[s], j2 = (TAPER ? C.j2[s] : P.J[2]) * ie[s];
+        const double j01 = (MC ? C.j01[s] : P.J[0]) * ie[s], j2 = (MC ? C.j2[s] : P.J[2]) * ie[s];
         const double z = w[2] * (j01 - j2);
         tq[s][0] = fma(w[1], z, tq[s][0]);
         tq[s][1] = fma(-w[0], z, tq[s][1]);
@@ -507,7 +509,8 @@ __device__ __forceinline__ void dynamic_n(const RodParams& P, const ConstN<EPL>&
     for (int s = 0; s < EPL; ++s) {
         const bool elem_valid = slot_local<F>(P, lane * EPL + s) < n;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) fma_inplace_u(L.v[s][c], P.damp_t, fma(C.cf[s], f[s][c], C.ca[s][c]));
+        for (int c = 0; c < 3; ++c)
+            fma_inplace_u(L.v[s][c], kEnvMaterial<F> ? C.damp_t : P.damp_t, fma(C.cf[s], f[s][c], C.ca[s][c]));
         const double ce01 = C.cw01[s] * e[s], ce2 = C.cw2[s] * e[s];
         double w0 = fma(ce01, tq[s][0], L.w[s][0]), w1 = fma(ce01, tq[s][1], L.w[s][1]),
                w2 = fma(ce2, tq[s][2], L.w[s][2]);
@@ -516,7 +519,7 @@ __device__ __forceinline__ void dynamic_n(const RodParams& P, const ConstN<EPL>&
             // c_r^e = c_r * c_r^(e-1): the strain e-1 is small, so the exponent stays in the
             // polynomial's range also where log c_r is not (octopus arms: log c_r = -0.057)
             const double em1 = e[s] - 1.0;
-            double x0 = em1 * (TAPER ? C.dlog0[s] : P.damp_logr[0]), x2 = em1 * (TAPER ? C.dlog2[s] : P.damp_logr[2]);
+            double x0 = em1 * (MC ? C.dlog0[s] : P.damp_logr[0]), x2 = em1 * (MC ? C.dlog2[s] : P.damp_logr[2]);
             if constexpr (TAPER) {
                 // The thin end of a tapered arm has log c_r = -nu dt m / J of -2000 and less (c_r underflows to 0: the
                 // damper annihilates omega there, pow(0, e) = 0 in the reference's arithmetic); a COMPRESSED element
@@ -525,7 +528,7 @@ __device__ __forceinline__ void dynamic_n(const RodParams& P, const ConstN<EPL>&
                 x0 = fmin(x0, 700.0); x2 = fmin(x2, 700.0);
             }
             exp_pair(x0, x2, elem_valid, ex0, ex2);
-            ex0 *= TAPER ? C.dr0[s] : P.damp_r[0]; ex2 *= TAPER ? C.dr2[s] : P.damp_r[2];
+            ex0 *= MC ? C.dr0[s] : P.damp_r[0]; ex2 *= MC ? C.dr2[s] : P.damp_r[2];
             w0 *= ex0; w1 *= ex0; w2 *= ex2;
         }
         L.w[s][0] = w0; L.w[s][1] = w1; L.w[s][2] = w2;
@@ -536,7 +539,8 @@ __device__ __forceinline__ void dynamic_n(const RodParams& P, const ConstN<EPL>&
         sucker_rates_n<F, EPL>(P, B, lane, L);
     } else {
         BcTargets Bs = B;
-        Bs.vel[0] *= P.damp_t; Bs.vel[1] *= P.damp_t; Bs.vel[2] *= P.damp_t;
+        const double dt_v = kEnvMaterial<F> ? C.damp_t : P.damp_t;
+        Bs.vel[0] *= dt_v; Bs.vel[1] *= dt_v; Bs.vel[2] *= dt_v;
         constrain_rates_n<F, EPL>(P, Bs, lane, L);
         sucker_rates_n<F, EPL>(P, B, lane, L);
         if (has<F>(P, SOFTROD_FEAT_LAPLACE_FILTER)) laplace_filter_rates_fast<EPL>(P, lane, L);
@@ -680,7 +684,8 @@ __device__ __attribute__((noinline)) void general_step_cold(const RodParams* __r
     constrain_values_n<F, EPL>(P, B, lane, L);
     double time = S.time[rod];
     ConstN<EPL> C;
-    build_const<F, EPL>(P, lane, A, C);
+    if constexpr (kEnvMaterial<F>) build_const_m<F, EPL>(P, S.env_mat[rod], lane, A, C);   // the env's row
+    else build_const<F, EPL>(P, lane, A, C);
     RodParams Pk = P;
     if (!has<F>(P, SOFTROD_FEAT_ANALYTICAL_DAMPER)) Pk.damp_t = 1.0;
     general_substeps<F, EPL>(P, Pk, C, B, lane, L, n_sub);
@@ -733,7 +738,7 @@ constexpr int fast_kernel_waves() {
              SOFTROD_FEAT_COOMM_MUSCLES))
         return SOFTROD_CONTACT_WAVES;
     if (TAPER) return SOFTROD_CONTACT_WAVES;
-    return F == SOFTROD_FEATURES_SOFTPENDULUM ? SOFTROD_PLANAR_WAVES : SOFTROD_FAST_WAVES;
+    return (F & ~kFeatEnvMaterial) == SOFTROD_FEATURES_SOFTPENDULUM ? SOFTROD_PLANAR_WAVES : SOFTROD_FAST_WAVES;
 }
 
 template <unsigned F, int E, int EPL, bool TAPER = false>
@@ -745,6 +750,11 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
     const int rod = blockIdx.x;
     const int lane = threadIdx.x;
     const size_t N = (size_t)P.n_envs;
+    // kFeatEnvMaterial: this env's material row, loaded once per launch ahead of every store and every intrinsic with
+    // side effects, so that the wave-uniform address makes scalar loads into SGPRs; build_const_m takes it in place
+    // of RodParams' fields
+    [[maybe_unused]] EnvMaterial M;
+    if constexpr (kEnvMaterial<F>) M = S.env_mat[rod];
     if (epilogue && S.skip && S.skip[rod]) {   // reset by the auto-reset pass of this env.step
         if (lane == 0) S.skip[rod] = 0;
         if (lane == 0 && early_term_on<F>(P)) S.aux[rod] = 0.0;   // no time limit on a restart
@@ -775,7 +785,8 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
     }
     double time = S.time[rod];
     ConstN<EPL> C;
-    build_const<F, EPL, TAPER>(P, lane, A, C, S.mat);
+    if constexpr (kEnvMaterial<F>) build_const_m<F, EPL, TAPER>(P, M, lane, A, C, S.mat);
+    else build_const_m<F, EPL, TAPER>(P, P, lane, A, C, S.mat);
     if constexpr (kMusclesCompiled<F>) build_muscle_const<F, EPL, true>(P, S, N, rod, lane, A, C);
     RodParams Pk = P;
     if (!has<F>(P, SOFTROD_FEAT_ANALYTICAL_DAMPER)) Pk.damp_t = 1.0;
@@ -791,13 +802,13 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
         time = clock_after(P, S, time, n_sub);
         stepped = true;
     }
-    if constexpr (F == SOFTROD_FEATURES_SOFTPENDULUM) {
+    if constexpr ((F & ~kFeatEnvMaterial) == SOFTROD_FEATURES_SOFTPENDULUM) {
         // SoftPendulum-v0 lives in the x-y plane: same substep without the identically
         // zero out-of-plane terms (softrod_planar.hpp); any other state takes the 3-D loop
         PlanarN<EPL> Z;
         if (n_sub > 0 && !stepped && planar_from_lane<EPL>(P, B, lane, L, Z)) {
             PlanarC<EPL> K;
-            planar_build_const<EPL>(Pk, C, lane, K);
+            planar_build_const<EPL, kEnvMaterial<F>>(Pk, C, lane, K);
             // The clock takes the reference's additions in the reference's order: 2 n_sub times
             // +dt/2, or n_sub times +dt.  They are 2 of the loop's ~100 VALU instructions, and the
             // result does not depend on the rod: the host has accumulated the same sequence of
@@ -877,7 +888,7 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
         }
     }
     if (n_sub > 0 && !stepped) {
-        if constexpr (F == SOFTROD_FEATURES_SOFTPENDULUM) {
+        if constexpr ((F & ~kFeatEnvMaterial) == SOFTROD_FEATURES_SOFTPENDULUM) {
             general_step_cold<F, E, EPL>(S.params, S.self, rod, lane, actions, n_sub);   // HBM -> HBM
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             load_lane<EPL, F>(S, N, rod, lane, L);

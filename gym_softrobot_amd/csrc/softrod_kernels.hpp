@@ -60,6 +60,13 @@ constexpr unsigned kFeatPlaneZup = 1u << 30;
 // RodParams.features and in the template mask of the instantiations that carry it, so that the default ones compile
 // none of it)
 constexpr unsigned kFeatEarlyTerm = 1u << 29;
+// Internal pseudo-feature: the handle has a per-env material table (softrod_set_env_material, StatePtrs.env_mat).  Only
+// in the template mask of the instantiations FOR it, which load their env's row once per launch; launch_step refuses
+// a handle with the table any other fast kernel.  The cold kernels (LIBM step, reset, auto-reset, observe, energies)
+// read the table at run time when StatePtrs.env_mat is set.
+constexpr unsigned kFeatEnvMaterial = 1u << 28;
+template <unsigned F>
+constexpr bool kEnvMaterial = F != kRuntimeFeatures && (F & kFeatEnvMaterial) != 0;
 constexpr int kRuntimeEnv = -1;
 // The fast kernel carries the COOMM muscle layers (softrod_muscle.hpp) in the instantiations compiled FOR a feature
 // set that has them: OctoArmPush (SOFTROD_FEATURES_ARM_PUSH) and the clamped / free muscle rod of the known-answer
@@ -122,6 +129,18 @@ struct RodParams {
 enum MatRow { kMatMass = 0, kMatShear01, kMatShear2, kMatBend01, kMatBend2, kMatJ0, kMatJ2, kMatInvJ0, kMatInvJ2,
               kMatDampLog0, kMatDampLog2, kMatDampR0, kMatDampR2, kMatR0s, kMatInvR0s, kMatRows = SOFTROD_MATERIAL_ROWS };
 
+// One env's row of the per-env material table (softrod_set_env_material): the constants fill_params derives from
+// (E, G, rho, nu), laid out with RodParams' names so that either can be the material source of build_const_m.
+// 24 doubles: three 64-byte lines.
+struct EnvMaterial {
+    double J[3], invJ[3];
+    double shear[3], bend[3];
+    double mass_node, mass_total, damp_t;
+    double damp_r[3], damp_logr[3];
+    double pad[3];
+};
+static_assert(sizeof(EnvMaterial) == 192, "EnvMaterial: three 64-byte lines");
+
 struct StatePtrs {
     double* pos;   // [3][N][64]
     double* vel;   // [3][N][64]
@@ -159,6 +178,7 @@ struct StatePtrs {
     // the muscle octopus envs (softrod_mocto.hpp): `sucker` / `sucker_idx` are [SOFTROD_MAX_SUCKERS][N * n_arm] there
     double* aux;            // [8][N] target x, y, z; the head's x, y before the step
     float* prev_kappa;      // [N][n_arm * (n_elem - 1)] ArmTwoEnv._prev_kappa
+    const EnvMaterial* env_mat;   // [N] per-env material rows (softrod_set_env_material), or nullptr (RodParams)
 };
 
 // ---------------------------------------------------------------------------------
@@ -254,6 +274,8 @@ struct ConstN {
     double mr[EPL][SOFTROD_MAX_MUSCLES][3], amp[EPL][SOFTROD_MAX_MUSCLES];
     const double* mtab_lane;   // the same from memory (run-time-mask / LIBM kernels): StatePtrs.mtab / .mact at this lane's slot 0
     const double* mact_lane;
+    // wave-uniform: the damper's exp(-nu dt) (1 without the damper) and the rod's mass, from build_const's material source
+    double damp_t, mass_total;
 };
 
 // value of index+1 / index-1 for a per-slot array
@@ -738,7 +760,7 @@ __device__ __forceinline__ void com_xy_n(const RodParams& P, const ConstN<EPL>& 
 #pragma unroll
         for (int s = 0; s < EPL; ++s)
             p += (slot_local(P, lane * EPL + s) <= P.n_elem) ? C.mass[s] * L.x[s][c] : 0.0;
-        com[c] = wave_sum(p) / P.mass_total;
+        com[c] = wave_sum(p) / C.mass_total;
     }
 }
 
@@ -957,14 +979,16 @@ __device__ __forceinline__ void env_observe_n(const RodParams& P, const StatePtr
 // the boundary condition's constrain_values), while v and omega are the end-of-step rates
 // (diagnostics.mid_substep_configuration).  time == 0 (a reset, no substep yet): the state as
 // it stands.  The rod starts at lane 0 of the wave (slot j = lane * EPL + s is node / element
-// j); `mat` is the tapered rod's material table (indexed by j) or nullptr (uniform: RodParams);
+// j); `mat` is the tapered rod's material table (indexed by j) or nullptr (uniform: M, RodParams or the env's
+// EnvMaterial row);
 // `B` the boundary condition's targets (`bc` false: constrain_values is a no-op).  Out of
 // the substep path: libm acos / sin / cos.  -> E[4] = translational, rotational, bending, shear
 // (the same in every lane).
 // ---------------------------------------------------------------------------------
-template <int EPL>
-__device__ __forceinline__ void rod_energies_n(const RodParams& P, const double* __restrict__ mat, const BcTargets& B,
-                                               bool bc, int lane, const LaneN<EPL>& L, double time, double (&E)[4]) {
+template <int EPL, class Mat>
+__device__ __forceinline__ void rod_energies_m(const RodParams& P, const Mat& M, const double* __restrict__ mat,
+                                               const BcTargets& B, bool bc, int lane, const LaneN<EPL>& L, double time,
+                                               double (&E)[4]) {
     const int n = P.n_elem;
     const bool mid = time != 0.0;
     const double h = P.half_dt;
@@ -1035,16 +1059,16 @@ __device__ __forceinline__ void rod_energies_n(const RodParams& P, const double*
         const int j = lane * EPL + s;
         if (j <= n) {
             const double m = mat ? mat[(size_t)kMatMass * kLanes * EPL + j]
-                                 : ((j == 0 || j == n) ? 0.5 * P.mass_node : P.mass_node);
+                                 : ((j == 0 || j == n) ? 0.5 * M.mass_node : M.mass_node);
             et += m * (L.v[s][0] * L.v[s][0] + L.v[s][1] * L.v[s][1] + L.v[s][2] * L.v[s][2]);
         }
         if (j < n) {
-            const double J0 = mat ? mat[(size_t)kMatJ0 * kLanes * EPL + j] : P.J[0];
-            const double J1 = mat ? J0 : P.J[1];
-            const double J2 = mat ? mat[(size_t)kMatJ2 * kLanes * EPL + j] : P.J[2];
-            const double S0 = mat ? mat[(size_t)kMatShear01 * kLanes * EPL + j] : P.shear[0];
-            const double S1 = mat ? S0 : P.shear[1];
-            const double S2 = mat ? mat[(size_t)kMatShear2 * kLanes * EPL + j] : P.shear[2];
+            const double J0 = mat ? mat[(size_t)kMatJ0 * kLanes * EPL + j] : M.J[0];
+            const double J1 = mat ? J0 : M.J[1];
+            const double J2 = mat ? mat[(size_t)kMatJ2 * kLanes * EPL + j] : M.J[2];
+            const double S0 = mat ? mat[(size_t)kMatShear01 * kLanes * EPL + j] : M.shear[0];
+            const double S1 = mat ? S0 : M.shear[1];
+            const double S2 = mat ? mat[(size_t)kMatShear2 * kLanes * EPL + j] : M.shear[2];
             const double d0 = xn[s][0] - x[s][0], d1 = xn[s][1] - x[s][1], d2 = xn[s][2] - x[s][2];
             const double l = sqrt(d0 * d0 + d1 * d1 + d2 * d2) + P.eps_length;
             const double e = l / P.rest_len;
@@ -1057,9 +1081,9 @@ __device__ __forceinline__ void rod_energies_n(const RodParams& P, const double*
             es += (S0 * s0 * s0 + S1 * s1 * s1 + S2 * s2 * s2) * P.rest_len;
         }
         if (j < n - 1) {
-            const double B0 = mat ? mat[(size_t)kMatBend01 * kLanes * EPL + j] : P.bend[0];
-            const double B1 = mat ? B0 : P.bend[1];
-            const double B2 = mat ? mat[(size_t)kMatBend2 * kLanes * EPL + j] : P.bend[2];
+            const double B0 = mat ? mat[(size_t)kMatBend01 * kLanes * EPL + j] : M.bend[0];
+            const double B1 = mat ? B0 : M.bend[1];
+            const double B2 = mat ? mat[(size_t)kMatBend2 * kLanes * EPL + j] : M.bend[2];
             // kappa = -log(Q_{k+1} Q_k^T) / D^  (_inv_rotate, as rod_strains)
             double R[9];
 #pragma unroll
@@ -1081,6 +1105,11 @@ __device__ __forceinline__ void rod_energies_n(const RodParams& P, const double*
     E[1] = 0.5 * wave_sum(er);
     E[2] = 0.5 * wave_sum(eb);
     E[3] = 0.5 * wave_sum(es);
+}
+template <int EPL>
+__device__ __forceinline__ void rod_energies_n(const RodParams& P, const double* __restrict__ mat, const BcTargets& B,
+                                               bool bc, int lane, const LaneN<EPL>& L, double time, double (&E)[4]) {
+    rod_energies_m<EPL>(P, P, mat, B, bc, lane, L, time, E);
 }
 
 template <int E, int EPL, unsigned F = kRuntimeFeatures, bool RT = false>
@@ -1240,13 +1269,16 @@ __device__ __forceinline__ void env_epilogue_n(const RodParams& P, const StatePt
     }
 }
 
-template <unsigned F, int EPL, bool TAPER = false>
-__device__ __forceinline__ void build_const(const RodParams& P, int lane, const EnvAction& A,
-                                            ConstN<EPL>& C, const double* __restrict__ mat = nullptr) {
+// M: the material source of a uniform rod — P itself, or the env's EnvMaterial row (the same field names)
+template <unsigned F, int EPL, bool TAPER = false, class Mat>
+__device__ __forceinline__ void build_const_m(const RodParams& P, const Mat& M, int lane, const EnvAction& A,
+                                              ConstN<EPL>& C, const double* __restrict__ mat = nullptr) {
     const int n = P.n_elem;
     const bool damp = has<F>(P, SOFTROD_FEAT_ANALYTICAL_DAMPER);
-    const double ct = damp ? P.damp_t : 1.0;
+    const double ct = damp ? M.damp_t : 1.0;
     constexpr int W = kLanes * EPL;
+    C.damp_t = ct;
+    C.mass_total = M.mass_total;
 #pragma unroll
     for (int s = 0; s < EPL; ++s) {
         const int raw = lane * EPL + s;
@@ -1256,10 +1288,10 @@ __device__ __forceinline__ void build_const(const RodParams& P, int lane, const 
                                                SOFTROD_FEAT_MOVING_BASE_BC);
         const bool held_x = first && has<F>(P, SOFTROD_FEAT_FIXED_BC | SOFTROD_FEAT_MOVING_BASE_BC);
         const bool node_valid = idx <= n, elem_valid = idx < n, vor_valid = idx < n - 1;
-        double mass = (idx == 0 || idx == n) ? 0.5 * P.mass_node : P.mass_node;
-        double mass_next = (idx + 1 == n) ? 0.5 * P.mass_node : P.mass_node;
-        double shear01 = P.shear[0], shear2 = P.shear[2], bend01 = P.bend[0], bend2 = P.bend[2];
-        double invJ0 = P.invJ[0], invJ2 = P.invJ[2];
+        double mass = (idx == 0 || idx == n) ? 0.5 * M.mass_node : M.mass_node;
+        double mass_next = (idx + 1 == n) ? 0.5 * M.mass_node : M.mass_node;
+        double shear01 = M.shear[0], shear2 = M.shear[2], bend01 = M.bend[0], bend2 = M.bend[2];
+        double invJ0 = M.invJ[0], invJ2 = M.invJ[2];
         if constexpr (TAPER) {      // CosseratRod.straight_rod with an array of radii: per-element constants
             // (the table is one wave wide; the arms of a multi-wave env repeat it: softrod_set_radius_profile)
             const int wide = raw;
@@ -1275,9 +1307,9 @@ __device__ __forceinline__ void build_const(const RodParams& P, int lane, const 
             C.dr0[s] = mat[kMatDampR0 * W + raw]; C.dr2[s] = mat[kMatDampR2 * W + raw];
             C.r0s[s] = mat[kMatR0s * W + raw]; C.ir0s[s] = mat[kMatInvR0s * W + raw];
         } else {
-            C.j01[s] = P.J[0]; C.j2[s] = P.J[2];
-            C.dlog0[s] = P.damp_logr[0]; C.dlog2[s] = P.damp_logr[2];
-            C.dr0[s] = P.damp_r[0]; C.dr2[s] = P.damp_r[2];
+            C.j01[s] = M.J[0]; C.j2[s] = M.J[2];
+            C.dlog0[s] = M.damp_logr[0]; C.dlog2[s] = M.damp_logr[2];
+            C.dr0[s] = M.damp_r[0]; C.dr2[s] = M.damp_r[2];
             C.r0s[s] = P.r0_sqrt_rest_len; C.ir0s[s] = 1.0 / P.r0_sqrt_rest_len;
         }
         // masses of slots past the rod's end are zeros (so that a product with them needs no select);
@@ -1308,6 +1340,25 @@ __device__ __forceinline__ void build_const(const RodParams& P, int lane, const 
         C.b01[s] = vor_valid ? bend01 : 0.0;
         C.bd[s] = vor_valid ? bend2 - bend01 : 0.0;
     }
+}
+template <unsigned F, int EPL, bool TAPER = false>
+__device__ __forceinline__ void build_const(const RodParams& P, int lane, const EnvAction& A,
+                                            ConstN<EPL>& C, const double* __restrict__ mat = nullptr) {
+    build_const_m<F, EPL, TAPER>(P, P, lane, A, C, mat);
+}
+
+// The material source of a cold kernel (run-time features): env `rod`'s row when the handle has the per-env table
+// (softrod_set_env_material), else the kernel's own RodParams, copied.
+__device__ __forceinline__ EnvMaterial env_material_rt(const RodParams& P, const StatePtrs& S, int rod) {
+    if (S.env_mat) return S.env_mat[rod];
+    EnvMaterial M{};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        M.J[i] = P.J[i]; M.invJ[i] = P.invJ[i]; M.shear[i] = P.shear[i]; M.bend[i] = P.bend[i];
+        M.damp_r[i] = P.damp_r[i]; M.damp_logr[i] = P.damp_logr[i];
+    }
+    M.mass_node = P.mass_node; M.mass_total = P.mass_total; M.damp_t = P.damp_t;
+    return M;
 }
 
 template <unsigned F, int E, int EPL>
@@ -1568,19 +1619,20 @@ __device__ __forceinline__ void libm_kinematic_step(const RodParams& P, double h
     for (int i = 0; i < 9; ++i) L.Q[0][i] = Qn[i];
 }
 
-// The material constants of this lane's element / Voronoi vertex: RodParams for a uniform rod,
-// the per-lane table for a tapered one (softrod_set_radius_profile).
+// The material constants of this lane's element / Voronoi vertex: `E` (RodParams' or the env's row of the per-env
+// table, env_material_rt) for a uniform rod, the per-lane table for a tapered one (softrod_set_radius_profile).
 struct LibmMat {
-    double shear[3], bend[3], J[3], invJ[3], damp_r[3], mass_next, r0s;
+    double shear[3], bend[3], J[3], invJ[3], damp_r[3], mass_next, r0s, damp_t;
 };
-__device__ __forceinline__ void libm_material(const RodParams& P, const double* __restrict__ mat, int lane,
-                                              LibmMat& M) {
+__device__ __forceinline__ void libm_material(const RodParams& P, const EnvMaterial& E, const double* __restrict__ mat,
+                                              int lane, LibmMat& M) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        M.shear[i] = P.shear[i]; M.bend[i] = P.bend[i]; M.J[i] = P.J[i]; M.invJ[i] = P.invJ[i];
-        M.damp_r[i] = P.damp_r[i];
+        M.shear[i] = E.shear[i]; M.bend[i] = E.bend[i]; M.J[i] = E.J[i]; M.invJ[i] = E.invJ[i];
+        M.damp_r[i] = E.damp_r[i];
     }
-    M.mass_next = (lane + 1 == P.n_elem) ? 0.5 * P.mass_node : P.mass_node;
+    M.damp_t = E.damp_t;
+    M.mass_next = (lane + 1 == P.n_elem) ? 0.5 * E.mass_node : E.mass_node;
     M.r0s = P.r0_sqrt_rest_len;
     if (mat) {
         constexpr int W = kLanes;
@@ -1747,7 +1799,7 @@ __device__ __forceinline__ void libm_dynamic_step(const RodParams& P, const Libm
         sucker_rates_n<kRuntimeFeatures, 1>(P, B, lane, L);
     }
     if (P.features & SOFTROD_FEAT_ANALYTICAL_DAMPER) {
-        L.v[0][0] *= P.damp_t; L.v[0][1] *= P.damp_t; L.v[0][2] *= P.damp_t;
+        L.v[0][0] *= M.damp_t; L.v[0][1] *= M.damp_t; L.v[0][2] *= M.damp_t;
         L.w[0][0] *= pow(M.damp_r[0], e);
         L.w[0][1] *= pow(M.damp_r[1], e);
         L.w[0][2] *= pow(M.damp_r[2], e);
@@ -1793,11 +1845,12 @@ softrod_step_libm_kernel(const RodParams P, const StatePtrs S, const float* __re
     set_action_n<kRuntimeFeatures, kRuntimeEnv, 1>(P, S, N, rod, lane, actions, A, B, L);
     if (epilogue) push_store_prev_com<kRuntimeFeatures, kRuntimeEnv, 1>(P, S, N, rod, lane, L, n_sub);
     ConstN<1> C;
-    if (S.mat) build_const<kRuntimeFeatures, 1, true>(P, lane, A, C, S.mat);
-    else build_const<kRuntimeFeatures, 1>(P, lane, A, C);
+    const EnvMaterial E = env_material_rt(P, S, rod);
+    if (S.mat) build_const_m<kRuntimeFeatures, 1, true>(P, E, lane, A, C, S.mat);
+    else build_const_m<kRuntimeFeatures, 1>(P, E, lane, A, C);
     build_muscle_const<kRuntimeFeatures, 1, false>(P, S, N, rod, lane, A, C);
     LibmMat M;
-    libm_material(P, S.mat, lane, M);
+    libm_material(P, E, S.mat, lane, M);
 
     double time = S.time[rod];
     const double mass = C.mass[0];
@@ -1842,8 +1895,9 @@ softrod_observe_kernel(const RodParams P, const StatePtrs S, const float* __rest
     A.force = 0.0;
     A.mu_set = false;
     ConstN<EPL> C;
-    if (S.mat) build_const<kRuntimeFeatures, EPL, true>(P, lane, A, C, S.mat);
-    else build_const<kRuntimeFeatures, EPL>(P, lane, A, C);
+    const EnvMaterial E = env_material_rt(P, S, rod);
+    if (S.mat) build_const_m<kRuntimeFeatures, EPL, true>(P, E, lane, A, C, S.mat);
+    else build_const_m<kRuntimeFeatures, EPL>(P, E, lane, A, C);
     const int adim = (P.env_kind == SOFTROD_ENV_SOFTPENDULUM3D) ? 2
                    : (P.env_kind == SOFTROD_ENV_ARM_SINGLE) ? 7 : (P.env_kind == SOFTROD_ENV_SOFT_ARM) ? 0
                    : is_push_env(P.env_kind) ? (P.push_mode == 0 ? 1 : 2) : 1;
@@ -1904,8 +1958,9 @@ __device__ __forceinline__ void reset_rod(const RodParams& P, const StatePtrs& S
         for (int i = 0; i < 7; ++i) A0.a[i] = 0.0f;
         A0.force = 0.0;
         ConstN<EPL> C;
-        if (S.mat) build_const<kRuntimeFeatures, EPL, true>(P, lane, A0, C, S.mat);
-        else build_const<kRuntimeFeatures, EPL>(P, lane, A0, C);
+        const EnvMaterial E = env_material_rt(P, S, rod);
+        if (S.mat) build_const_m<kRuntimeFeatures, EPL, true>(P, E, lane, A0, C, S.mat);
+        else build_const_m<kRuntimeFeatures, EPL>(P, E, lane, A0, C);
         com_xy_n<EPL>(P, C, lane, L, com);
     }
     if (P.features & SOFTROD_FEAT_COOMM_MUSCLES) {
@@ -1995,8 +2050,9 @@ softrod_autoreset_kernel(const RodParams P, const StatePtrs S, float* __restrict
     A.force = 0.0;
     A.mu_set = false;
     ConstN<EPL> C;
-    if (S.mat) build_const<kRuntimeFeatures, EPL, true>(P, lane, A, C, S.mat);
-    else build_const<kRuntimeFeatures, EPL>(P, lane, A, C);
+    const EnvMaterial E = env_material_rt(P, S, rod);
+    if (S.mat) build_const_m<kRuntimeFeatures, EPL, true>(P, E, lane, A, C, S.mat);
+    else build_const_m<kRuntimeFeatures, EPL>(P, E, lane, A, C);
     float pa[7];
 #pragma unroll
     for (int i = 0; i < 7; ++i) pa[i] = S.prev_action[7 * (size_t)rod + i];
@@ -2052,7 +2108,7 @@ softrod_rod_energies_kernel(const RodParams P, const StatePtrs S, const int rods
         if (P.features & SOFTROD_FEAT_MOVING_BASE_BC) { B.pos[0] = S.ctrl[env]; B.pos[1] = S.ctrl[N + env]; }
     }
     double E[4];
-    rod_energies_n<EPL>(P, S.mat, B, bc, lane, L, S.time[env], E);
+    rod_energies_m<EPL>(P, env_material_rt(P, S, env), S.mat, B, bc, lane, L, S.time[env], E);
     if (lane == 0) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) out[(size_t)rod * 4 + i] = E[i];

@@ -109,7 +109,8 @@ __device__ __forceinline__ void fma_inplace(double& x, double m, double a) {
 __device__ __forceinline__ double rcp3(double x) { return fast_rcp(x); }       // (third order, softrod_kernels.hpp)
 __device__ __forceinline__ double rsqrt3(double x) { return fast_rsqrt(x); }
 
-template <int EPL>
+// EM: the material constants come from C (build_const_m with the env's row, kFeatEnvMaterial), not from P
+template <int EPL, bool EM = false>
 __device__ __forceinline__ void planar_build_const(const RodParams& P, const ConstN<EPL>& C, int lane,
                                                    PlanarC<EPL>& K) {
 #pragma unroll
@@ -121,18 +122,19 @@ __device__ __forceinline__ void planar_build_const(const RodParams& P, const Con
         const double two_vor = 2.0 * P.rest_vor;
         K.bk[s] = C.b01[s] * (P.inv_rest_vor * (1.0 + P.acos_shift * (1.0 / 3.0))) * (two_vor * two_vor * two_vor);
         K.bke[s] = P.neg_eps_sin * K.bk[s];
-        K.xl[s] = (lane * EPL + s) < P.n_elem ? P.damp_logr[0] * P.inv_rest_len : 0.0;
+        K.xl[s] = (lane * EPL + s) < P.n_elem ? (EM ? C.dlog0[s] : P.damp_logr[0]) * P.inv_rest_len : 0.0;
         K.hq_dt[s] = C.hq[s] * P.dt;
         if (EPL > 1) K.hq_dt[s] = opaque_v(K.hq_dt[s]);     // (or it is recomputed in the loop from a spilled dt)
         K.hq_hdt[s] = C.hq[s] * P.half_dt;
     }
-    K.jr = P.J[0] * P.rest_len;
+    K.jr = (EM ? C.j01[0] : P.J[0]) * P.rest_len;
     K.s3 = uniform_k<EPL>(-1.0 / 5040.0); K.s2 = opaque_v(1.0 / 120.0); K.s1 = uniform_k<EPL>(-1.0 / 6.0);
     K.c3 = uniform_k<EPL>(-1.0 / 720.0); K.c2 = opaque_v(1.0 / 24.0);
     K.e4 = uniform_k<EPL>(1.0 / 24.0); K.e3 = opaque_v(1.0 / 6.0);
     K.eps_length = EPL > 1 ? opaque_v(P.eps_length) : P.eps_length;
     K.rest_len = EPL > 1 ? opaque_v(P.rest_len) : P.rest_len;
-    K.damp_t = EPL > 1 ? opaque_v(P.damp_t) : P.damp_t;
+    const double damp_t = EM ? C.damp_t : P.damp_t;
+    K.damp_t = EPL > 1 ? opaque_v(damp_t) : damp_t;
     K.two_shift = EPL > 1 ? opaque_v(P.two_acos_shift) : P.two_acos_shift;
     if (EPL > 1) K.jr = opaque_v(K.jr);
 }

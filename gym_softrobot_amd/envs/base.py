@@ -53,6 +53,17 @@ except Exception:  # noqa: BLE001
             pass
 
 
+class SingleEnvMaterial:
+    """set_material / material of a single env (its one-env vec env `_vec`): VecRodEnvBase.set_material with N = 1."""
+
+    def set_material(self, *, youngs_modulus=None, shear_modulus=None, density=None, damping_constant=None):
+        self._vec.set_material(youngs_modulus=youngs_modulus, shear_modulus=shear_modulus, density=density,
+                               damping_constant=damping_constant)
+
+    def material(self) -> Dict[str, float]:
+        return {k: float(v[0]) for k, v in self._vec.material().items()}
+
+
 def time_table(cfg: _capi.SoftrodConfig, n_steps: int) -> np.ndarray:
     """float64 simulated time after k env.steps, accumulated exactly as
     `self.time = self.do_step(self.simulator, self.time, self.time_step)` does
@@ -412,6 +423,77 @@ class VecRodEnvBase:
         numpy_output=True)."""
         return self._out(self.backend.rod_energies())
 
+    # -- per-env material (domain randomisation) ----------------------------------------
+    _MATERIAL_KEYS = ("youngs_modulus", "shear_modulus", "density", "damping_constant")
+
+    def set_material(self, mask=None, *, youngs_modulus=None, shear_modulus=None, density=None,
+                     damping_constant=None):
+        """Give each env its own rod material: Young's modulus E, shear modulus G, density rho and the
+        AnalyticalLinearDamper's damping constant nu.  Upstream builds every env's rod with one
+        CosseratRod.straight_rod(density, youngs_modulus, shear_modulus) and has no counterpart; here a batch
+        can randomise them per env without leaving the GPU.
+
+        Each value is a scalar or an (N,) array (NumPy, or a CPU / device torch tensor); None keeps the current
+        value.  `youngs_modulus` without `shear_modulus` sets G = E / 3 (PyElastica's default at Poisson ratio
+        0.5, which the env builds use).  `mask` (N,) bool, or None for every env: only those envs change.  Values
+        must be finite, with E, G, rho > 0 and nu >= 0.
+
+        Material belongs to the env slot, not to the episode: it persists through host and device auto-resets.
+        To resample per episode, call set_material(mask=finished, ...) between two steps; under NEXT_STEP
+        auto-reset the restarted episode then runs with the new values from its first step.  Takes effect at
+        the next launch on the env's stream.  SoftPendulum, SoftPendulum3D and OctoArmSingle (uniform rods of up
+        to 63 elements) on the HIP backend only; elsewhere NotImplementedError."""
+        be = self.backend
+        if not hasattr(be, "set_env_material"):
+            raise NotImplementedError(f"per-env material needs the HIP backend, not {type(be).__name__}")
+        why = _capi.env_material_refusal(self.cfg, tapered="radius_profile" in getattr(be, "_tables", {}))
+        if why is not None:
+            raise NotImplementedError(why)
+        n = self.num_envs
+
+        def col(v, name):
+            if v is None:
+                return None
+            if hasattr(v, "detach"):
+                v = v.detach().cpu().numpy()
+            a = np.asarray(v, dtype=np.float64)
+            if a.ndim == 0:
+                a = np.full(n, float(a))
+            if a.shape != (n,):
+                raise ValueError(f"{name}: expected a scalar or shape ({n},), got {a.shape}")
+            return a
+
+        cols = [col(v, k) for v, k in zip((youngs_modulus, shear_modulus, density, damping_constant),
+                                          self._MATERIAL_KEYS)]
+        if cols[0] is not None and cols[1] is None:
+            cols[1] = cols[0] / 3.0
+        if mask is None:
+            sel = np.ones(n, bool)
+        else:
+            if hasattr(mask, "detach"):
+                mask = mask.detach().cpu().numpy()
+            sel = np.asarray(mask, dtype=bool).reshape(-1)
+            if sel.shape != (n,):
+                raise ValueError(f"mask: expected shape ({n},), got {sel.shape}")
+        m = be.env_material()
+        for j, c in enumerate(cols):
+            if c is not None:
+                m[sel, j] = c[sel]
+        rows = m[sel]
+        if not np.isfinite(rows).all():
+            raise ValueError("set_material: values must be finite")
+        if not ((rows[:, :3] > 0.0).all() and (rows[:, 3] >= 0.0).all()):
+            raise ValueError("set_material: E, G and density must be > 0, damping_constant >= 0")
+        be.set_env_material(m, sel.astype(np.uint8))
+
+    def material(self) -> Dict[str, np.ndarray]:
+        """Every env's rod material: youngs_modulus, shear_modulus, density, damping_constant as (N,) float64
+        arrays (the config's values until set_material)."""
+        be = self.backend
+        m = be.env_material() if hasattr(be, "env_material") else np.tile(_capi.env_material_defaults(self.cfg),
+                                                                          (self.num_envs, 1))
+        return {k: m[:, j].copy() for j, k in enumerate(self._MATERIAL_KEYS)}
+
     def capture_policy_step(self, policy):
         """One HIP graph for `actions = policy(obs); step(actions)` — the launch-bound tail of an on-device
         rollout (a small policy is half a dozen tiny kernels per step) becomes ONE graph launch per env.step.
@@ -425,7 +507,9 @@ class VecRodEnvBase:
         back every step and cannot live in a graph); the queue top-ups of the device mode stay outside the graph
         and run between replays.  Results are bit-identical to the eager loop (tests/test_gpu_policy_loop.py).
         The kernel arguments (RodParams, array pointers) are baked into the graph BY VALUE at capture: after
-        anything that changes them (a radius profile, an action basis, enabling auto-reset) capture again.
+        anything that changes them (a radius profile, an action basis, enabling auto-reset, enabling per-env material)
+        capture again.  Once per-env material is on, later set_material calls update its table in place: replays
+        issued on the env's stream see them.
         Kernel timing (set_timing) is switched off by the capture and stays off."""
         import torch
 

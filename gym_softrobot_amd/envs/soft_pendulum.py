@@ -23,7 +23,7 @@ from .. import _capi
 from ..seeding import initial_angle
 from ..spaces import Box
 from .base import GymEnv as _GymEnv
-from .base import VecRodEnvBase
+from .base import SingleEnvMaterial, VecRodEnvBase
 from .base import time_table as _time_table  # noqa: F401  (re-exported for tests)
 
 
@@ -81,7 +81,7 @@ class VecSoftPendulumEnv(VecRodEnvBase):
         self.backend.queue_push(th, counts)
 
 
-class SoftPendulumEnv(_GymEnv):
+class SoftPendulumEnv(SingleEnvMaterial, _GymEnv):
     """Drop-in for gym_softrobot's SoftPendulumEnv (soft_pendulum.py:45-322), N = 1.
 
     Same constructor keywords (soft_pendulum.py:59-67), spaces (:84-94), return

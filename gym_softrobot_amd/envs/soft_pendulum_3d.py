@@ -15,7 +15,7 @@ import numpy as np
 from .. import _capi
 from ..spaces import Box
 from .base import GymEnv as _GymEnv
-from .base import VecRodEnvBase
+from .base import SingleEnvMaterial, VecRodEnvBase
 
 
 def initial_tilt(rng: np.random.Generator) -> float:
@@ -99,7 +99,7 @@ class VecSoftPendulum3DEnv(VecRodEnvBase):
         return {"time": times, "tilt": self._out(self.backend.aux[:, 0])}
 
 
-class SoftPendulum3DEnv(_GymEnv):
+class SoftPendulum3DEnv(SingleEnvMaterial, _GymEnv):
     """Drop-in for gym_softrobot's SoftPendulum3DEnv (soft_pendulum_3d.py:20-174), N = 1."""
 
     metadata = {"render_modes": ["rgb_array"], "render_fps": 25}

@@ -658,6 +658,25 @@ int softrod_observe(softrod_handle* h, const float* prev_action, float* obs,
  *   shear          1/2 sum_e sigma_e . S_e sigma_e  l^_e           (rest sigma 0)  */
 int softrod_rod_energies(softrod_handle* h, double* out, void* stream);
 
+/* Per-env rod material, for domain randomisation of single-rod envs.  Upstream has no counterpart: there
+ * every env builds its rod with CosseratRod.straight_rod(..., density, youngs_modulus, shear_modulus) and
+ * AnalyticalLinearDamper(damping_constant, ...), and a batch of them shares one softrod_config.  This call
+ * gives env i its own (E, G, rho, nu):
+ *   material  host [n_envs][4] float64: youngs_modulus, shear_modulus, density, damping_constant;
+ *             each finite, E, G, rho > 0, nu >= 0 (checked for the rows that change)
+ *   mask      host [n_envs], or NULL for every env: only rows with mask[i] != 0 change.
+ * Each row holds what fill_params derives from the four values (J, 1/J, shear and bend stiffnesses, node and
+ * rod mass, the damper's factors), computed by fill_params itself on a copy of the config: a row set to the
+ * config's own values holds the kernel arguments' doubles bit for bit.  The first call allocates the table
+ * with every row at the config's values; the rest geometry, reset records and the auto-reset queue do not
+ * depend on it.  A row takes effect at the next launch on `stream` (step, reset, observe, device auto-reset,
+ * softrod_rod_energies).  A graph captured before the first call does not see the table (capture again);
+ * later calls update it in place.
+ * Scope: uniform rods of up to 63 elements of SOFTROD_ENV_SOFTPENDULUM, _SOFTPENDULUM3D and _ARM_SINGLE with
+ * their own feature sets, both math modes.  Anything else (tapered rods, the two-slot and windowed long rods,
+ * OctoFlat, the muscle envs, SoftArmTracking) -> SOFTROD_EINVAL, with the reason in softrod_last_error.   */
+int softrod_set_env_material(softrod_handle* h, const double* material, const uint8_t* mask, void* stream);
+
 /* Run `n` bare PositionVerlet substeps with fixed per-env forcing inputs and no
  * env epilogue (the inner loop of soft_pendulum.py:183-184 alone); `actions`
  * (device [n_envs] float32 or NULL) feeds SOFTROD_FEAT_POINT_FORCE_NODE0_X.
