@@ -756,6 +756,63 @@ def env_material_defaults(cfg: "SoftrodConfig") -> "np.ndarray":
     return np.array([cfg.youngs_modulus, cfg.shear_modulus, cfg.density, cfg.damping_constant], np.float64)
 
 
+def octo_waves_per_env(cfg: "SoftrodConfig") -> int:
+    """Wavefronts per OctoFlat env: n_arm arms of one power-of-two segment each (fill_params' seg), 64 lanes a wave."""
+    n = int(cfg.n_elem)
+    seg = 16 if n <= 15 else (32 if n <= 31 else 64)
+    return (int(cfg.n_arm) * seg + 63) // 64
+
+
+def env_contact_refusal(cfg: "SoftrodConfig", tapered: bool = False):
+    """Why softrod_set_env_contact would refuse a handle of `cfg` (None: it would not).  The same scope as the
+    C-ABI's check: OctoArmSingle (uniform rods of up to 63 elements) and OctoFlat / OctoFlatLite (at most two
+    waves per env), each with its own feature set on a contact plane with normal e_z."""
+    kind, feats = int(cfg.env_kind), int(cfg.features)
+    if kind in MUSCLE_OCTOPUS_ENVS or feats & FEAT_COOMM_MUSCLES:
+        return "per-env contact: not for the muscle envs"
+    if not ((kind == ENV_ARM_SINGLE and feats == FEATURES_ARM_SINGLE) or
+            (kind == ENV_OCTO_FLAT and feats == FEATURES_OCTO_FLAT)):
+        return "per-env contact: OctoArmSingle, OctoFlat and OctoFlatLite with their own feature sets only"
+    if tuple(cfg.plane_normal) != (0.0, 0.0, 1.0):
+        return "per-env contact: a contact plane with normal e_z only"
+    if int(cfg.early_termination):
+        return "per-env contact: not with early_termination"
+    if kind == ENV_OCTO_FLAT:
+        if octo_waves_per_env(cfg) > 2:
+            return "per-env contact: OctoFlat with at most two waves per env only (not the four- and eight-wave shapes)"
+        return None
+    if tapered:
+        return "per-env contact: not for a tapered rod"
+    if int(cfg.n_elem) > 63:
+        return "per-env contact: rods of up to 63 elements only"
+    return None
+
+
+def env_contact_defaults(cfg: "SoftrodConfig") -> "np.ndarray":
+    """(8,) float64: the config's own contact_k, contact_nu, kinetic_mu[3], static_mu[3] (forward, backward,
+    sideways)."""
+    import numpy as np
+
+    return np.array([cfg.contact_k, cfg.contact_nu, *cfg.kinetic_mu, *cfg.static_mu], np.float64)
+
+
+def friction_mu_arrays(cfg: "SoftrodConfig", friction_multiplier=1.0, friction_symmetry=False):
+    """(kinetic_mu_array, static_mu_array), each (3,) float64, as build_arm / build_octopus compute them from
+    override_params' friction_multiplier and friction_symmetry (octopus/build.py:178-190, 240-257) with the config's
+    base_length and gravity, in the same order of operations: a multiplier of 1 without symmetry gives the
+    config's own arrays bit for bit."""
+    import numpy as np
+
+    L0, g = float(cfg.base_length), float(cfg.gravity[2])
+    period, froude = 2.0, 0.1
+    mu = L0 / (period * period * np.abs(g) * froude)
+    if friction_symmetry:
+        kinetic = np.array([mu, mu, mu]) * friction_multiplier
+    else:
+        kinetic = np.array([mu, 1.5 * mu, 2.0 * mu]) * friction_multiplier
+    return kinetic, 2 * kinetic
+
+
 class SoftrodError(RuntimeError):
     pass
 
@@ -804,6 +861,7 @@ _EXPORTS = {
     "softrod_observe": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_rod_energies": (C.c_int, [_VP, _VP, _VP]),
     "softrod_set_env_material": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "softrod_set_env_contact": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_substeps": (C.c_int, [_VP, _VP, C.c_int, _VP]),
     "softrod_state_view_get": (C.c_int, [_VP, C.POINTER(SoftrodStateView)]),
     "softrod_set_timing": (C.c_int, [_VP, C.c_int]),

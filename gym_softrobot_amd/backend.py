@@ -141,6 +141,28 @@ class HipRodBackend:
             return np.tile(_capi.env_material_defaults(self.cfg), (self.n_envs, 1))
         return cur.copy()
 
+    def set_env_contact(self, contact, mask: Optional[np.ndarray] = None) -> None:
+        """softrod_set_env_contact: per-env (contact_k, contact_nu, kinetic_mu[3], static_mu[3]), host (n_envs, 8)
+        float64; only rows with mask != 0 change.  Takes effect at the next launch on the current stream; persists
+        through resets."""
+        why = _capi.env_contact_refusal(self.cfg, tapered="radius_profile" in self._tables)
+        if why is not None:
+            raise NotImplementedError(why)
+        c = np.ascontiguousarray(contact, dtype=np.float64).reshape(self.n_envs, 8)
+        k = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.n_envs)
+        check(self._lib.softrod_set_env_contact(self._h, c.ctypes.data, None if k is None else k.ctypes.data,
+                                                self._stream()), self._h)
+        cur = self.env_contact()
+        self._env_contact = np.where(k[:, None] != 0, c, cur) if k is not None else c.copy()
+
+    def env_contact(self) -> np.ndarray:
+        """(n_envs, 8) float64 host copy of every env's (k, nu, kinetic_mu[3], static_mu[3]): the config's until
+        set_env_contact."""
+        cur = getattr(self, "_env_contact", None)
+        if cur is None:
+            return np.tile(_capi.env_contact_defaults(self.cfg), (self.n_envs, 1))
+        return cur.copy()
+
     def reset(self, theta0: np.ndarray, mask: Optional[np.ndarray] = None) -> None:
         th = np.ascontiguousarray(theta0, dtype=np.float64).reshape(self.n_envs)
         m = None
@@ -463,6 +485,8 @@ class HipRodBackend:
         snap = {k: st[k].cpu().clone() for k in self._snapshot_keys()}
         if getattr(self, "_env_material", None) is not None:        # per-env material (set_env_material)
             snap["env_material"] = torch.from_numpy(self._env_material.copy())
+        if getattr(self, "_env_contact", None) is not None:         # per-env contact (set_env_contact)
+            snap["env_contact"] = torch.from_numpy(self._env_contact.copy())
         snap["config_fingerprint"] = torch.frombuffer(bytearray(self.config_fingerprint()), dtype=torch.uint8).clone()
         return snap
 
@@ -485,6 +509,11 @@ class HipRodBackend:
             self.set_env_material(snap["env_material"].numpy())
         elif getattr(self, "_env_material", None) is not None:
             self.set_env_material(np.tile(_capi.env_material_defaults(self.cfg), (self.n_envs, 1)))
+        # the same for per-env contact
+        if "env_contact" in snap:
+            self.set_env_contact(snap["env_contact"].numpy())
+        elif getattr(self, "_env_contact", None) is not None:
+            self.set_env_contact(np.tile(_capi.env_contact_defaults(self.cfg), (self.n_envs, 1)))
         torch.cuda.synchronize(self.device)
 
     def rod_snapshot(self, env_indices) -> Dict[str, np.ndarray]:

@@ -80,6 +80,10 @@ struct softrod_handle {
     EnvMaterial* d_env_mat = nullptr;  // [N]
     EnvMaterial* h_env_mat = nullptr;  // pinned [N]: every row as last uploaded (the staging buffer)
     hipEvent_t ev_env_mat = nullptr;   // guards reuse of h_env_mat
+    // per-env contact (softrod_set_env_contact): nullptr until the first call
+    EnvContact* d_env_contact = nullptr;  // [N]
+    EnvContact* h_env_contact = nullptr;  // pinned [N]: every row as last uploaded (the staging buffer)
+    hipEvent_t ev_env_contact = nullptr;  // guards reuse of h_env_contact
     std::string err;
 };
 
@@ -297,6 +301,42 @@ void env_material_row(const softrod_config& c, const double m[4], EnvMaterial& R
     R.mass_node = Q.mass_node; R.mass_total = Q.mass_total; R.damp_t = Q.damp_t;
 }
 
+// softrod_set_env_contact's scope: OctoArmSingle's uniform one-slot rod with its own feature set on an e_z plane (the
+// two kFeatEnvContact fast instantiations, with and without kFeatEnvMaterial; the LIBM kernel reads the table at run
+// time), and OctoFlat / OctoFlatLite on an e_z plane in the two-wave shapes (the two kFeatEnvContact octo
+// instantiations).  nullptr: in scope; else why not.
+const char* env_contact_refusal(const softrod_handle* h) {
+    const unsigned f = h->cfg.features;
+    const int e = h->cfg.env_kind;
+    const bool zup = (h->P.features & kFeatPlaneZup) != 0;
+    if (is_mocto(h) || is_pull(h) || (f & SOFTROD_FEAT_COOMM_MUSCLES)) return "per-env contact: not for the muscle envs";
+    if (!(f & SOFTROD_FEAT_PLANE_CONTACT_ANISO) || !((f == SOFTROD_FEATURES_ARM_SINGLE && e == SOFTROD_ENV_ARM_SINGLE) ||
+                                                    (f == SOFTROD_FEATURES_OCTO_FLAT && e == SOFTROD_ENV_OCTO_FLAT)))
+        return "per-env contact: OctoArmSingle, OctoFlat and OctoFlatLite with their own feature sets only";
+    if (!zup) return "per-env contact: a contact plane with normal e_z only";
+    if (h->cfg.early_termination) return "per-env contact: not with early_termination";
+    if (is_octo(h)) {
+        if (h->nw > 2)
+            return "per-env contact: OctoFlat with at most two waves per env only (n_arm x segment <= 128 lanes; "
+                   "not the four- and eight-wave shapes)";
+        return nullptr;
+    }
+    if (h->tapered) return "per-env contact: not for a tapered rod (softrod_set_radius_profile)";
+    if (h->epl != 1 || h->window_refresh > 0)
+        return "per-env contact: rods of up to 63 elements only (not the two-slot or windowed long rods)";
+    return nullptr;
+}
+// One row of the per-env contact table from (k, nu, kinetic_mu[3], static_mu[3]): the means and half differences with
+// contact_params()' operations, so that the config's own values give the kernels' doubles bit for bit.
+void env_contact_row(const double c[8], EnvContact& R) {
+    std::memset(&R, 0, sizeof(R));
+    R.k = c[0];
+    R.nu = c[1];
+    for (int i = 0; i < 3; ++i) { R.kin_mu[i] = c[2 + i]; R.stat_mu[i] = c[5 + i]; }
+    R.kin_am[0] = 0.5 * (R.kin_mu[0] + R.kin_mu[1]); R.kin_am[1] = 0.5 * (R.kin_mu[0] - R.kin_mu[1]);
+    R.stat_am[0] = 0.5 * (R.stat_mu[0] + R.stat_mu[1]); R.stat_am[1] = 0.5 * (R.stat_mu[0] - R.stat_mu[1]);
+}
+
 int launch_step(softrod_handle* h, const float* actions, float* obs, double* reward,
                 uint8_t* term, uint8_t* trunc, double* aux, int n_sub, int epilogue, int pack,
                 hipStream_t st) {
@@ -334,6 +374,9 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
     if (h->d_env_mat) {   // never let a kernel that ignores the per-env table step this handle
         if (const char* why = env_material_refusal(h)) return fail(h, SOFTROD_EINVAL, why);
     }
+    if (h->d_env_contact) {   // the same for the per-env contact table
+        if (const char* why = env_contact_refusal(h)) return fail(h, SOFTROD_EINVAL, why);
+    }
     const bool timing = h->timed < (int)h->ev_start.size();
     if (timing) SR_HIP(h, hipEventRecord(h->ev_start[h->timed], st));
     const bool zup = (h->P.features & kFeatPlaneZup) != 0;
@@ -357,7 +400,14 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
         hipLaunchKernelGGL((softrod_octo_step_kernel<FEATS, MAXW>), grid, block, 0, st, h->P, h->S,     \
                            actions, obs, reward, term, trunc, n_sub, epilogue, pack)
         // the reference shape (two waves per env): four envs per workgroup, partner waves on one SIMD
-        if (zup && h->nw == 2) {
+        if (h->d_env_contact) {   // per-env contact: the instantiations FOR it (env_contact_refusal: zup, nw <= 2)
+            if (h->nw == 2)
+                hipLaunchKernelGGL((softrod_octo_step_kernel<SOFTROD_FEATURES_OCTO_FLAT | kFeatPlaneZup | kFeatEnvContact, 2, 4>),
+                                   dim3((unsigned)((h->cfg.n_envs + 3) / 4)), dim3(kLanes * 8), 0, st, h->P, h->S,
+                                   actions, obs, reward, term, trunc, n_sub, epilogue, pack);
+            else
+                SR_OCTO(SOFTROD_FEATURES_OCTO_FLAT | kFeatPlaneZup | kFeatEnvContact, 2);
+        } else if (zup && h->nw == 2) {
             hipLaunchKernelGGL((softrod_octo_step_kernel<SOFTROD_FEATURES_OCTO_FLAT | kFeatPlaneZup, 2, 4>),
                                dim3((unsigned)((h->cfg.n_envs + 3) / 4)), dim3(kLanes * 8), 0, st, h->P, h->S,
                                actions, obs, reward, term, trunc, n_sub, epilogue, pack);
@@ -434,7 +484,14 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
                 SR_LAUNCH_TAPER(kRuntimeFeatures, kRuntimeEnv);
 #undef SR_LAUNCH_TAPER
         } else if (h->epl == 2) SR_DISPATCH(2);
-        else if (h->d_env_mat) {   // per-env material: the instantiations FOR it (kFeatEnvMaterial; env_material_refusal
+        else if (h->d_env_contact) {   // per-env contact (kFeatEnvContact; env_contact_refusal has admitted OctoArmSingle
+                                       // only here), with or without per-env material
+            if (h->d_env_mat)
+                SR_LAUNCH(SOFTROD_FEATURES_ARM_SINGLE | kFeatPlaneZup | kFeatEnvContact | kFeatEnvMaterial,
+                          SOFTROD_ENV_ARM_SINGLE, 1);
+            else
+                SR_LAUNCH(SOFTROD_FEATURES_ARM_SINGLE | kFeatPlaneZup | kFeatEnvContact, SOFTROD_ENV_ARM_SINGLE, 1);
+        } else if (h->d_env_mat) {   // per-env material: the instantiations FOR it (kFeatEnvMaterial; env_material_refusal
                                    // has admitted exactly these three)
             if (e == SOFTROD_ENV_SOFTPENDULUM)
                 SR_LAUNCH(SOFTROD_FEATURES_SOFTPENDULUM | kFeatEnvMaterial, SOFTROD_ENV_SOFTPENDULUM, 1);
@@ -1492,6 +1549,45 @@ int softrod_set_env_material(softrod_handle* h, const double* material, const ui
     return SOFTROD_OK;
 }
 
+int softrod_set_env_contact(softrod_handle* h, const double* contact, const uint8_t* mask, void* stream) {
+    if (!h || !contact) return fail(h, SOFTROD_EINVAL, "null argument");
+    if (const char* why = env_contact_refusal(h)) return fail(h, SOFTROD_EINVAL, why);
+    const size_t N = (size_t)h->cfg.n_envs;
+    for (size_t i = 0; i < N; ++i) {
+        if (mask && !mask[i]) continue;
+        const double* c = contact + 8 * i;
+        for (int j = 0; j < 8; ++j) {
+            if (!std::isfinite(c[j]))
+                return fail(h, SOFTROD_EINVAL, "per-env contact: env " + std::to_string(i) + " has a non-finite value");
+            if (!(c[j] >= 0.0))
+                return fail(h, SOFTROD_EINVAL, "per-env contact: env " + std::to_string(i) +
+                                                   " needs contact_k, contact_nu and every mu >= 0");
+        }
+    }
+    SR_ON_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (!h->d_env_contact) {   // every row starts at the config's own values
+        SR_HIP(h, hipMalloc((void**)&h->d_env_contact, N * sizeof(EnvContact)));
+        SR_HIP(h, hipHostMalloc((void**)&h->h_env_contact, N * sizeof(EnvContact), hipHostMallocDefault));
+        SR_HIP(h, hipEventCreateWithFlags(&h->ev_env_contact, hipEventDisableTiming));
+        const softrod_config& c = h->cfg;
+        const double c0[8] = {c.contact_k, c.contact_nu, c.kinetic_mu[0], c.kinetic_mu[1], c.kinetic_mu[2],
+                              c.static_mu[0], c.static_mu[1], c.static_mu[2]};
+        EnvContact R0;
+        env_contact_row(c0, R0);
+        for (size_t i = 0; i < N; ++i) h->h_env_contact[i] = R0;
+        h->S.env_contact = h->d_env_contact;
+        SR_HIP(h, hipMemcpy(h->d_state, &h->S, sizeof(StatePtrs), hipMemcpyHostToDevice));
+    } else {
+        SR_HIP(h, hipEventSynchronize(h->ev_env_contact));   // the previous upload has left the staging buffer
+    }
+    for (size_t i = 0; i < N; ++i)
+        if (!mask || mask[i]) env_contact_row(contact + 8 * i, h->h_env_contact[i]);
+    SR_HIP(h, hipMemcpyAsync(h->d_env_contact, h->h_env_contact, N * sizeof(EnvContact), hipMemcpyHostToDevice, st));
+    SR_HIP(h, hipEventRecord(h->ev_env_contact, st));
+    return SOFTROD_OK;
+}
+
 int softrod_set_muscle_layers(softrod_handle* h, const double* ratio_position, const double* strength) {
     if (!h || !ratio_position || !strength) return fail(h, SOFTROD_EINVAL, "null argument");
     if (!(h->cfg.features & SOFTROD_FEAT_COOMM_MUSCLES)) return fail(h, SOFTROD_EINVAL, "this handle has no COOMM muscles");
@@ -1850,6 +1946,7 @@ const char* softrod_kernel_tier(softrod_handle* h) {
     } else
         t = "softrod_step_libm_kernel";
     if (h->d_env_mat) t += ",env material";
+    if (h->d_env_contact) t += ",env contact";
     h->tier = t;
     return h->tier.c_str();
 }
@@ -1860,11 +1957,13 @@ int softrod_destroy(softrod_handle* h) {
     (void)hipDeviceSynchronize();
     autoreset_release(h);
     void* bufs[] = {h->S.pos, h->S.vel, h->S.dir, h->S.omg, h->S.tan, h->S.time, h->S.bc,
-                    h->S.ctrl, h->S.kap, h->S.rkap, h->S.envmem, h->S.prev_action, h->S.head, h->d_params, h->d_state, h->d_time_tab, h->d_mat, h->d_sucker, h->d_sucker_idx, h->d_aux, h->d_prev_kappa, h->d_mact, h->d_mtab, h->d_basis, h->d_spline, h->d_init, h->d_mask, h->d_ticket, h->d_env_mat};
+                    h->S.ctrl, h->S.kap, h->S.rkap, h->S.envmem, h->S.prev_action, h->S.head, h->d_params, h->d_state, h->d_time_tab, h->d_mat, h->d_sucker, h->d_sucker_idx, h->d_aux, h->d_prev_kappa, h->d_mact, h->d_mtab, h->d_basis, h->d_spline, h->d_init, h->d_mask, h->d_ticket, h->d_env_mat, h->d_env_contact};
     for (void* p : bufs) (void)hipFree(p);
     if (h->h_init) (void)hipHostFree(h->h_init);
     if (h->h_env_mat) (void)hipHostFree(h->h_env_mat);
     if (h->ev_env_mat) (void)hipEventDestroy(h->ev_env_mat);
+    if (h->h_env_contact) (void)hipHostFree(h->h_env_contact);
+    if (h->ev_env_contact) (void)hipEventDestroy(h->ev_env_contact);
     if (h->h_mask) (void)hipHostFree(h->h_mask);
     for (hipEvent_t e : h->ev_start) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->ev_stop) (void)hipEventDestroy(e);

@@ -318,7 +318,8 @@ struct NoConnections {
 // ---- forces, torques, rate update, dampers, constrain_rates -------------------------------------
 template <unsigned F, int EPL, bool TAPER = false, class Connections = NoConnections>
 __device__ __forceinline__ void dynamic_n(const RodParams& P, const ConstN<EPL>& C, const BcTargets& B,
-                                          int lane, LaneN<EPL>& L, Connections&& connect = Connections()) {
+                                          int lane, LaneN<EPL>& L, Connections&& connect = Connections(),
+                                          int es = 0) {   // es: the OctoFlat kernel's env slot (kFeatEnvContact)
     const int n = P.n_elem;
     // material constants from C (build_const_m): per lane for a tapered rod, the env's row for kFeatEnvMaterial
     constexpr bool MC = TAPER || kEnvMaterial<F>;
@@ -493,12 +494,18 @@ __device__ __forceinline__ void dynamic_n(const RodParams& P, const ConstN<EPL>&
                 Fg[s][c] = f[s][c] + C.gm[s][c];     // (a per-lane constant: no select, no scalar operand)
             }
         }
-        if constexpr (F != kRuntimeFeatures && (F & SOFTROD_FEAT_OCTO_HEAD) != 0 && (F & kFeatPlaneZup) != 0)
-            plane_contact_n<EPL, true, true, TAPER>(contact_params_lds(P), P, lane, C, L, xn, vn, len, Fg, tq, fc);
-        else if (has<F>(P, kFeatPlaneZup))
-            plane_contact_n<EPL, true, true, TAPER>(contact_params(P), P, lane, C, L, xn, vn, len, Fg, tq, fc);
+        // kFeatEnvContact: the env's row (OctoFlat: its slot's LDS table) in place of RodParams' k, nu and mu
+        if constexpr (F != kRuntimeFeatures && (F & SOFTROD_FEAT_OCTO_HEAD) != 0 && (F & kFeatPlaneZup) != 0) {
+            if constexpr (kEnvContact<F>)
+                plane_contact_n<EPL, true, true, TAPER>(contact_params_lds_env(P, es), P, lane, C, L, xn, vn, len, Fg, tq, fc);
+            else
+                plane_contact_n<EPL, true, true, TAPER>(contact_params_lds(P), P, lane, C, L, xn, vn, len, Fg, tq, fc);
+        } else if (has<F>(P, kFeatPlaneZup))
+            plane_contact_n<EPL, true, true, TAPER>(kEnvContact<F> ? contact_params_row(P, C.ct) : contact_params(P), P,
+                                                    lane, C, L, xn, vn, len, Fg, tq, fc);
         else
-            plane_contact_n<EPL, false, true, TAPER>(contact_params(P), P, lane, C, L, xn, vn, len, Fg, tq, fc);
+            plane_contact_n<EPL, false, true, TAPER>(kEnvContact<F> ? contact_params_row(P, C.ct) : contact_params(P), P,
+                                                     lane, C, L, xn, vn, len, Fg, tq, fc);
 #pragma unroll
         for (int s = 0; s < EPL; ++s)
 #pragma unroll
@@ -686,6 +693,7 @@ __device__ __attribute__((noinline)) void general_step_cold(const RodParams* __r
     ConstN<EPL> C;
     if constexpr (kEnvMaterial<F>) build_const_m<F, EPL>(P, S.env_mat[rod], lane, A, C);   // the env's row
     else build_const<F, EPL>(P, lane, A, C);
+    if constexpr (kEnvContact<F>) C.ct = S.env_contact[rod];
     RodParams Pk = P;
     if (!has<F>(P, SOFTROD_FEAT_ANALYTICAL_DAMPER)) Pk.damp_t = 1.0;
     general_substeps<F, EPL>(P, Pk, C, B, lane, L, n_sub);
@@ -755,6 +763,9 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
     // of RodParams' fields
     [[maybe_unused]] EnvMaterial M;
     if constexpr (kEnvMaterial<F>) M = S.env_mat[rod];
+    // kFeatEnvContact: this env's contact row, loaded the same way; plane_contact_n takes it in place of RodParams'
+    [[maybe_unused]] EnvContact CT;
+    if constexpr (kEnvContact<F>) CT = S.env_contact[rod];
     if (epilogue && S.skip && S.skip[rod]) {   // reset by the auto-reset pass of this env.step
         if (lane == 0) S.skip[rod] = 0;
         if (lane == 0 && early_term_on<F>(P)) S.aux[rod] = 0.0;   // no time limit on a restart
@@ -787,6 +798,7 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
     ConstN<EPL> C;
     if constexpr (kEnvMaterial<F>) build_const_m<F, EPL, TAPER>(P, M, lane, A, C, S.mat);
     else build_const_m<F, EPL, TAPER>(P, P, lane, A, C, S.mat);
+    if constexpr (kEnvContact<F>) C.ct = CT;
     if constexpr (kMusclesCompiled<F>) build_muscle_const<F, EPL, true>(P, S, N, rod, lane, A, C);
     RodParams Pk = P;
     if (!has<F>(P, SOFTROD_FEAT_ANALYTICAL_DAMPER)) Pk.damp_t = 1.0;

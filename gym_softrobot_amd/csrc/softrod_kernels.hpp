@@ -67,6 +67,13 @@ constexpr unsigned kFeatEarlyTerm = 1u << 29;
 constexpr unsigned kFeatEnvMaterial = 1u << 28;
 template <unsigned F>
 constexpr bool kEnvMaterial = F != kRuntimeFeatures && (F & kFeatEnvMaterial) != 0;
+// Internal pseudo-feature: the handle has a per-env contact table (softrod_set_env_contact, StatePtrs.env_contact).  Only
+// in the template mask of the instantiations FOR it: the one-rod fast kernel loads its env's row once per launch, the
+// OctoFlat kernel stages one LDS table per env slot; launch_step refuses a handle with the table any other fast kernel.
+// The LIBM step reads the table at run time when StatePtrs.env_contact is set; no other kernel reads contact.
+constexpr unsigned kFeatEnvContact = 1u << 27;
+template <unsigned F>
+constexpr bool kEnvContact = F != kRuntimeFeatures && (F & kFeatEnvContact) != 0;
 constexpr int kRuntimeEnv = -1;
 // The fast kernel carries the COOMM muscle layers (softrod_muscle.hpp) in the instantiations compiled FOR a feature
 // set that has them: OctoArmPush (SOFTROD_FEATURES_ARM_PUSH) and the clamped / free muscle rod of the known-answer
@@ -141,6 +148,19 @@ struct EnvMaterial {
 };
 static_assert(sizeof(EnvMaterial) == 192, "EnvMaterial: three 64-byte lines");
 
+// One env's row of the per-env contact table (softrod_set_env_contact): what ContactParams takes from the config's
+// contact_k, contact_nu, kinetic_mu and static_mu.  The host fills kin_am / stat_am with contact_params()' operations;
+// only the OctoFlat kernel's LDS staging reads them.  The one-rod fast kernel and the LIBM kernel read k, nu and the
+// mu arrays and form the means / half differences themselves (contact_params_row: the same doubles).  16 doubles:
+// two 64-byte lines.
+struct EnvContact {
+    double k, nu;
+    double kin_am[2], stat_am[2];   // (forward + backward) / 2, (forward - backward) / 2
+    double kin_mu[3], stat_mu[3];   // forward, backward, sideways
+    double pad[4];
+};
+static_assert(sizeof(EnvContact) == 128, "EnvContact: two 64-byte lines");
+
 struct StatePtrs {
     double* pos;   // [3][N][64]
     double* vel;   // [3][N][64]
@@ -179,6 +199,7 @@ struct StatePtrs {
     double* aux;            // [8][N] target x, y, z; the head's x, y before the step
     float* prev_kappa;      // [N][n_arm * (n_elem - 1)] ArmTwoEnv._prev_kappa
     const EnvMaterial* env_mat;   // [N] per-env material rows (softrod_set_env_material), or nullptr (RodParams)
+    const EnvContact* env_contact;   // [N] per-env contact rows (softrod_set_env_contact), or nullptr (RodParams)
 };
 
 // ---------------------------------------------------------------------------------
@@ -276,6 +297,8 @@ struct ConstN {
     const double* mact_lane;
     // wave-uniform: the damper's exp(-nu dt) (1 without the damper) and the rod's mass, from build_const's material source
     double damp_t, mass_total;
+    // kFeatEnvContact instantiations and the LIBM kernel only (dead otherwise): the env's contact row
+    EnvContact ct;
 };
 
 // value of index+1 / index-1 for a per-slot array
@@ -719,6 +742,43 @@ __device__ __forceinline__ ContactParams contact_params_lds_impl(const RodParams
 __device__ __forceinline__ void stage_contact_params(const RodParams& P) { (void)contact_params_lds_impl(P, true); }
 __device__ __forceinline__ ContactParams contact_params_lds(const RodParams& P) { return contact_params_lds_impl(P, false); }
 
+// kFeatEnvContact (the OctoFlat kernel): the same table once per env slot of the workgroup (four at most; one env
+// per workgroup uses slot 0), staged by one thread per slot from its env's row of the per-env contact table.  A
+// function of its own, so that the instantiations without the bit keep the one-table array above.
+__device__ __forceinline__ ContactParams contact_params_lds_env_impl(const RodParams& P, const EnvContact* row, int es,
+                                                                     const bool stage) {
+    __shared__ double c_[4][16];
+    double* c = c_[es];
+    ContactParams C;
+    if (stage) {
+        if (row) {
+            c[0] = row->k; c[1] = row->nu; c[2] = P.slip_tol; c[3] = P.surface_tol;
+            c[4] = row->kin_am[0]; c[5] = row->kin_am[1]; c[6] = row->kin_mu[2];
+            c[7] = row->stat_am[0]; c[8] = row->stat_am[1]; c[9] = row->stat_mu[2];
+            c[10] = P.r0_sqrt_rest_len; c[11] = 1.0 / P.r0_sqrt_rest_len; c[12] = P.plane_origin[2];
+        }
+        return C;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        C.origin[i] = P.plane_origin[i]; C.normal[i] = P.plane_normal[i];
+        C.kin_mu[i] = c[4 + i]; C.stat_mu[i] = c[7 + i];     // ([0], [1]: see kin_am / stat_am; only [2] is read)
+    }
+    C.kin_am[0] = c[4]; C.kin_am[1] = c[5]; C.stat_am[0] = c[7]; C.stat_am[1] = c[8];
+    C.origin[2] = c[12];
+    C.k = c[0]; C.nu = c[1]; C.slip_tol = c[2]; C.surface_tol = c[3];
+    C.r0_sqrt_rest_len = c[10];
+    C.inv_r0_sqrt_rest_len = c[11];
+    return C;
+}
+// `row`: the env's row for the thread that stages slot `es`, nullptr for every other thread
+__device__ __forceinline__ void stage_contact_params_env(const RodParams& P, const EnvContact* row, int es) {
+    (void)contact_params_lds_env_impl(P, row, es, true);
+}
+__device__ __forceinline__ ContactParams contact_params_lds_env(const RodParams& P, int es) {
+    return contact_params_lds_env_impl(P, nullptr, es, false);
+}
+
 __device__ __forceinline__ ContactParams contact_params(const RodParams& P) {
     ContactParams C;
 #pragma unroll
@@ -732,6 +792,31 @@ __device__ __forceinline__ ContactParams contact_params(const RodParams& P) {
     C.kin_am[0] = 0.5 * (P.kin_mu[0] + P.kin_mu[1]); C.kin_am[1] = 0.5 * (P.kin_mu[0] - P.kin_mu[1]);
     C.stat_am[0] = 0.5 * (P.stat_mu[0] + P.stat_mu[1]); C.stat_am[1] = 0.5 * (P.stat_mu[0] - P.stat_mu[1]);
     return C;
+}
+// contact_params with the env's row of the per-env contact table in place of RodParams' k, nu and mu
+__device__ __forceinline__ ContactParams contact_params_row(const RodParams& P, const EnvContact& R) {
+    ContactParams C = contact_params(P);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { C.kin_mu[i] = R.kin_mu[i]; C.stat_mu[i] = R.stat_mu[i]; }
+    C.k = R.k; C.nu = R.nu;
+    // the means and half differences again from forward / backward, as contact_params() forms them (the row's
+    // copies are the same doubles): read from the row they changed the one-rod kernel's register allocation
+    // (256 VGPRs against its uniform twin's 255, two more register copies in the loop)
+    C.kin_am[0] = 0.5 * (R.kin_mu[0] + R.kin_mu[1]); C.kin_am[1] = 0.5 * (R.kin_mu[0] - R.kin_mu[1]);
+    C.stat_am[0] = 0.5 * (R.stat_mu[0] + R.stat_mu[1]); C.stat_am[1] = 0.5 * (R.stat_mu[0] - R.stat_mu[1]);
+    return C;
+}
+// The contact source of the LIBM kernel (run-time features): env `rod`'s row when the handle has the per-env table
+// (softrod_set_env_contact), else RodParams' values with contact_params()' operations.
+__device__ __forceinline__ EnvContact env_contact_rt(const RodParams& P, const StatePtrs& S, int rod) {
+    if (S.env_contact) return S.env_contact[rod];
+    EnvContact R{};
+    R.k = P.contact_k; R.nu = P.contact_nu;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { R.kin_mu[i] = P.kin_mu[i]; R.stat_mu[i] = P.stat_mu[i]; }
+    R.kin_am[0] = 0.5 * (P.kin_mu[0] + P.kin_mu[1]); R.kin_am[1] = 0.5 * (P.kin_mu[0] - P.kin_mu[1]);
+    R.stat_am[0] = 0.5 * (P.stat_mu[0] + P.stat_mu[1]); R.stat_am[1] = 0.5 * (P.stat_mu[0] - P.stat_mu[1]);
+    return R;
 }
 
 // ---------------------------------------------------------------------------------
@@ -1741,7 +1826,7 @@ __device__ __forceinline__ void libm_dynamic_step(const RodParams& P, const Libm
     const double mass_next = M.mass_next;
     const double xn[1][3] = {{xn0, xn1, xn2}}, vn[1][3] = {{vn0, vn1, vn2}};
     ConstN<1> CK;
-    ContactParams CP = contact_params(P);
+    ContactParams CP = contact_params_row(P, CM.ct);     // RodParams' values or the env's row (env_contact_rt)
     CP.r0_sqrt_rest_len = M.r0s;
     CP.inv_r0_sqrt_rest_len = 1.0 / M.r0s;
     CK.mass[0] = mass;
@@ -1849,6 +1934,7 @@ softrod_step_libm_kernel(const RodParams P, const StatePtrs S, const float* __re
     if (S.mat) build_const_m<kRuntimeFeatures, 1, true>(P, E, lane, A, C, S.mat);
     else build_const_m<kRuntimeFeatures, 1>(P, E, lane, A, C);
     build_muscle_const<kRuntimeFeatures, 1, false>(P, S, N, rod, lane, A, C);
+    C.ct = env_contact_rt(P, S, rod);
     LibmMat M;
     libm_material(P, E, S.mat, lane, M);
 

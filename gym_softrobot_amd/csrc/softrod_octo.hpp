@@ -232,7 +232,9 @@ softrod_octo_step_kernel(const RodParams P, const StatePtrs S, const float* __re
     const int n = P.n_elem, nk = P.n_action;
     const int r = tid & (P.seg - 1), arm = tid >> P.seg_shift;
     const bool arm_ok = arm < P.n_arm;
-    if constexpr ((F & kFeatPlaneZup) != 0) stage_contact_params(P);   // (barriers follow)
+    if constexpr (kEnvContact<F>)      // one table per env slot, staged by the slot's first thread (barriers follow)
+        stage_contact_params_env(P, tid == 0 ? S.env_contact + env : nullptr, es);
+    else if constexpr ((F & kFeatPlaneZup) != 0) stage_contact_params(P);   // (barriers follow)
     if (tid < 2 * MAXW * 4) (&xch[0][0][0])[tid] = 0.0;   // rows of absent waves read as zero loads
     if constexpr (EPB == 1) __syncthreads();     // the staged tables are there before any wave reads them (EPB > 1: below)
     if (EPB > 1 && tid < 2 * MAXW) (&flag_[es][0][0])[tid] = 0;
@@ -504,7 +506,7 @@ softrod_octo_step_kernel(const RodParams P, const StatePtrs S, const float* __re
         head_step();
         for (int s = 0; s < n_sub; ++s) {
             if constexpr (EPB > 1) __builtin_amdgcn_s_setprio(1);
-            dynamic_n<F, 1, kMusclesCompiled<F>>(Pk, C, B, tid, L, joints);
+            dynamic_n<F, 1, kMusclesCompiled<F>>(Pk, C, B, tid, L, joints, es);
             const bool last = (s == n_sub - 1);
             const double h = last ? P.half_dt : P.dt;
             kinematic_n<1>(h, C, L);

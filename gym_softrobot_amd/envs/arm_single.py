@@ -18,7 +18,7 @@ import numpy as np
 from .. import _capi
 from ..spaces import Box
 from .base import GymEnv as _GymEnv
-from .base import SingleEnvMaterial, VecRodEnvBase
+from .base import SingleEnvContact, SingleEnvMaterial, VecRodEnvBase
 
 
 class VecArmSingleEnv(VecRodEnvBase):
@@ -90,7 +90,7 @@ class VecArmSingleEnv(VecRodEnvBase):
         self.backend.reset_straight(start, direction, normal, mask.astype(np.uint8) if use_mask else None)
 
 
-class ArmSingleEnv(SingleEnvMaterial, _GymEnv):
+class ArmSingleEnv(SingleEnvMaterial, SingleEnvContact, _GymEnv):
     """Drop-in for gym_softrobot's ArmSingleEnv (octopus/arm_single_env.py:41-316), N = 1."""
 
     metadata = {"render_modes": ["rgb_array", "human"], "render_fps": 20}

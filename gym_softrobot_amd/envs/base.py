@@ -64,6 +64,20 @@ class SingleEnvMaterial:
         return {k: float(v[0]) for k, v in self._vec.material().items()}
 
 
+class SingleEnvContact:
+    """set_contact / contact of a single env (its one-env vec env `_vec`): VecRodEnvBase.set_contact with N = 1."""
+
+    def set_contact(self, *, contact_k=None, contact_nu=None, kinetic_mu=None, static_mu=None,
+                    friction_multiplier=None, friction_symmetry=None):
+        self._vec.set_contact(contact_k=contact_k, contact_nu=contact_nu, kinetic_mu=kinetic_mu, static_mu=static_mu,
+                              friction_multiplier=friction_multiplier, friction_symmetry=friction_symmetry)
+
+    def contact(self) -> Dict[str, Any]:
+        c = self._vec.contact()
+        return {"contact_k": float(c["contact_k"][0]), "contact_nu": float(c["contact_nu"][0]),
+                "kinetic_mu": c["kinetic_mu"][0].copy(), "static_mu": c["static_mu"][0].copy()}
+
+
 def time_table(cfg: _capi.SoftrodConfig, n_steps: int) -> np.ndarray:
     """float64 simulated time after k env.steps, accumulated exactly as
     `self.time = self.do_step(self.simulator, self.time, self.time_step)` does
@@ -494,6 +508,109 @@ class VecRodEnvBase:
                                                                           (self.num_envs, 1))
         return {k: m[:, j].copy() for j, k in enumerate(self._MATERIAL_KEYS)}
 
+    # -- per-env ground contact and friction (domain randomisation) ---------------------
+    def set_contact(self, mask=None, *, contact_k=None, contact_nu=None, kinetic_mu=None, static_mu=None,
+                    friction_multiplier=None, friction_symmetry=None):
+        """Give each env its own ground: the contact stiffness k and damping nu and the kinetic / static friction
+        coefficients (forward, backward, sideways) of RodPlaneContactWithAnisotropicFriction
+        (octopus/build.py:236-283).  Upstream builds every env with one set; here a batch can randomise them per
+        env without leaving the GPU.
+
+        `contact_k`, `contact_nu`: a scalar or an (N,) array.  `kinetic_mu`, `static_mu`: a scalar, a (3,) or an
+        (N, 3) array.  NumPy or a CPU / device torch tensor; None keeps the current value.  `kinetic_mu` without
+        `static_mu` sets static = 2 * kinetic (upstream's static_mu_array = 2 * kinetic_mu_array).
+        `friction_multiplier` (scalar or (N,)) and `friction_symmetry` (bool or (N,) bool) are upstream's
+        override_params knobs (build.py:30-44,178-190): both mu arrays are recomputed as build_arm / build_octopus
+        do, mu = L0 / (period^2 |g| froude), [mu, mu, mu] or [mu, 1.5 mu, 2 mu] times the multiplier, static twice
+        kinetic (a multiplier of 1 without symmetry gives the config's arrays bit for bit); given either, the
+        other defaults to 1 / False, and explicit `kinetic_mu` / `static_mu` are a ValueError.  `mask` (N,) bool,
+        or None for every env: only those envs change.  Values must be finite and >= 0.
+
+        Contact belongs to the env slot, not to the episode: it persists through host and device auto-resets and
+        is carried by state_dict().  Takes effect at the next launch on the env's stream.  OctoArmSingle (uniform
+        rods of up to 63 elements, both math modes), OctoFlat and OctoFlatLite on the HIP backend only;
+        elsewhere NotImplementedError."""
+        be = self.backend
+        if not hasattr(be, "set_env_contact"):
+            raise NotImplementedError(f"per-env contact needs the HIP backend, not {type(be).__name__}")
+        why = _capi.env_contact_refusal(self.cfg, tapered="radius_profile" in getattr(be, "_tables", {}))
+        if why is not None:
+            raise NotImplementedError(why)
+        n = self.num_envs
+
+        def arr(v):
+            if hasattr(v, "detach"):
+                v = v.detach().cpu().numpy()
+            return np.asarray(v)
+
+        def col(v, name):
+            if v is None:
+                return None
+            a = arr(v).astype(np.float64)
+            if a.ndim == 0:
+                a = np.full(n, float(a))
+            if a.shape != (n,):
+                raise ValueError(f"{name}: expected a scalar or shape ({n},), got {a.shape}")
+            return a
+
+        def mu3(v, name):
+            if v is None:
+                return None
+            a = arr(v).astype(np.float64)
+            if a.ndim == 0:
+                a = np.full((n, 3), float(a))
+            elif a.shape == (3,):
+                a = np.tile(a, (n, 1))
+            if a.shape != (n, 3):
+                raise ValueError(f"{name}: expected a scalar, shape (3,) or ({n}, 3), got {a.shape}")
+            return a
+
+        k, nu = col(contact_k, "contact_k"), col(contact_nu, "contact_nu")
+        kin, stat = mu3(kinetic_mu, "kinetic_mu"), mu3(static_mu, "static_mu")
+        if friction_multiplier is not None or friction_symmetry is not None:
+            if kin is not None or stat is not None:
+                raise ValueError("friction_multiplier / friction_symmetry recompute both mu arrays: "
+                                 "not together with kinetic_mu / static_mu")
+            mult = col(1.0 if friction_multiplier is None else friction_multiplier, "friction_multiplier")
+            sym = arr(False if friction_symmetry is None else friction_symmetry)
+            if sym.dtype.kind not in "bui":
+                raise ValueError(f"friction_symmetry: expected a bool or ({n},) bools, got dtype {sym.dtype}")
+            sym = np.broadcast_to(sym.astype(bool), (n,)) if sym.ndim == 0 else sym.astype(bool)
+            if sym.shape != (n,):
+                raise ValueError(f"friction_symmetry: expected a bool or shape ({n},), got {sym.shape}")
+            kin, stat = np.empty((n, 3)), np.empty((n, 3))
+            for i in range(n):
+                kin[i], stat[i] = _capi.friction_mu_arrays(self.cfg, float(mult[i]), bool(sym[i]))
+        elif kin is not None and stat is None:
+            stat = 2 * kin
+        if mask is None:
+            sel = np.ones(n, bool)
+        else:
+            if hasattr(mask, "detach"):
+                mask = mask.detach().cpu().numpy()
+            sel = np.asarray(mask, dtype=bool).reshape(-1)
+            if sel.shape != (n,):
+                raise ValueError(f"mask: expected shape ({n},), got {sel.shape}")
+        c = be.env_contact()
+        for sl, v in ((slice(0, 1), k), (slice(1, 2), nu), (slice(2, 5), kin), (slice(5, 8), stat)):
+            if v is not None:
+                c[sel, sl] = v[sel].reshape(-1, sl.stop - sl.start)
+        rows = c[sel]
+        if not np.isfinite(rows).all():
+            raise ValueError("set_contact: values must be finite")
+        if not (rows >= 0.0).all():
+            raise ValueError("set_contact: contact_k, contact_nu and every mu must be >= 0")
+        be.set_env_contact(c, sel.astype(np.uint8))
+
+    def contact(self) -> Dict[str, np.ndarray]:
+        """Every env's ground: contact_k, contact_nu as (N,) and kinetic_mu, static_mu as (N, 3) float64 arrays
+        (forward, backward, sideways; the config's values until set_contact)."""
+        be = self.backend
+        c = be.env_contact() if hasattr(be, "env_contact") else np.tile(_capi.env_contact_defaults(self.cfg),
+                                                                        (self.num_envs, 1))
+        return {"contact_k": c[:, 0].copy(), "contact_nu": c[:, 1].copy(), "kinetic_mu": c[:, 2:5].copy(),
+                "static_mu": c[:, 5:8].copy()}
+
     def capture_policy_step(self, policy):
         """One HIP graph for `actions = policy(obs); step(actions)` — the launch-bound tail of an on-device
         rollout (a small policy is half a dozen tiny kernels per step) becomes ONE graph launch per env.step.
@@ -507,9 +624,9 @@ class VecRodEnvBase:
         back every step and cannot live in a graph); the queue top-ups of the device mode stay outside the graph
         and run between replays.  Results are bit-identical to the eager loop (tests/test_gpu_policy_loop.py).
         The kernel arguments (RodParams, array pointers) are baked into the graph BY VALUE at capture: after
-        anything that changes them (a radius profile, an action basis, enabling auto-reset, enabling per-env material)
+        anything that changes them (a radius profile, an action basis, enabling auto-reset, enabling per-env material or contact)
         capture again.  Once per-env material is on, later set_material calls update its table in place: replays
-        issued on the env's stream see them.
+        issued on the env's stream see them.  The same holds for per-env contact (set_contact).
         Kernel timing (set_timing) is switched off by the capture and stays off."""
         import torch
 

@@ -18,7 +18,7 @@ import numpy as np
 from .. import _capi
 from ..spaces import Box, Dict
 from .base import GymEnv as _GymEnv
-from .base import VecRodEnvBase
+from .base import SingleEnvContact, VecRodEnvBase
 
 
 class VecOctoFlatEnv(VecRodEnvBase):
@@ -107,7 +107,7 @@ class VecOctoFlatEnv(VecRodEnvBase):
         return {"individual": ind, "shared": obs[:, na * w:]}
 
 
-class FlatEnv(_GymEnv):
+class FlatEnv(SingleEnvContact, _GymEnv):
     """Drop-in for gym_softrobot's FlatEnv (octopus/flat_env.py:40-408), N = 1."""
 
     metadata = {"render_modes": ["rgb_array", "human"], "render_fps": 5}

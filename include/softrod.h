@@ -677,6 +677,30 @@ int softrod_rod_energies(softrod_handle* h, double* out, void* stream);
  * OctoFlat, the muscle envs, SoftArmTracking) -> SOFTROD_EINVAL, with the reason in softrod_last_error.   */
 int softrod_set_env_material(softrod_handle* h, const double* material, const uint8_t* mask, void* stream);
 
+/* Per-env ground contact and friction, for domain randomisation of the contact envs.  Upstream registers
+ * RodPlaneContactWithAnisotropicFriction(k, nu, slip_velocity_tol, static_mu_array, kinetic_mu_array) once per
+ * build (octopus/build.py:236-283 for build_arm, the same block in build_octopus), with k = 1e2, nu = 1e1 marked
+ * "These need to be global parameter to tune", and the mu arrays from override_params' friction_multiplier and
+ * friction_symmetry (build.py:30-44,178-190); a batch of them shares one softrod_config.  This call gives env i
+ * its own contact law inputs:
+ *   contact   host [n_envs][8] float64: contact_k, contact_nu, kinetic_mu[3], static_mu[3] (each mu array
+ *             forward, backward, sideways, as in softrod_config); each finite and >= 0 (checked for the rows
+ *             that change)
+ *   mask      host [n_envs], or NULL for every env: only rows with mask[i] != 0 change.
+ * The first call allocates the table with every row at the config's values (a row set to them gives the kernel
+ * arguments' doubles bit for bit); slip_velocity_tol, the plane and the rest of the config stay shared.  A row
+ * takes effect at the next launch of the step on `stream` (reset, observe, auto-reset and the energies do not
+ * read contact).  A graph captured before the first call does not see the table (capture again); later calls
+ * update it in place.  A handle may carry this table and softrod_set_env_material's.
+ * Scope: SOFTROD_ENV_ARM_SINGLE with its own feature set on a plane with normal e_z, uniform rods of up to 63
+ * elements, both math modes; SOFTROD_ENV_OCTO_FLAT (OctoFlat, OctoFlatLite) on an e_z plane with at most two
+ * waves per env, i.e. n_arm x segment <= 128 lanes (OctoFlat-v0: four envs per workgroup; OctoFlatLite-v0: one).
+ * Anything else (tapered arms, the long and windowed arms, the muscle envs, other planes, envs without contact,
+ * OctoFlat's four- and eight-wave shapes, and a handle with early_termination set, in either math mode: the
+ * fast kernels that evaluate it do not carry the table, and the scope stays one for both modes) ->
+ * SOFTROD_EINVAL with "per-env contact" in softrod_last_error.  */
+int softrod_set_env_contact(softrod_handle* h, const double* contact, const uint8_t* mask, void* stream);
+
 /* Run `n` bare PositionVerlet substeps with fixed per-env forcing inputs and no
  * env epilogue (the inner loop of soft_pendulum.py:183-184 alone); `actions`
  * (device [n_envs] float32 or NULL) feeds SOFTROD_FEAT_POINT_FORCE_NODE0_X.
