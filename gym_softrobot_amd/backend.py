@@ -27,6 +27,26 @@ class _DevArray:
         }
 
 
+def _set_env_table(self, name: str, width: int, values, mask) -> None:
+    """HipRodBackend.set_env_<name>: one per-env table (softrod_set_env_<name>): refusal, upload, and the host copy."""
+    why = getattr(_capi, f"env_{name}_refusal")(self.cfg, tapered="radius_profile" in self._tables)
+    if why is not None:
+        raise NotImplementedError(why)
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(self.n_envs, width)
+    k = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.n_envs)
+    check(getattr(self._lib, f"softrod_set_env_{name}")(self._h, v.ctypes.data, None if k is None else k.ctypes.data,
+                                                        self._stream()), self._h)
+    cur = _env_table(self, name)
+    setattr(self, f"_env_{name}", np.where(k[:, None] != 0, v, cur) if k is not None else v.copy())
+
+def _env_table(self, name: str) -> np.ndarray:
+    """HipRodBackend.env_<name>() (a function of the backend, so that a stand-in backend can borrow the method)."""
+    cur = getattr(self, f"_env_{name}", None)
+    if cur is None:
+        return np.tile(getattr(_capi, f"env_{name}_defaults")(self.cfg), (self.n_envs, 1))
+    return cur.copy()
+
+
 class HipRodBackend:
     """Resident batch of rods on one MI355X."""
 
@@ -124,44 +144,22 @@ class HipRodBackend:
     def set_env_material(self, material, mask: Optional[np.ndarray] = None) -> None:
         """softrod_set_env_material: per-env (E, G, rho, nu), host (n_envs, 4) float64; only rows with mask != 0
         change.  Takes effect at the next launch on the current stream; persists through resets."""
-        why = _capi.env_material_refusal(self.cfg, tapered="radius_profile" in self._tables)
-        if why is not None:
-            raise NotImplementedError(why)
-        m = np.ascontiguousarray(material, dtype=np.float64).reshape(self.n_envs, 4)
-        k = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.n_envs)
-        check(self._lib.softrod_set_env_material(self._h, m.ctypes.data, None if k is None else k.ctypes.data,
-                                                 self._stream()), self._h)
-        cur = self.env_material()
-        self._env_material = np.where(k[:, None] != 0, m, cur) if k is not None else m.copy()
+        _set_env_table(self, "material", 4, material, mask)
 
     def env_material(self) -> np.ndarray:
         """(n_envs, 4) float64 host copy of every env's (E, G, rho, nu): the config's until set_env_material."""
-        cur = getattr(self, "_env_material", None)
-        if cur is None:
-            return np.tile(_capi.env_material_defaults(self.cfg), (self.n_envs, 1))
-        return cur.copy()
+        return _env_table(self, "material")
 
     def set_env_contact(self, contact, mask: Optional[np.ndarray] = None) -> None:
         """softrod_set_env_contact: per-env (contact_k, contact_nu, kinetic_mu[3], static_mu[3]), host (n_envs, 8)
         float64; only rows with mask != 0 change.  Takes effect at the next launch on the current stream; persists
         through resets."""
-        why = _capi.env_contact_refusal(self.cfg, tapered="radius_profile" in self._tables)
-        if why is not None:
-            raise NotImplementedError(why)
-        c = np.ascontiguousarray(contact, dtype=np.float64).reshape(self.n_envs, 8)
-        k = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.n_envs)
-        check(self._lib.softrod_set_env_contact(self._h, c.ctypes.data, None if k is None else k.ctypes.data,
-                                                self._stream()), self._h)
-        cur = self.env_contact()
-        self._env_contact = np.where(k[:, None] != 0, c, cur) if k is not None else c.copy()
+        _set_env_table(self, "contact", 8, contact, mask)
 
     def env_contact(self) -> np.ndarray:
         """(n_envs, 8) float64 host copy of every env's (k, nu, kinetic_mu[3], static_mu[3]): the config's until
         set_env_contact."""
-        cur = getattr(self, "_env_contact", None)
-        if cur is None:
-            return np.tile(_capi.env_contact_defaults(self.cfg), (self.n_envs, 1))
-        return cur.copy()
+        return _env_table(self, "contact")
 
     def reset(self, theta0: np.ndarray, mask: Optional[np.ndarray] = None) -> None:
         th = np.ascontiguousarray(theta0, dtype=np.float64).reshape(self.n_envs)

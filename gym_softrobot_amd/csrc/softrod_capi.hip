@@ -19,6 +19,19 @@
 
 using namespace softrod;
 
+// One per-env table (set_env_table): nullptr until the first call
+template <class Row>
+struct EnvTable {
+    Row* dev = nullptr;        // [N]
+    Row* host = nullptr;       // pinned [N]: every row as last uploaded (the staging buffer)
+    hipEvent_t ev = nullptr;   // guards reuse of host
+    void release() {
+        (void)hipFree(dev);
+        if (host) (void)hipHostFree(host);
+        if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
 struct softrod_handle {
     softrod_config cfg;
     int device = 0;
@@ -76,14 +89,8 @@ struct softrod_handle {
     hipEvent_t ev_status = nullptr;
     bool status_pending = false;
     hipEvent_t ev_queue = nullptr;  // guards reuse of h_queue / h_produced
-    // per-env material (softrod_set_env_material): nullptr until the first call
-    EnvMaterial* d_env_mat = nullptr;  // [N]
-    EnvMaterial* h_env_mat = nullptr;  // pinned [N]: every row as last uploaded (the staging buffer)
-    hipEvent_t ev_env_mat = nullptr;   // guards reuse of h_env_mat
-    // per-env contact (softrod_set_env_contact): nullptr until the first call
-    EnvContact* d_env_contact = nullptr;  // [N]
-    EnvContact* h_env_contact = nullptr;  // pinned [N]: every row as last uploaded (the staging buffer)
-    hipEvent_t ev_env_contact = nullptr;  // guards reuse of h_env_contact
+    EnvTable<EnvMaterial> env_mat;      // softrod_set_env_material
+    EnvTable<EnvContact> env_contact;   // softrod_set_env_contact
     std::string err;
 };
 
@@ -264,26 +271,6 @@ bool is_pull(const softrod_handle* h) { return h->cfg.env_kind == SOFTROD_ENV_AR
 // the muscle octopus envs (softrod_mocto.hpp): FlatEnv's host API (arm frames + target), the muscle arm's tables
 bool mocto_kind(int e) { return e == SOFTROD_ENV_CRAWL || e == SOFTROD_ENV_ARM_TWO || e == SOFTROD_ENV_REACH; }
 bool is_mocto(const softrod_handle* h) { return mocto_kind(h->cfg.env_kind); }
-// softrod_set_env_material's scope: a uniform one-slot rod of SoftPendulum, SoftPendulum3D or OctoArmSingle with the
-// env's own feature set (the three kFeatEnvMaterial instantiations; the LIBM kernel reads the table at run time).
-// nullptr: in scope; else why not.
-const char* env_material_refusal(const softrod_handle* h) {
-    const unsigned f = h->cfg.features;
-    const int e = h->cfg.env_kind;
-    const bool zup = (h->P.features & kFeatPlaneZup) != 0;
-    if (is_octo(h) || is_mocto(h)) return "per-env material: not for OctoFlat or the muscle octopus envs";
-    if (f & SOFTROD_FEAT_COOMM_MUSCLES) return "per-env material: not for the muscle envs";
-    if (e == SOFTROD_ENV_SOFT_ARM) return "per-env material: not for SoftArmTracking (its muscle torque scale depends on E)";
-    if (h->tapered) return "per-env material: not for a tapered rod (softrod_set_radius_profile)";
-    if (h->epl != 1 || h->window_refresh > 0)
-        return "per-env material: rods of up to 63 elements only (not the two-slot or windowed long rods)";
-    const bool known = (f == SOFTROD_FEATURES_SOFTPENDULUM && e == SOFTROD_ENV_SOFTPENDULUM) ||
-                       (f == SOFTROD_FEATURES_SOFTPENDULUM3D && e == SOFTROD_ENV_SOFTPENDULUM3D) ||
-                       (f == SOFTROD_FEATURES_ARM_SINGLE && e == SOFTROD_ENV_ARM_SINGLE && zup);
-    if (!known || h->cfg.early_termination)
-        return "per-env material: SoftPendulum, SoftPendulum3D and OctoArmSingle with their own feature sets only";
-    return nullptr;
-}
 // One row of the per-env table: fill_params itself on the config with this env's (E, G, rho, nu).
 void env_material_row(const softrod_config& c, const double m[4], EnvMaterial& R) {
     softrod_config ci = c;
@@ -300,32 +287,6 @@ void env_material_row(const softrod_config& c, const double m[4], EnvMaterial& R
     }
     R.mass_node = Q.mass_node; R.mass_total = Q.mass_total; R.damp_t = Q.damp_t;
 }
-
-// softrod_set_env_contact's scope: OctoArmSingle's uniform one-slot rod with its own feature set on an e_z plane (the
-// two kFeatEnvContact fast instantiations, with and without kFeatEnvMaterial; the LIBM kernel reads the table at run
-// time), and OctoFlat / OctoFlatLite on an e_z plane in the two-wave shapes (the two kFeatEnvContact octo
-// instantiations).  nullptr: in scope; else why not.
-const char* env_contact_refusal(const softrod_handle* h) {
-    const unsigned f = h->cfg.features;
-    const int e = h->cfg.env_kind;
-    const bool zup = (h->P.features & kFeatPlaneZup) != 0;
-    if (is_mocto(h) || is_pull(h) || (f & SOFTROD_FEAT_COOMM_MUSCLES)) return "per-env contact: not for the muscle envs";
-    if (!(f & SOFTROD_FEAT_PLANE_CONTACT_ANISO) || !((f == SOFTROD_FEATURES_ARM_SINGLE && e == SOFTROD_ENV_ARM_SINGLE) ||
-                                                    (f == SOFTROD_FEATURES_OCTO_FLAT && e == SOFTROD_ENV_OCTO_FLAT)))
-        return "per-env contact: OctoArmSingle, OctoFlat and OctoFlatLite with their own feature sets only";
-    if (!zup) return "per-env contact: a contact plane with normal e_z only";
-    if (h->cfg.early_termination) return "per-env contact: not with early_termination";
-    if (is_octo(h)) {
-        if (h->nw > 2)
-            return "per-env contact: OctoFlat with at most two waves per env only (n_arm x segment <= 128 lanes; "
-                   "not the four- and eight-wave shapes)";
-        return nullptr;
-    }
-    if (h->tapered) return "per-env contact: not for a tapered rod (softrod_set_radius_profile)";
-    if (h->epl != 1 || h->window_refresh > 0)
-        return "per-env contact: rods of up to 63 elements only (not the two-slot or windowed long rods)";
-    return nullptr;
-}
 // One row of the per-env contact table from (k, nu, kinetic_mu[3], static_mu[3]): the means and half differences with
 // contact_params()' operations, so that the config's own values give the kernels' doubles bit for bit.
 void env_contact_row(const double c[8], EnvContact& R) {
@@ -337,25 +298,250 @@ void env_contact_row(const double c[8], EnvContact& R) {
     R.stat_am[0] = 0.5 * (R.stat_mu[0] + R.stat_mu[1]); R.stat_am[1] = 0.5 * (R.stat_mu[0] - R.stat_mu[1]);
 }
 
+// NEXT_STEP auto-reset pass in front of a step: finished envs restart instead of stepping
+int launch_autoreset(softrod_handle* h, float* obs, double* reward, uint8_t* term, uint8_t* trunc, double* aux, int pack,
+                     hipStream_t st) {
+    const dim3 grid((unsigned)h->cfg.n_envs), block(kLanes * h->nw);
+    if (is_octo(h))
+        hipLaunchKernelGGL(softrod_octo_autoreset_kernel, grid, block, 0, st, h->P, h->S, obs, reward, term, trunc, pack);
+    else if (h->epl == 2)
+        hipLaunchKernelGGL(softrod_autoreset_kernel<2>, grid, block, 0, st, h->P, h->S, obs, reward, term, trunc, aux, pack);
+    else
+        hipLaunchKernelGGL(softrod_autoreset_kernel<1>, grid, block, 0, st, h->P, h->S, obs, reward, term, trunc, aux, pack);
+    SR_HIP(h, hipGetLastError());
+    return SOFTROD_OK;
+}
+
+// ---- the step kernels: one table (kStepRows) decides what a handle runs, what it refuses and what its tier says ----
+// What a handle may carry that a step kernel must not ignore, each by the bit that marks it in a kernel's feature mask:
+// select_step() takes only a row that honours every option active on the handle.
+enum : unsigned { kOptMuscles = SOFTROD_FEAT_COOMM_MUSCLES, kOptEarlyTerm = kFeatEarlyTerm, kOptEnvMaterial = kFeatEnvMaterial,
+                  kOptEnvContact = kFeatEnvContact, kOptCompiledFor = kOptEarlyTerm | kOptEnvMaterial | kOptEnvContact };
+constexpr int kAny = -1, kMoctoEnvs = -2;    // StepRow: every value / (env) the three muscle octopus envs
+constexpr unsigned kAnyFeatures = kRuntimeFeatures;
+using StepKernel = void (*)(RodParams, StatePtrs, const float*, float*, double*, uint8_t*, uint8_t*, double*, int, int, int);
+using OctoKernel = void (*)(RodParams, StatePtrs, const float*, float*, double*, uint8_t*, uint8_t*, int, int, int);
+using WindowKernel = void (*)(RodParams, StatePtrs, const float*, int, int);
+
+struct StepRow {
+    // when it applies
+    unsigned feats;           // softrod_config.features, or kAnyFeatures
+    int env;                  // softrod_config.env_kind, kAny or kMoctoEnvs
+    int math, epl;            // SOFTROD_MATH_*; slots per lane
+    int taper, zup;           // 0, 1 or kAny: softrod_set_radius_profile was called; the contact plane is e_z
+    int nw_min, nw_max;       // waves per env
+    bool windowed;            // env.step of a two-window handle (window_refresh > 0 and the epilogue asked for)
+    unsigned needs, honours;  // options it is compiled FOR (the handle must have them) / honours (the handle may)
+    StepKernel step; OctoKernel octo; WindowKernel window;    // exactly one of the three is set
+    int epb, waves;           // launch shape: envs per workgroup, waves per workgroup (0: the handle's waves per env)
+    const char* label;        // softrod_kernel_tier; {waves}: the handle's waves per env, {refresh}: its window_refresh
+};
+
+// The "when" and the options of an instantiation compiled for the feature mask F follow from F itself.
+constexpr StepRow compiled_row(unsigned F, int env, int epl, int taper, int nw_min, int nw_max, const char* label) {
+    const bool rt = F == kRuntimeFeatures;
+    StepRow r{};
+    r.feats = rt ? kAnyFeatures : F & ~(kFeatPlaneZup | kOptCompiledFor);
+    r.env = env; r.math = SOFTROD_MATH_FAST; r.epl = epl; r.taper = taper; r.nw_min = nw_min; r.nw_max = nw_max;
+    r.zup = rt ? kAny : (F & kFeatPlaneZup) != 0;
+    r.needs = rt ? 0u : F & kOptCompiledFor;
+    r.honours = rt ? 0u : F & (kOptCompiledFor | kOptMuscles);
+    r.epb = 1; r.label = label;
+    return r;
+}
+template <unsigned F, int E, int EPL, bool TAPER = false>
+constexpr StepRow fast_row(const char* label) {
+    StepRow r = compiled_row(F, E, EPL, TAPER, 1, 1, label);
+    r.step = softrod_step_fast_kernel<F, E, EPL, TAPER>;
+    return r;
+}
+template <unsigned F, int MAXW, int EPB>
+constexpr StepRow octo_row(int env, int nw_min, int nw_max, const char* label) {
+    StepRow r = compiled_row(F, env, 1, kAny, nw_min, nw_max, label);
+    r.octo = softrod_octo_step_kernel<F, MAXW, EPB>;
+    r.epb = EPB; r.waves = EPB == 1 ? 0 : MAXW * EPB;
+    return r;
+}
+template <unsigned F, int RPB>     // RPB rods per workgroup: 4 (a rod's two windows on one SIMD) or 1 (with s_barrier)
+constexpr StepRow window_row(const char* label) {
+    StepRow r = compiled_row(F, SOFTROD_ENV_ARM_SINGLE, 2, 0, 1, 1, label);
+    r.window = softrod_step_window_kernel<F, RPB>;
+    r.windowed = true; r.epb = RPB; r.waves = 2 * RPB;
+    return r;
+}
+// The LIBM kernel evaluates any feature mix and reads the per-env tables at run time; the tables themselves exist for
+// the uniform rods of the envs named here.
+template <bool ET>
+constexpr StepRow libm_row(unsigned feats, int env, int zup, int taper, unsigned honours) {
+    StepRow r{};
+    r.feats = feats; r.env = env; r.math = SOFTROD_MATH_LIBM; r.epl = 1; r.taper = taper; r.zup = zup;
+    r.nw_min = r.nw_max = r.epb = 1;
+    r.needs = ET ? kOptEarlyTerm : 0u; r.honours = r.needs | kOptMuscles | honours;
+    r.step = softrod_step_libm_kernel<ET>;
+    r.label = "softrod_step_libm_kernel";
+    return r;
+}
+
+constexpr unsigned kArmSingleZup = SOFTROD_FEATURES_ARM_SINGLE | kFeatPlaneZup, kOctoFlatZup = SOFTROD_FEATURES_OCTO_FLAT | kFeatPlaneZup;
+// One row per instantiation; the first row that serves a handle is its kernel, so the run-time-mask rows (custom
+// feature mixes, known-answer tests) stand behind the specialised ones of their (epl, taper).
+const StepRow kStepRows[] = {
+    // the muscle arm with a weight, and the muscle octopus (action kernel | this | epilogue kernel, softrod_mocto.hpp)
+    octo_row<SOFTROD_FEATURES_ARM_PULL_WEIGHT | kFeatEarlyTerm, 2, 1>(SOFTROD_ENV_ARM_PULL_WEIGHT, 1, 1, "softrod_octo_step_kernel<ArmPullWeight,1 wave,1 env/wg,taper>"),
+    octo_row<SOFTROD_FEATURES_ARM_PULL_WEIGHT, 2, 1>(SOFTROD_ENV_ARM_PULL_WEIGHT, 1, 1, "softrod_octo_step_kernel<ArmPullWeight,1 wave,1 env/wg,taper>"),
+    octo_row<SOFTROD_FEATURES_ARM_PULL_WEIGHT, 4, 1>(kMoctoEnvs, 1, 4, "softrod_mocto_action_kernel | softrod_octo_step_kernel<muscle arms,"
+                                                                       "{waves},1 env/wg,taper> | softrod_mocto_epilogue_kernel"),
+    // OctoFlat; the reference shape (two waves per env) runs four envs per workgroup, partner waves on one SIMD
+    octo_row<kOctoFlatZup | kFeatEnvContact, 2, 4>(SOFTROD_ENV_OCTO_FLAT, 2, 2, "softrod_octo_step_kernel<zup,2 waves,4 envs/wg>"),
+    octo_row<kOctoFlatZup | kFeatEnvContact, 2, 1>(SOFTROD_ENV_OCTO_FLAT, 1, 1, "softrod_octo_step_kernel<zup,2 waves max,1 env/wg>"),
+    octo_row<kOctoFlatZup, 2, 4>(SOFTROD_ENV_OCTO_FLAT, 2, 2, "softrod_octo_step_kernel<zup,2 waves,4 envs/wg>"),
+    octo_row<kOctoFlatZup, 2, 1>(SOFTROD_ENV_OCTO_FLAT, 1, 1, "softrod_octo_step_kernel<zup,2 waves max,1 env/wg>"),
+    octo_row<kOctoFlatZup, 8, 1>(SOFTROD_ENV_OCTO_FLAT, 3, 8, "softrod_octo_step_kernel<zup,8 waves max,1 env/wg>"),
+    octo_row<SOFTROD_FEATURES_OCTO_FLAT, 2, 1>(SOFTROD_ENV_OCTO_FLAT, 1, 2, "softrod_octo_step_kernel<general plane,2 waves max,1 env/wg>"),
+    octo_row<SOFTROD_FEATURES_OCTO_FLAT, 8, 1>(SOFTROD_ENV_OCTO_FLAT, 3, 8, "softrod_octo_step_kernel<general plane,8 waves max,1 env/wg>"),
+    // OctoArmSingle of 64..102 elements: substeps on two overlapping one-node-per-lane windows (softrod_window.hpp), then
+    // reward / observation by the two-slot row below with n_sub = 0
+    window_row<kArmSingleZup, 4>("softrod_step_window_kernel<ArmSingle,4 rods/wg> refresh={refresh}"),
+    window_row<kArmSingleZup, 1>("softrod_step_window_kernel<ArmSingle,1 rod/wg,s_barrier> refresh={refresh}"),
+    fast_row<kArmSingleZup, SOFTROD_ENV_ARM_SINGLE, 2>("softrod_step_fast_kernel<ArmSingle,epl=2>"),
+    // tapered rods (per-lane material constants): the ArmPush arm of 64..126 and of up to 63 elements, the tapered
+    // OctoArmSingle (`bench.py --taper`), the damped arm with suckers of arm_push_env.py:160-196 without its muscles
+    fast_row<SOFTROD_FEATURES_ARM_PUSH | kFeatEarlyTerm, SOFTROD_ENV_ARM_PUSH, 2, true>("softrod_step_fast_kernel<ArmPush,epl=2,taper>"),
+    fast_row<SOFTROD_FEATURES_ARM_PUSH, SOFTROD_ENV_ARM_PUSH, 2, true>("softrod_step_fast_kernel<ArmPush,epl=2,taper>"),
+    fast_row<kArmSingleZup, SOFTROD_ENV_ARM_SINGLE, 1, true>("softrod_step_fast_kernel<ArmSingle,epl=1,taper>"),
+    fast_row<kFeaturesTaperedSuckerArm, SOFTROD_ENV_NONE, 1, true>("softrod_step_fast_kernel<damped sucker arm,epl=1,taper>"),
+    fast_row<SOFTROD_FEATURES_ARM_PUSH | kFeatEarlyTerm, SOFTROD_ENV_ARM_PUSH, 1, true>("softrod_step_fast_kernel<ArmPush,epl=1,taper>"),
+    fast_row<SOFTROD_FEATURES_ARM_PUSH, SOFTROD_ENV_ARM_PUSH, 1, true>("softrod_step_fast_kernel<ArmPush,epl=1,taper>"),
+    fast_row<kRuntimeFeatures, kRuntimeEnv, 1, true>("softrod_step_fast_kernel<runtime mask,epl=1,taper>"),
+    // uniform rods, two slots per lane, and the uniform muscle rod of the known-answer tests
+    fast_row<SOFTROD_FEATURES_SOFTPENDULUM, SOFTROD_ENV_SOFTPENDULUM, 2>("softrod_step_fast_kernel<SoftPendulum,epl=2>"),
+    fast_row<SOFTROD_FEATURES_SOFTPENDULUM3D, SOFTROD_ENV_SOFTPENDULUM3D, 2>("softrod_step_fast_kernel<SoftPendulum3D,epl=2>"),
+    fast_row<SOFTROD_FEATURES_SOFT_ARM, SOFTROD_ENV_SOFT_ARM, 2>("softrod_step_fast_kernel<SoftArm,epl=2>"),
+    fast_row<kFeaturesMuscleRod, SOFTROD_ENV_NONE, 1>("softrod_step_fast_kernel<muscle rod,epl=1>"),
+    fast_row<kRuntimeFeatures, kRuntimeEnv, 2>("softrod_step_fast_kernel<runtime mask,epl=2>"),
+    // uniform rods, one slot per lane: with the per-env tables, then without
+    fast_row<kArmSingleZup | kFeatEnvContact | kFeatEnvMaterial, SOFTROD_ENV_ARM_SINGLE, 1>("softrod_step_fast_kernel<ArmSingle,epl=1>"),
+    fast_row<kArmSingleZup | kFeatEnvContact, SOFTROD_ENV_ARM_SINGLE, 1>("softrod_step_fast_kernel<ArmSingle,epl=1>"),
+    fast_row<SOFTROD_FEATURES_SOFTPENDULUM | kFeatEnvMaterial, SOFTROD_ENV_SOFTPENDULUM, 1>("softrod_step_fast_kernel<SoftPendulum,epl=1>"),
+    fast_row<SOFTROD_FEATURES_SOFTPENDULUM3D | kFeatEnvMaterial, SOFTROD_ENV_SOFTPENDULUM3D, 1>("softrod_step_fast_kernel<SoftPendulum3D,epl=1>"),
+    fast_row<kArmSingleZup | kFeatEnvMaterial, SOFTROD_ENV_ARM_SINGLE, 1>("softrod_step_fast_kernel<ArmSingle,epl=1>"),
+    fast_row<SOFTROD_FEATURES_SOFTPENDULUM, SOFTROD_ENV_SOFTPENDULUM, 1>("softrod_step_fast_kernel<SoftPendulum,epl=1>"),
+    fast_row<SOFTROD_FEATURES_SOFTPENDULUM3D, SOFTROD_ENV_SOFTPENDULUM3D, 1>("softrod_step_fast_kernel<SoftPendulum3D,epl=1>"),
+    fast_row<kArmSingleZup, SOFTROD_ENV_ARM_SINGLE, 1>("softrod_step_fast_kernel<ArmSingle,epl=1>"),
+    fast_row<SOFTROD_FEATURES_SOFT_ARM, SOFTROD_ENV_SOFT_ARM, 1>("softrod_step_fast_kernel<SoftArm,epl=1>"),
+    fast_row<kRuntimeFeatures, kRuntimeEnv, 1>("softrod_step_fast_kernel<runtime mask,epl=1>"),
+    // SOFTROD_MATH_LIBM
+    libm_row<true>(kAnyFeatures, kAny, kAny, kAny, 0u),
+    libm_row<false>(SOFTROD_FEATURES_SOFTPENDULUM, SOFTROD_ENV_SOFTPENDULUM, kAny, 0, kOptEnvMaterial),
+    libm_row<false>(SOFTROD_FEATURES_SOFTPENDULUM3D, SOFTROD_ENV_SOFTPENDULUM3D, kAny, 0, kOptEnvMaterial),
+    libm_row<false>(SOFTROD_FEATURES_ARM_SINGLE, SOFTROD_ENV_ARM_SINGLE, 1, 0, kOptEnvMaterial | kOptEnvContact),
+    libm_row<false>(kAnyFeatures, kAny, kAny, kAny, 0u),
+};
+
+unsigned active_options(const softrod_handle* h) {
+    return (h->cfg.features & kOptMuscles) | (h->cfg.early_termination ? kOptEarlyTerm : 0u) |
+           (h->env_mat.dev ? kOptEnvMaterial : 0u) | (h->env_contact.dev ? kOptEnvContact : 0u);
+}
+
+// The wording of a refusal, consulted only once no row of kStepRows serves the handle with the options `opts`: the
+// first reason that applies.  nullptr: none of these.
+const char* material_why_not(const softrod_handle* h) {
+    const unsigned f = h->cfg.features;
+    const int e = h->cfg.env_kind;
+    if (is_octo(h) || is_mocto(h)) return "per-env material: not for OctoFlat or the muscle octopus envs";
+    if (f & SOFTROD_FEAT_COOMM_MUSCLES) return "per-env material: not for the muscle envs";
+    if (e == SOFTROD_ENV_SOFT_ARM) return "per-env material: not for SoftArmTracking (its muscle torque scale depends on E)";
+    if (h->tapered) return "per-env material: not for a tapered rod (softrod_set_radius_profile)";
+    if (h->epl != 1 || h->window_refresh > 0)
+        return "per-env material: rods of up to 63 elements only (not the two-slot or windowed long rods)";
+    return "per-env material: SoftPendulum, SoftPendulum3D and OctoArmSingle with their own feature sets only";
+}
+const char* contact_why_not(const softrod_handle* h) {
+    const unsigned f = h->cfg.features;
+    const int e = h->cfg.env_kind;
+    if (is_mocto(h) || is_pull(h) || (f & SOFTROD_FEAT_COOMM_MUSCLES)) return "per-env contact: not for the muscle envs";
+    if (!(f & SOFTROD_FEAT_PLANE_CONTACT_ANISO) || !((f == SOFTROD_FEATURES_ARM_SINGLE && e == SOFTROD_ENV_ARM_SINGLE) ||
+                                                    (f == SOFTROD_FEATURES_OCTO_FLAT && e == SOFTROD_ENV_OCTO_FLAT)))
+        return "per-env contact: OctoArmSingle, OctoFlat and OctoFlatLite with their own feature sets only";
+    if (!(h->P.features & kFeatPlaneZup)) return "per-env contact: a contact plane with normal e_z only";
+    if (h->cfg.early_termination) return "per-env contact: not with early_termination";
+    if (is_octo(h))
+        return "per-env contact: OctoFlat with at most two waves per env only (n_arm x segment <= 128 lanes; "
+               "not the four- and eight-wave shapes)";
+    if (h->tapered) return "per-env contact: not for a tapered rod (softrod_set_radius_profile)";
+    return "per-env contact: rods of up to 63 elements only (not the two-slot or windowed long rods)";
+}
+const char* why_no_row(const softrod_handle* h, unsigned opts) {
+    if ((opts & kOptEarlyTerm) && h->cfg.math_mode == SOFTROD_MATH_FAST && !is_pull(h) &&
+        !(h->tapered && h->cfg.features == SOFTROD_FEATURES_ARM_PUSH && h->cfg.env_kind == SOFTROD_ENV_ARM_PUSH))
+        return "early_termination (SOFTROD_MATH_FAST) runs on the tapered SOFTROD_FEATURES_ARM_PUSH arm "
+               "and on SOFTROD_ENV_ARM_PULL_WEIGHT only; other feature mixes: SOFTROD_MATH_LIBM";
+    if (opts & kOptEnvMaterial) return material_why_not(h);
+    if (opts & kOptEnvContact) return contact_why_not(h);
+    return nullptr;
+}
+
+// The handle's step kernel: the first row of kStepRows that applies to it and honours every option it has, together
+// with `with` (an option about to be added).  epilogue = 0: softrod_substeps' form, which a windowed handle takes on
+// its two-slot kernel.  No such row: `why` says so, naming `with` first.
+struct StepChoice { const StepRow* row; const char* why; };
+StepChoice select_step(const softrod_handle* h, int epilogue = 1, unsigned with = 0u) {
+    const unsigned opts = active_options(h) | with;
+    const int e = h->cfg.env_kind, zup = (h->P.features & kFeatPlaneZup) != 0;
+    const bool windowed = h->window_refresh > 0 && epilogue;
+    for (const StepRow& r : kStepRows)
+        if (r.math == h->cfg.math_mode && (r.feats == kAnyFeatures || r.feats == h->cfg.features) &&
+            (r.env == kAny || (r.env == kMoctoEnvs ? mocto_kind(e) : r.env == e)) && r.epl == h->epl &&
+            (r.taper == kAny || r.taper == (int)h->tapered) && (r.zup == kAny || r.zup == zup) &&
+            r.nw_min <= h->nw && h->nw <= r.nw_max && r.windowed == windowed &&
+            (!r.window || r.epb == (h->window_paired ? 4 : 1)) && !(r.needs & ~opts) && !(opts & ~r.honours))
+            return {&r, nullptr};
+    const char* why = why_no_row(h, with);
+    if (!why) why = why_no_row(h, opts);
+    return {nullptr, why ? why : "no step kernel is compiled for this handle's feature set, env kind and options"};
+}
+
+// softrod_set_env_material / softrod_set_env_contact: W doubles per env in, one Row per env on the device.  Refused
+// unless a step kernel honours `option` on this handle; `bad` names what is wrong with an env's values (nullptr: nothing);
+// the first call allocates the table with every row at the config's `own` values; only rows with mask != 0 change.
+template <int W, class Row, class Bad, class Build>
+int set_env_table(softrod_handle* h, EnvTable<Row>& T, const Row*& slot, unsigned option, const char* what,
+                  const double* values, const double (&own)[W], const uint8_t* mask, void* stream, Bad bad, Build build) {
+    const StepChoice serves = select_step(h, 1, option);
+    if (!serves.row) return fail(h, SOFTROD_EINVAL, serves.why);
+    const size_t N = (size_t)h->cfg.n_envs;
+    for (size_t i = 0; i < N; ++i) {
+        if (mask && !mask[i]) continue;
+        if (const char* why = bad(values + W * i)) return fail(h, SOFTROD_EINVAL, what + std::to_string(i) + why);
+    }
+    SR_ON_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (!T.dev) {
+        SR_HIP(h, hipMalloc((void**)&T.dev, N * sizeof(Row)));
+        SR_HIP(h, hipHostMalloc((void**)&T.host, N * sizeof(Row), hipHostMallocDefault));
+        SR_HIP(h, hipEventCreateWithFlags(&T.ev, hipEventDisableTiming));
+        Row R0;
+        build(own, R0);
+        for (size_t i = 0; i < N; ++i) T.host[i] = R0;
+        slot = T.dev;
+        SR_HIP(h, hipMemcpy(h->d_state, &h->S, sizeof(StatePtrs), hipMemcpyHostToDevice));
+    } else {
+        SR_HIP(h, hipEventSynchronize(T.ev));   // the previous upload has left the staging buffer
+    }
+    for (size_t i = 0; i < N; ++i)
+        if (!mask || mask[i]) build(values + W * i, T.host[i]);
+    SR_HIP(h, hipMemcpyAsync(T.dev, T.host, N * sizeof(Row), hipMemcpyHostToDevice, st));
+    SR_HIP(h, hipEventRecord(T.ev, st));
+    return SOFTROD_OK;
+}
+
 int launch_step(softrod_handle* h, const float* actions, float* obs, double* reward,
                 uint8_t* term, uint8_t* trunc, double* aux, int n_sub, int epilogue, int pack,
                 hipStream_t st) {
-    const dim3 grid((unsigned)h->cfg.n_envs), block(kLanes * h->nw);
-    if (h->q_depth > 0 && epilogue) {   // NEXT_STEP auto-reset pass: finished envs restart instead of stepping
-        if (is_octo(h))
-            hipLaunchKernelGGL(softrod_octo_autoreset_kernel, grid, block, 0, st, h->P, h->S, obs, reward, term,
-                               trunc, pack);
-        else if (h->epl == 2)
-            hipLaunchKernelGGL(softrod_autoreset_kernel<2>, grid, block, 0, st, h->P, h->S, obs, reward, term,
-                               trunc, aux, pack);
-        else
-            hipLaunchKernelGGL(softrod_autoreset_kernel<1>, grid, block, 0, st, h->P, h->S, obs, reward, term,
-                               trunc, aux, pack);
-        SR_HIP(h, hipGetLastError());
-    }
+    if (h->q_depth > 0 && epilogue)
+        if (const int rc = launch_autoreset(h, obs, reward, term, trunc, aux, pack, st)) return rc;
     if ((h->cfg.features & SOFTROD_FEAT_COOMM_MUSCLES) && h->cfg.math_mode == SOFTROD_MATH_FAST) {
-        // the fast kernel carries the muscle layers in two instantiations only (kMusclesCompiled): the tapered
-        // ArmPush arm and the uniform muscle rod; never let another one run a muscle handle without its muscles
+        // what the muscle handles need set before they step
         const bool push = h->cfg.env_kind == SOFTROD_ENV_ARM_PUSH || is_pull(h) || is_mocto(h);
         if (is_mocto(h) && (!h->tapered || !h->muscles_set || (h->cfg.env_kind == SOFTROD_ENV_ARM_TWO && !h->basis_set)))
             return fail(h, SOFTROD_EINVAL, "the muscle octopus needs softrod_set_radius_profile and softrod_set_muscle_layers "
@@ -366,148 +552,28 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
         if (!push && h->tapered)
             return fail(h, SOFTROD_EINVAL, "a tapered muscle rod outside SOFTROD_ENV_ARM_PUSH runs under SOFTROD_MATH_LIBM only");
     }
-    if (h->cfg.early_termination && h->cfg.math_mode == SOFTROD_MATH_FAST && !(is_octo(h) && is_pull(h)) &&
-        !(h->tapered && h->cfg.features == SOFTROD_FEATURES_ARM_PUSH && h->cfg.env_kind == SOFTROD_ENV_ARM_PUSH))
-        // only the instantiations FOR the flag evaluate it (kFeatEarlyTerm): never let another kernel ignore it
-        return fail(h, SOFTROD_EINVAL, "early_termination (SOFTROD_MATH_FAST) runs on the tapered SOFTROD_FEATURES_ARM_PUSH arm "
-                                       "and on SOFTROD_ENV_ARM_PULL_WEIGHT only; other feature mixes: SOFTROD_MATH_LIBM");
-    if (h->d_env_mat) {   // never let a kernel that ignores the per-env table step this handle
-        if (const char* why = env_material_refusal(h)) return fail(h, SOFTROD_EINVAL, why);
-    }
-    if (h->d_env_contact) {   // the same for the per-env contact table
-        if (const char* why = env_contact_refusal(h)) return fail(h, SOFTROD_EINVAL, why);
-    }
+    const StepChoice c = select_step(h, epilogue);
+    if (!c.row) return fail(h, SOFTROD_EINVAL, c.why);
+    // a windowed env.step: its substeps, then reward / observation by the row of the same handle's plain substeps
+    const StepChoice after = c.row->windowed ? select_step(h, 0) : StepChoice{nullptr, nullptr};
+    if (c.row->windowed && !after.row) return fail(h, SOFTROD_EINVAL, after.why);
+    auto launch = [&](const StepRow& r, int n, int epi) {
+        const dim3 grid((unsigned)((h->cfg.n_envs + r.epb - 1) / r.epb)), block(kLanes * (r.waves ? r.waves : h->nw));
+        if (r.window) hipLaunchKernelGGL(r.window, grid, block, 0, st, h->P, h->S, actions, n, h->window_refresh);
+        else if (r.octo) hipLaunchKernelGGL(r.octo, grid, block, 0, st, h->P, h->S, actions, obs, reward, term, trunc, n, epi, pack);
+        else hipLaunchKernelGGL(r.step, grid, block, 0, st, h->P, h->S, actions, obs, reward, term, trunc, aux, n, epi, pack);
+    };
     const bool timing = h->timed < (int)h->ev_start.size();
     if (timing) SR_HIP(h, hipEventRecord(h->ev_start[h->timed], st));
-    const bool zup = (h->P.features & kFeatPlaneZup) != 0;
-    if (is_octo(h) && is_pull(h)) {
-        if (h->cfg.early_termination)
-            hipLaunchKernelGGL((softrod_octo_step_kernel<SOFTROD_FEATURES_ARM_PULL_WEIGHT | kFeatEarlyTerm, 2, 1>), grid, block,
-                               0, st, h->P, h->S, actions, obs, reward, term, trunc, n_sub, epilogue, pack);
-        else
-        hipLaunchKernelGGL((softrod_octo_step_kernel<SOFTROD_FEATURES_ARM_PULL_WEIGHT, 2, 1>), grid, block, 0, st, h->P, h->S,
-                           actions, obs, reward, term, trunc, n_sub, epilogue, pack);
-    } else if (is_mocto(h)) {
-        // set_action | the body's substeps | get_state + reward (softrod_mocto.hpp); the timing events bracket all three
-        if (epilogue && actions)
-            hipLaunchKernelGGL(softrod_mocto_action_kernel, grid, block, 0, st, h->P, h->S, actions, n_sub);
-        hipLaunchKernelGGL((softrod_octo_step_kernel<SOFTROD_FEATURES_ARM_PULL_WEIGHT, 4, 1>), grid, block, 0, st, h->P, h->S,
-                           actions, obs, reward, term, trunc, n_sub, epilogue, pack);
-        if (epilogue)
-            hipLaunchKernelGGL(softrod_mocto_epilogue_kernel, grid, block, 0, st, h->P, h->S, obs, reward, term, trunc, 1, pack);
-    } else if (is_octo(h)) {
-#define SR_OCTO(FEATS, MAXW)                                                                        \
-        hipLaunchKernelGGL((softrod_octo_step_kernel<FEATS, MAXW>), grid, block, 0, st, h->P, h->S,     \
-                           actions, obs, reward, term, trunc, n_sub, epilogue, pack)
-        // the reference shape (two waves per env): four envs per workgroup, partner waves on one SIMD
-        if (h->d_env_contact) {   // per-env contact: the instantiations FOR it (env_contact_refusal: zup, nw <= 2)
-            if (h->nw == 2)
-                hipLaunchKernelGGL((softrod_octo_step_kernel<SOFTROD_FEATURES_OCTO_FLAT | kFeatPlaneZup | kFeatEnvContact, 2, 4>),
-                                   dim3((unsigned)((h->cfg.n_envs + 3) / 4)), dim3(kLanes * 8), 0, st, h->P, h->S,
-                                   actions, obs, reward, term, trunc, n_sub, epilogue, pack);
-            else
-                SR_OCTO(SOFTROD_FEATURES_OCTO_FLAT | kFeatPlaneZup | kFeatEnvContact, 2);
-        } else if (zup && h->nw == 2) {
-            hipLaunchKernelGGL((softrod_octo_step_kernel<SOFTROD_FEATURES_OCTO_FLAT | kFeatPlaneZup, 2, 4>),
-                               dim3((unsigned)((h->cfg.n_envs + 3) / 4)), dim3(kLanes * 8), 0, st, h->P, h->S,
-                               actions, obs, reward, term, trunc, n_sub, epilogue, pack);
-        } else if (zup) {
-            if (h->nw <= 2) SR_OCTO(SOFTROD_FEATURES_OCTO_FLAT | kFeatPlaneZup, 2);
-            else SR_OCTO(SOFTROD_FEATURES_OCTO_FLAT | kFeatPlaneZup, 8);
-        } else {
-            if (h->nw <= 2) SR_OCTO(SOFTROD_FEATURES_OCTO_FLAT, 2);
-            else SR_OCTO(SOFTROD_FEATURES_OCTO_FLAT, 8);
-        }
-#undef SR_OCTO
-    } else if (h->window_refresh > 0 && epilogue) {
-        // substeps on two overlapping one-node-per-lane windows, then reward / observation by the
-        // two-slot kernel with n_sub = 0 on the same rows (the timing events bracket both)
-        if (h->window_paired)     // four rods per workgroup, a rod's two windows on one SIMD (softrod_window.hpp)
-            hipLaunchKernelGGL((softrod_step_window_kernel<SOFTROD_FEATURES_ARM_SINGLE | kFeatPlaneZup, 4>),
-                               dim3((unsigned)((h->cfg.n_envs + 3) / 4)), dim3(8 * kLanes), 0, st, h->P, h->S, actions,
-                               n_sub, h->window_refresh);
-        else
-        hipLaunchKernelGGL((softrod_step_window_kernel<SOFTROD_FEATURES_ARM_SINGLE | kFeatPlaneZup>), grid,
-                           dim3(2 * kLanes), 0, st, h->P, h->S, actions, n_sub, h->window_refresh);
-        hipLaunchKernelGGL((softrod_step_fast_kernel<SOFTROD_FEATURES_ARM_SINGLE | kFeatPlaneZup,
-                                                     SOFTROD_ENV_ARM_SINGLE, 2>),
-                           grid, dim3(kLanes), 0, st, h->P, h->S, actions, obs, reward, term, trunc, aux, 0, 1, pack);
-    } else if (h->cfg.math_mode == SOFTROD_MATH_FAST) {
-        // instantiations specialised for the registered envs' feature sets (one or two
-        // slots per lane); anything else (known-answer tests, custom feature mixes) takes
-        // the run-time-mask instantiation
-        const unsigned f = h->cfg.features;
-        const int e = h->cfg.env_kind;
-#define SR_LAUNCH(FEATS, ENV, EPL)                                                                  \
-        hipLaunchKernelGGL((softrod_step_fast_kernel<FEATS, ENV, EPL>), grid, block, 0, st, h->P, h->S, \
-                           actions, obs, reward, term, trunc, aux, n_sub, epilogue, pack)
-#define SR_DISPATCH(EPL)                                                                            \
-        do {                                                                                        \
-            if (f == SOFTROD_FEATURES_SOFTPENDULUM && e == SOFTROD_ENV_SOFTPENDULUM)                \
-                SR_LAUNCH(SOFTROD_FEATURES_SOFTPENDULUM, SOFTROD_ENV_SOFTPENDULUM, EPL);            \
-            else if (f == SOFTROD_FEATURES_SOFTPENDULUM3D && e == SOFTROD_ENV_SOFTPENDULUM3D)       \
-                SR_LAUNCH(SOFTROD_FEATURES_SOFTPENDULUM3D, SOFTROD_ENV_SOFTPENDULUM3D, EPL);        \
-            else if (f == SOFTROD_FEATURES_ARM_SINGLE && e == SOFTROD_ENV_ARM_SINGLE && zup)        \
-                SR_LAUNCH(SOFTROD_FEATURES_ARM_SINGLE | kFeatPlaneZup, SOFTROD_ENV_ARM_SINGLE, EPL); \
-            else if (f == SOFTROD_FEATURES_SOFT_ARM && e == SOFTROD_ENV_SOFT_ARM)                   \
-                SR_LAUNCH(SOFTROD_FEATURES_SOFT_ARM, SOFTROD_ENV_SOFT_ARM, EPL);                    \
-            else if (f == kFeaturesMuscleRod && e == SOFTROD_ENV_NONE && EPL == 1)                  \
-                SR_LAUNCH(kFeaturesMuscleRod, SOFTROD_ENV_NONE, 1);                                 \
-            else                                                                                    \
-                SR_LAUNCH(kRuntimeFeatures, kRuntimeEnv, EPL);                                      \
-        } while (0)
-        if (h->tapered && h->epl == 2) {    // the ArmPush arm of 64..126 elements, two slots per lane
-            // (softrod_set_radius_profile tapers no other two-slot handle)
-            if (h->cfg.early_termination)
-                hipLaunchKernelGGL((softrod_step_fast_kernel<SOFTROD_FEATURES_ARM_PUSH | kFeatEarlyTerm, SOFTROD_ENV_ARM_PUSH, 2, true>),
-                                   grid, block, 0, st, h->P, h->S, actions, obs, reward, term, trunc, aux, n_sub, epilogue, pack);
-            else
-                hipLaunchKernelGGL((softrod_step_fast_kernel<SOFTROD_FEATURES_ARM_PUSH, SOFTROD_ENV_ARM_PUSH, 2, true>),
-                                   grid, block, 0, st, h->P, h->S, actions, obs, reward, term, trunc, aux, n_sub, epilogue, pack);
-        } else if (h->tapered) {    // per-lane material constants (TAPER = true), one slot per lane
-#define SR_LAUNCH_TAPER(FEATS, ENV)                                                                 \
-            hipLaunchKernelGGL((softrod_step_fast_kernel<FEATS, ENV, 1, true>), grid, block, 0, st, h->P, h->S, \
-                               actions, obs, reward, term, trunc, aux, n_sub, epilogue, pack)
-            // the two tapered feature sets the reference holds on disk get their own instantiation: the
-            // OctoArmSingle set (a tapered arm on the plane, `bench.py --taper`) and the damped arm with
-            // ControllableFixConstraint suckers of arm_push_env.py:160-196 (its COOMM muscles are not on
-            // disk); any other mix takes the run-time mask
-            if (f == SOFTROD_FEATURES_ARM_SINGLE && e == SOFTROD_ENV_ARM_SINGLE && zup)
-                SR_LAUNCH_TAPER(SOFTROD_FEATURES_ARM_SINGLE | kFeatPlaneZup, SOFTROD_ENV_ARM_SINGLE);
-            else if (f == kFeaturesTaperedSuckerArm && e == SOFTROD_ENV_NONE)
-                SR_LAUNCH_TAPER(kFeaturesTaperedSuckerArm, SOFTROD_ENV_NONE);
-            else if (f == SOFTROD_FEATURES_ARM_PUSH && e == SOFTROD_ENV_ARM_PUSH && h->cfg.early_termination)
-                SR_LAUNCH_TAPER(SOFTROD_FEATURES_ARM_PUSH | kFeatEarlyTerm, SOFTROD_ENV_ARM_PUSH);
-            else if (f == SOFTROD_FEATURES_ARM_PUSH && e == SOFTROD_ENV_ARM_PUSH)     // OctoArmPush-v0 / -v1
-                SR_LAUNCH_TAPER(SOFTROD_FEATURES_ARM_PUSH, SOFTROD_ENV_ARM_PUSH);
-            else
-                SR_LAUNCH_TAPER(kRuntimeFeatures, kRuntimeEnv);
-#undef SR_LAUNCH_TAPER
-        } else if (h->epl == 2) SR_DISPATCH(2);
-        else if (h->d_env_contact) {   // per-env contact (kFeatEnvContact; env_contact_refusal has admitted OctoArmSingle
-                                       // only here), with or without per-env material
-            if (h->d_env_mat)
-                SR_LAUNCH(SOFTROD_FEATURES_ARM_SINGLE | kFeatPlaneZup | kFeatEnvContact | kFeatEnvMaterial,
-                          SOFTROD_ENV_ARM_SINGLE, 1);
-            else
-                SR_LAUNCH(SOFTROD_FEATURES_ARM_SINGLE | kFeatPlaneZup | kFeatEnvContact, SOFTROD_ENV_ARM_SINGLE, 1);
-        } else if (h->d_env_mat) {   // per-env material: the instantiations FOR it (kFeatEnvMaterial; env_material_refusal
-                                   // has admitted exactly these three)
-            if (e == SOFTROD_ENV_SOFTPENDULUM)
-                SR_LAUNCH(SOFTROD_FEATURES_SOFTPENDULUM | kFeatEnvMaterial, SOFTROD_ENV_SOFTPENDULUM, 1);
-            else if (e == SOFTROD_ENV_SOFTPENDULUM3D)
-                SR_LAUNCH(SOFTROD_FEATURES_SOFTPENDULUM3D | kFeatEnvMaterial, SOFTROD_ENV_SOFTPENDULUM3D, 1);
-            else
-                SR_LAUNCH(SOFTROD_FEATURES_ARM_SINGLE | kFeatPlaneZup | kFeatEnvMaterial, SOFTROD_ENV_ARM_SINGLE, 1);
-        } else SR_DISPATCH(1);
-#undef SR_DISPATCH
-#undef SR_LAUNCH
-    } else if (h->cfg.early_termination) {
-        hipLaunchKernelGGL(softrod_step_libm_kernel<true>, grid, block, 0, st, h->P, h->S,
-                           actions, obs, reward, term, trunc, aux, n_sub, epilogue, pack);
-    } else
-        hipLaunchKernelGGL(softrod_step_libm_kernel<false>, grid, block, 0, st, h->P, h->S,
-                           actions, obs, reward, term, trunc, aux, n_sub, epilogue, pack);
+    // the muscle octopus: set_action | the body's substeps | get_state + reward; the timing events bracket all three
+    const bool mocto = c.row->env == kMoctoEnvs;
+    const dim3 grid((unsigned)h->cfg.n_envs), block(kLanes * h->nw);
+    if (mocto && epilogue && actions)
+        hipLaunchKernelGGL(softrod_mocto_action_kernel, grid, block, 0, st, h->P, h->S, actions, n_sub);
+    launch(*c.row, n_sub, epilogue);
+    if (after.row) launch(*after.row, 0, 1);
+    if (mocto && epilogue)
+        hipLaunchKernelGGL(softrod_mocto_epilogue_kernel, grid, block, 0, st, h->P, h->S, obs, reward, term, trunc, 1, pack);
     SR_HIP(h, hipGetLastError());
     if (timing) {
         SR_HIP(h, hipEventRecord(h->ev_stop[h->timed], st));
@@ -1444,7 +1510,7 @@ int softrod_set_spline_table(softrod_handle* h, const double* breaks, const doub
 // kernels' per-lane material table.  Mirrors straight_rod() of oracle/softrod_oracle.c.
 int softrod_set_radius_profile(softrod_handle* h, const double* radius) {
     if (!h || !radius) return fail(h, SOFTROD_EINVAL, "null argument");
-    // two slots per lane: the ArmPush arm only (its two-slot instantiations in launch_step)
+    // two slots per lane: the ArmPush arm only (its two-slot rows of kStepRows)
     const bool two_slot_push = h->epl == 2 && h->cfg.features == SOFTROD_FEATURES_ARM_PUSH &&
                                h->cfg.env_kind == SOFTROD_ENV_ARM_PUSH && h->cfg.math_mode == SOFTROD_MATH_FAST;
     if ((is_octo(h) && !is_pull(h) && !is_mocto(h)) || (h->epl != 1 && !two_slot_push) || h->window_refresh > 0)
@@ -1515,77 +1581,32 @@ int softrod_set_radius_profile(softrod_handle* h, const double* radius) {
 
 int softrod_set_env_material(softrod_handle* h, const double* material, const uint8_t* mask, void* stream) {
     if (!h || !material) return fail(h, SOFTROD_EINVAL, "null argument");
-    if (const char* why = env_material_refusal(h)) return fail(h, SOFTROD_EINVAL, why);
-    const size_t N = (size_t)h->cfg.n_envs;
-    for (size_t i = 0; i < N; ++i) {
-        if (mask && !mask[i]) continue;
-        const double* m = material + 4 * i;
-        if (!(std::isfinite(m[0]) && std::isfinite(m[1]) && std::isfinite(m[2]) && std::isfinite(m[3])))
-            return fail(h, SOFTROD_EINVAL, "per-env material: env " + std::to_string(i) + " has a non-finite value");
-        if (!(m[0] > 0.0 && m[1] > 0.0 && m[2] > 0.0 && m[3] >= 0.0))
-            return fail(h, SOFTROD_EINVAL, "per-env material: env " + std::to_string(i) +
-                                               " needs E, G, density > 0 and damping constant >= 0");
-    }
-    SR_ON_DEVICE(h);
-    hipStream_t st = (hipStream_t)stream;
-    if (!h->d_env_mat) {   // every row starts at the config's own constants
-        SR_HIP(h, hipMalloc((void**)&h->d_env_mat, N * sizeof(EnvMaterial)));
-        SR_HIP(h, hipHostMalloc((void**)&h->h_env_mat, N * sizeof(EnvMaterial), hipHostMallocDefault));
-        SR_HIP(h, hipEventCreateWithFlags(&h->ev_env_mat, hipEventDisableTiming));
-        const softrod_config& c = h->cfg;
-        const double m0[4] = {c.youngs_modulus, c.shear_modulus, c.density, c.damping_constant};
-        EnvMaterial R0;
-        env_material_row(c, m0, R0);
-        for (size_t i = 0; i < N; ++i) h->h_env_mat[i] = R0;
-        h->S.env_mat = h->d_env_mat;
-        SR_HIP(h, hipMemcpy(h->d_state, &h->S, sizeof(StatePtrs), hipMemcpyHostToDevice));
-    } else {
-        SR_HIP(h, hipEventSynchronize(h->ev_env_mat));   // the previous upload has left the staging buffer
-    }
-    for (size_t i = 0; i < N; ++i)
-        if (!mask || mask[i]) env_material_row(h->cfg, material + 4 * i, h->h_env_mat[i]);
-    SR_HIP(h, hipMemcpyAsync(h->d_env_mat, h->h_env_mat, N * sizeof(EnvMaterial), hipMemcpyHostToDevice, st));
-    SR_HIP(h, hipEventRecord(h->ev_env_mat, st));
-    return SOFTROD_OK;
+    const softrod_config& c = h->cfg;
+    const double own[4] = {c.youngs_modulus, c.shear_modulus, c.density, c.damping_constant};
+    return set_env_table(h, h->env_mat, h->S.env_mat, kOptEnvMaterial, "per-env material: env ", material, own, mask, stream,
+        [](const double* m) -> const char* {
+            if (!(std::isfinite(m[0]) && std::isfinite(m[1]) && std::isfinite(m[2]) && std::isfinite(m[3])))
+                return " has a non-finite value";
+            return m[0] > 0.0 && m[1] > 0.0 && m[2] > 0.0 && m[3] >= 0.0 ? nullptr
+                       : " needs E, G, density > 0 and damping constant >= 0";
+        },
+        [&c](const double* m, EnvMaterial& R) { env_material_row(c, m, R); });
 }
 
 int softrod_set_env_contact(softrod_handle* h, const double* contact, const uint8_t* mask, void* stream) {
     if (!h || !contact) return fail(h, SOFTROD_EINVAL, "null argument");
-    if (const char* why = env_contact_refusal(h)) return fail(h, SOFTROD_EINVAL, why);
-    const size_t N = (size_t)h->cfg.n_envs;
-    for (size_t i = 0; i < N; ++i) {
-        if (mask && !mask[i]) continue;
-        const double* c = contact + 8 * i;
-        for (int j = 0; j < 8; ++j) {
-            if (!std::isfinite(c[j]))
-                return fail(h, SOFTROD_EINVAL, "per-env contact: env " + std::to_string(i) + " has a non-finite value");
-            if (!(c[j] >= 0.0))
-                return fail(h, SOFTROD_EINVAL, "per-env contact: env " + std::to_string(i) +
-                                                   " needs contact_k, contact_nu and every mu >= 0");
-        }
-    }
-    SR_ON_DEVICE(h);
-    hipStream_t st = (hipStream_t)stream;
-    if (!h->d_env_contact) {   // every row starts at the config's own values
-        SR_HIP(h, hipMalloc((void**)&h->d_env_contact, N * sizeof(EnvContact)));
-        SR_HIP(h, hipHostMalloc((void**)&h->h_env_contact, N * sizeof(EnvContact), hipHostMallocDefault));
-        SR_HIP(h, hipEventCreateWithFlags(&h->ev_env_contact, hipEventDisableTiming));
-        const softrod_config& c = h->cfg;
-        const double c0[8] = {c.contact_k, c.contact_nu, c.kinetic_mu[0], c.kinetic_mu[1], c.kinetic_mu[2],
-                              c.static_mu[0], c.static_mu[1], c.static_mu[2]};
-        EnvContact R0;
-        env_contact_row(c0, R0);
-        for (size_t i = 0; i < N; ++i) h->h_env_contact[i] = R0;
-        h->S.env_contact = h->d_env_contact;
-        SR_HIP(h, hipMemcpy(h->d_state, &h->S, sizeof(StatePtrs), hipMemcpyHostToDevice));
-    } else {
-        SR_HIP(h, hipEventSynchronize(h->ev_env_contact));   // the previous upload has left the staging buffer
-    }
-    for (size_t i = 0; i < N; ++i)
-        if (!mask || mask[i]) env_contact_row(contact + 8 * i, h->h_env_contact[i]);
-    SR_HIP(h, hipMemcpyAsync(h->d_env_contact, h->h_env_contact, N * sizeof(EnvContact), hipMemcpyHostToDevice, st));
-    SR_HIP(h, hipEventRecord(h->ev_env_contact, st));
-    return SOFTROD_OK;
+    const softrod_config& c = h->cfg;
+    const double own[8] = {c.contact_k, c.contact_nu, c.kinetic_mu[0], c.kinetic_mu[1], c.kinetic_mu[2],
+                           c.static_mu[0], c.static_mu[1], c.static_mu[2]};
+    return set_env_table(h, h->env_contact, h->S.env_contact, kOptEnvContact, "per-env contact: env ", contact, own, mask, stream,
+        [](const double* v) -> const char* {
+            for (int j = 0; j < 8; ++j) {
+                if (!std::isfinite(v[j])) return " has a non-finite value";
+                if (!(v[j] >= 0.0)) return " needs contact_k, contact_nu and every mu >= 0";
+            }
+            return nullptr;
+        },
+        [](const double* v, EnvContact& R) { env_contact_row(v, R); });
 }
 
 int softrod_set_muscle_layers(softrod_handle* h, const double* ratio_position, const double* strength) {
@@ -1626,10 +1647,9 @@ int softrod_set_action_basis(softrod_handle* h, const double* basis) {
     return SOFTROD_OK;
 }
 
-int softrod_step(softrod_handle* h, const float* actions, float* obs, double* reward,
-                 uint8_t* terminated, uint8_t* truncated, double* aux, void* stream) {
-    if (!h || !actions || !obs || !reward || !terminated || !truncated)
-        return fail(h, SOFTROD_EINVAL, "null argument");
+namespace {
+// what softrod_step and softrod_step_packed need of the handle before they launch
+int step_preconditions(softrod_handle* h) {
     if ((h->cfg.features & SOFTROD_FEAT_REST_KAPPA_ACTION) && !h->basis_set)
         return fail(h, SOFTROD_EINVAL, "softrod_set_action_basis must be called before softrod_step");
     if ((h->cfg.features & SOFTROD_FEAT_SPLINE_MUSCLE_TORQUES) && !h->spline_set)
@@ -1638,6 +1658,15 @@ int softrod_step(softrod_handle* h, const float* actions, float* obs, double* re
         return fail(h, SOFTROD_EINVAL, "env_kind NONE has no step epilogue; use softrod_substeps");
     if ((h->cfg.features & SOFTROD_FEAT_COOMM_MUSCLES) && !h->muscles_set)
         return fail(h, SOFTROD_EINVAL, "softrod_set_muscle_layers must be called before softrod_step");
+    return SOFTROD_OK;
+}
+}  // namespace
+
+int softrod_step(softrod_handle* h, const float* actions, float* obs, double* reward,
+                 uint8_t* terminated, uint8_t* truncated, double* aux, void* stream) {
+    if (!h || !actions || !obs || !reward || !terminated || !truncated)
+        return fail(h, SOFTROD_EINVAL, "null argument");
+    if (const int rc = step_preconditions(h)) return rc;
     SR_ON_DEVICE(h);
     return launch_step(h, actions, obs, reward, terminated, truncated, aux, h->cfg.n_substeps, 1, 0,
                        (hipStream_t)stream);
@@ -1645,14 +1674,7 @@ int softrod_step(softrod_handle* h, const float* actions, float* obs, double* re
 
 int softrod_step_packed(softrod_handle* h, const float* actions, float* packed, double* aux, void* stream) {
     if (!h || !actions || !packed) return fail(h, SOFTROD_EINVAL, "null argument");
-    if (h->cfg.env_kind == SOFTROD_ENV_NONE)
-        return fail(h, SOFTROD_EINVAL, "env_kind NONE has no step epilogue; use softrod_substeps");
-    if ((h->cfg.features & SOFTROD_FEAT_REST_KAPPA_ACTION) && !h->basis_set)
-        return fail(h, SOFTROD_EINVAL, "softrod_set_action_basis must be called before softrod_step");
-    if ((h->cfg.features & SOFTROD_FEAT_SPLINE_MUSCLE_TORQUES) && !h->spline_set)
-        return fail(h, SOFTROD_EINVAL, "softrod_set_spline_table must be called before softrod_step");
-    if ((h->cfg.features & SOFTROD_FEAT_COOMM_MUSCLES) && !h->muscles_set)
-        return fail(h, SOFTROD_EINVAL, "softrod_set_muscle_layers must be called before softrod_step");
+    if (const int rc = step_preconditions(h)) return rc;
     SR_ON_DEVICE(h);
     return launch_step(h, actions, packed, nullptr, nullptr, nullptr, aux, h->cfg.n_substeps, 1, 1,
                        (hipStream_t)stream);
@@ -1909,44 +1931,21 @@ int softrod_last_kernel_ms(softrod_handle* h, float* ms) {
 
 const char* softrod_last_error(softrod_handle* h) { return h ? h->err.c_str() : g_err.c_str(); }
 
-// Mirrors launch_step's choice (the env.step form: epilogue = 1).
+// What select_step chooses for env.step (epilogue = 1), by its row's label.
 const char* softrod_kernel_tier(softrod_handle* h) {
     if (!h) return "";
-    const bool zup = (h->P.features & kFeatPlaneZup) != 0;
-    const unsigned f = h->cfg.features;
-    const int e = h->cfg.env_kind;
-    std::string t;
-    if (is_mocto(h)) {
-        t = std::string("softrod_mocto_action_kernel | softrod_octo_step_kernel<muscle arms,") + std::to_string(h->nw) +
-            (h->nw == 1 ? " wave" : " waves") + ",1 env/wg,taper> | softrod_mocto_epilogue_kernel";
-    } else if (is_octo(h) && is_pull(h)) {
-        t = "softrod_octo_step_kernel<ArmPullWeight,1 wave,1 env/wg,taper>";
-    } else if (is_octo(h)) {
-        if (zup && h->nw == 2)
-            t = "softrod_octo_step_kernel<zup,2 waves,4 envs/wg>";
-        else
-            t = std::string("softrod_octo_step_kernel<") + (zup ? "zup," : "general plane,") +
-                (h->nw <= 2 ? "2" : "8") + " waves max,1 env/wg>";
-    } else if (h->window_refresh > 0) {
-        t = std::string("softrod_step_window_kernel<ArmSingle,") + (h->window_paired ? "4 rods/wg" : "1 rod/wg,s_barrier") +
-            "> refresh=" + std::to_string(h->window_refresh) + " + softrod_step_fast_kernel<ArmSingle,epl=2> epilogue";
-    } else if (h->cfg.math_mode == SOFTROD_MATH_FAST) {
-        const char* spec = "runtime mask";
-        if (h->tapered) {
-            if (f == SOFTROD_FEATURES_ARM_SINGLE && e == SOFTROD_ENV_ARM_SINGLE && zup) spec = "ArmSingle";
-            else if (f == kFeaturesTaperedSuckerArm && e == SOFTROD_ENV_NONE) spec = "damped sucker arm";
-            else if (f == SOFTROD_FEATURES_ARM_PUSH && e == SOFTROD_ENV_ARM_PUSH) spec = "ArmPush";
-        } else if (f == SOFTROD_FEATURES_SOFTPENDULUM && e == SOFTROD_ENV_SOFTPENDULUM) spec = "SoftPendulum";
-        else if (f == SOFTROD_FEATURES_SOFTPENDULUM3D && e == SOFTROD_ENV_SOFTPENDULUM3D) spec = "SoftPendulum3D";
-        else if (f == SOFTROD_FEATURES_ARM_SINGLE && e == SOFTROD_ENV_ARM_SINGLE && zup) spec = "ArmSingle";
-        else if (f == SOFTROD_FEATURES_SOFT_ARM && e == SOFTROD_ENV_SOFT_ARM) spec = "SoftArm";
-        else if (f == kFeaturesMuscleRod && e == SOFTROD_ENV_NONE) spec = "muscle rod";
-        t = std::string("softrod_step_fast_kernel<") + spec + ",epl=" + std::to_string(h->epl) +
-            (h->tapered ? ",taper>" : ">");
-    } else
-        t = "softrod_step_libm_kernel";
-    if (h->d_env_mat) t += ",env material";
-    if (h->d_env_contact) t += ",env contact";
+    const StepChoice c = select_step(h);
+    std::string t = c.row ? c.row->label : std::string("none: ") + c.why;
+    auto fill = [&t](const char* token, const std::string& with) {
+        const size_t at = t.find(token);
+        if (at != std::string::npos) t.replace(at, std::strlen(token), with);
+    };
+    fill("{waves}", std::to_string(h->nw) + (h->nw == 1 ? " wave" : " waves"));
+    fill("{refresh}", std::to_string(h->window_refresh));
+    if (c.row && c.row->windowed)
+        if (const StepRow* after = select_step(h, 0).row) t += std::string(" + ") + after->label + " epilogue";
+    if (h->env_mat.dev) t += ",env material";
+    if (h->env_contact.dev) t += ",env contact";
     h->tier = t;
     return h->tier.c_str();
 }
@@ -1957,13 +1956,11 @@ int softrod_destroy(softrod_handle* h) {
     (void)hipDeviceSynchronize();
     autoreset_release(h);
     void* bufs[] = {h->S.pos, h->S.vel, h->S.dir, h->S.omg, h->S.tan, h->S.time, h->S.bc,
-                    h->S.ctrl, h->S.kap, h->S.rkap, h->S.envmem, h->S.prev_action, h->S.head, h->d_params, h->d_state, h->d_time_tab, h->d_mat, h->d_sucker, h->d_sucker_idx, h->d_aux, h->d_prev_kappa, h->d_mact, h->d_mtab, h->d_basis, h->d_spline, h->d_init, h->d_mask, h->d_ticket, h->d_env_mat, h->d_env_contact};
+                    h->S.ctrl, h->S.kap, h->S.rkap, h->S.envmem, h->S.prev_action, h->S.head, h->d_params, h->d_state, h->d_time_tab, h->d_mat, h->d_sucker, h->d_sucker_idx, h->d_aux, h->d_prev_kappa, h->d_mact, h->d_mtab, h->d_basis, h->d_spline, h->d_init, h->d_mask, h->d_ticket};
     for (void* p : bufs) (void)hipFree(p);
     if (h->h_init) (void)hipHostFree(h->h_init);
-    if (h->h_env_mat) (void)hipHostFree(h->h_env_mat);
-    if (h->ev_env_mat) (void)hipEventDestroy(h->ev_env_mat);
-    if (h->h_env_contact) (void)hipHostFree(h->h_env_contact);
-    if (h->ev_env_contact) (void)hipEventDestroy(h->ev_env_contact);
+    h->env_mat.release();
+    h->env_contact.release();
     if (h->h_mask) (void)hipHostFree(h->h_mask);
     for (hipEvent_t e : h->ev_start) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->ev_stop) (void)hipEventDestroy(e);
