@@ -31,8 +31,7 @@ import numpy as np
 
 from .. import _capi
 from ..spaces import Box, Discrete
-from .base import GymEnv as _GymEnv
-from .base import VecRodEnvBase
+from .base import SingleRodEnv, VecRodEnvBase
 
 PARITY_LABEL = "parity-unpinned (COOMM muscle law restated from the published model; not on disk)"
 
@@ -75,11 +74,7 @@ class VecArmPushEnv(VecRodEnvBase):
                            mode=mode, math_mode=math_mode, early_termination=config_early_termination, n_elems=n_elems)
         super().__init__(num_envs, cfg, render_mode=render_mode, config_generate_video=config_generate_video,
                          device=device, numpy_output=numpy_output, autoreset=autoreset, backend=backend)
-        self.final_time = final_time
-        self.time_step = time_step
-        self.total_steps = int(self.final_time / self.time_step)
-        self.recording_fps = recording_fps
-        self.step_skip = int(1.0 / (recording_fps * time_step))
+        self._set_timing(final_time, time_step, recording_fps)
         self.n_elem = int(cfg.n_elem)                   # :88
         self.mode = int(cfg.arm_push_mode)
         self.config_early_termination = bool(config_early_termination)
@@ -137,12 +132,14 @@ class VecArmPullWeightEnv(VecArmPushEnv):
         return _capi.arm_pull_weight_config(num_envs, **kw)
 
 
-class ArmPushEnv(_GymEnv):
+class ArmPushEnv(SingleRodEnv):
     """Drop-in for gym_softrobot's ArmPushEnv (octopus/arm_push_env.py:52-347), N = 1.  PARITY UNPINNED
     (module docstring)."""
 
     metadata = {"render_modes": ["rgb_array", "human"], "render_fps": 40}
     parity_label = PARITY_LABEL
+    shares_rng = False                                  # _build draws nothing from the RNG
+    _make_vec = VecArmPushEnv                           # what builds the one-env batch from __init__'s keywords
 
     def __init__(
         self,
@@ -159,17 +156,10 @@ class ArmPushEnv(_GymEnv):
         backend=None,
         n_elems: int = 40,
     ):
-        super().__init__()
-        if render_mode not in {None, *self.metadata["render_modes"]}:
-            raise ValueError(f"Unsupported render mode: {render_mode}")
-        self.render_mode = render_mode
-        self._vec = self._make_vec(final_time, time_step, recording_fps, mode, config_generate_video,
-                                   config_early_termination, device, math_mode, backend, n_elems)
-        self.final_time = final_time
-        self.time_step = time_step
-        self.total_steps = self._vec.total_steps
-        self.recording_fps = recording_fps
-        self.step_skip = self._vec.step_skip
+        super().__init__(render_mode, self._make_vec, final_time=final_time, time_step=time_step,
+                         recording_fps=recording_fps, mode=mode, config_generate_video=config_generate_video,
+                         config_early_termination=config_early_termination, render_mode=None, device=device,
+                         math_mode=math_mode, backend=backend, n_elems=n_elems)
         self.n_elem = self._vec.n_elem
         self.mode = self._vec.mode
         if self.mode == 0:
@@ -182,53 +172,21 @@ class ArmPushEnv(_GymEnv):
         self._prev_action = np.zeros(list(self.action_space.shape), dtype=self.action_space.dtype)
         self.config_generate_video = config_generate_video
         self.config_early_termination = config_early_termination
-        self.time = np.float64(0.0)
 
-    @staticmethod
-    def _make_vec(final_time, time_step, recording_fps, mode, config_generate_video, config_early_termination,
-                  device, math_mode, backend, n_elems):
-        return VecArmPushEnv(1, final_time, time_step, recording_fps, mode, config_generate_video,
-                             config_early_termination, None, device=device, math_mode=math_mode,
-                             numpy_output=True, backend=backend, n_elems=n_elems)
-
-    def reset(self, *, seed: Optional[int] = None, options: Optional[dict] = None):
-        super().reset(seed=seed)
-        obs, _ = self._vec.reset()
-        self.time = np.float64(0.0)
-        return np.asarray(obs[0], dtype=np.float32).copy(), {}
-
-    def get_state(self):
-        obs = self._vec.backend.observe(None)
-        return np.asarray(obs[0].cpu().numpy() if hasattr(obs, "cpu") else obs[0], dtype=np.float32).copy()
-
-    def step(self, action):
+    def _action_row(self, action):
         if self.mode == 0:
             if action not in (0, 1):
                 raise NotImplementedError("Action must be 1 or 0")     # arm_push_env.py:267
-            a = np.array([[float(action)]], np.float32)
-        else:
-            a = np.asarray(action, dtype=np.float32).reshape(1, 2)
-        obs, reward, term, trunc, infos = self._vec.step(a)
+            return np.array([[float(action)]], np.float32)
+        return super()._action_row(action)
+
+    def _book_reset(self):
+        self.time = np.float64(0.0)                     # the reference's ArmPushEnv keeps no step counter
+
+    def _book_step(self, action, row, infos, terminated):
         self._prev_action = action
         self.time = np.float64(infos["time"][0])
-        return (
-            np.asarray(obs[0], dtype=np.float32).copy(),
-            float(reward[0]),
-            bool(term[0]),
-            bool(trunc[0]),
-            {"time": self.time, "TimeLimit.truncated": bool(infos["TimeLimit.truncated"][0])},
-        )
-
-    def render(self):
-        from ..render import render_env
-
-        return render_env(self)
-
-    def close(self):
-        from ..render import close_env
-
-        close_env(self)
-        self._vec.close()
+        return {"time": self.time, "TimeLimit.truncated": bool(infos["TimeLimit.truncated"][0])}
 
 
 class ArmPullWeightEnv(ArmPushEnv):
@@ -240,9 +198,5 @@ class ArmPullWeightEnv(ArmPushEnv):
         super().__init__(time_step=2.5e-5, **kwargs)        # :518
 
     @staticmethod
-    def _make_vec(final_time, time_step, recording_fps, mode, config_generate_video, config_early_termination,
-                  device, math_mode, backend, n_elems):
-        return VecArmPullWeightEnv(1, final_time=final_time, recording_fps=recording_fps, mode=mode,
-                                   config_generate_video=config_generate_video,
-                                   config_early_termination=config_early_termination, render_mode=None, device=device,
-                                   math_mode=math_mode, numpy_output=True, backend=backend, n_elems=n_elems)
+    def _make_vec(num_envs, *, time_step, **kwargs):        # the batch class sets its own time_step, as :518 does
+        return VecArmPullWeightEnv(num_envs, **kwargs)

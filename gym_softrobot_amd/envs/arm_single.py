@@ -17,8 +17,7 @@ import numpy as np
 
 from .. import _capi
 from ..spaces import Box
-from .base import GymEnv as _GymEnv
-from .base import SingleEnvContact, SingleEnvMaterial, VecRodEnvBase
+from .base import SingleEnvContact, SingleEnvMaterial, SingleEnvSummary, SingleRodEnv, VecRodEnvBase
 
 
 class VecArmSingleEnv(VecRodEnvBase):
@@ -59,11 +58,7 @@ class VecArmSingleEnv(VecRodEnvBase):
         super().__init__(num_envs, cfg, render_mode=render_mode,
                          config_generate_video=config_generate_video, device=device,
                          numpy_output=numpy_output, autoreset=autoreset, backend=backend)
-        self.final_time = final_time
-        self.time_step = time_step
-        self.total_steps = int(self.final_time / self.time_step)
-        self.recording_fps = recording_fps
-        self.step_skip = int(1.0 / (recording_fps * time_step))
+        self._set_timing(final_time, time_step, recording_fps)
         self.control_penalty_coeff = control_penalty_coeff
         self.n_elems = n_elems
         self.n_seg = n_elems - 1
@@ -90,10 +85,12 @@ class VecArmSingleEnv(VecRodEnvBase):
         self.backend.reset_straight(start, direction, normal, mask.astype(np.uint8) if use_mask else None)
 
 
-class ArmSingleEnv(SingleEnvMaterial, SingleEnvContact, _GymEnv):
-    """Drop-in for gym_softrobot's ArmSingleEnv (octopus/arm_single_env.py:41-316), N = 1."""
+class ArmSingleEnv(SingleEnvMaterial, SingleEnvContact, SingleEnvSummary, SingleRodEnv):
+    """Drop-in for gym_softrobot's ArmSingleEnv (octopus/arm_single_env.py:41-316), N = 1; get_state :186-224,
+    summary :116-133."""
 
     metadata = {"render_modes": ["rgb_array", "human"], "render_fps": 20}
+    shares_rng = False                                # build_arm draws nothing from the RNG
 
     def __init__(
         self,
@@ -111,20 +108,9 @@ class ArmSingleEnv(SingleEnvMaterial, SingleEnvContact, _GymEnv):
         math_mode: int = _capi.MATH_FAST,
         backend=None,
     ):
-        super().__init__()
-        if render_mode not in {None, *self.metadata["render_modes"]}:
-            raise ValueError(f"Unsupported render mode: {render_mode}")
-        self.render_mode = render_mode
-        self._vec = VecArmSingleEnv(
-            1, final_time, time_step, recording_fps, n_elems, n_action, control_penalty_coeff,
-            config_generate_video, policy_mode, None, device=device, math_mode=math_mode,
-            numpy_output=True, backend=backend,
-        )
-        self.final_time = final_time
-        self.time_step = time_step
-        self.total_steps = self._vec.total_steps
-        self.recording_fps = recording_fps
-        self.step_skip = self._vec.step_skip
+        super().__init__(render_mode, VecArmSingleEnv, final_time, time_step, recording_fps, n_elems, n_action,
+                         control_penalty_coeff, config_generate_video, policy_mode, None, device=device,
+                         math_mode=math_mode, backend=backend)
         self.control_penalty_coeff = control_penalty_coeff
         self.n_elems = n_elems
         self.n_seg = n_elems - 1
@@ -136,67 +122,3 @@ class ArmSingleEnv(SingleEnvMaterial, SingleEnvContact, _GymEnv):
         self.kappa_range = [-49.33508476187419, 49.33545827754751]
         self.kappa_rate_range = [-21.063520620377012, 24.664591289161944]
         self._target = np.array([1.0, 0.0])
-        self.time = np.float64(0.0)
-        self.counter = 0
-
-    def reset(self, *, seed: Optional[int] = None, options: Optional[dict] = None):
-        super().reset(seed=seed)
-        obs, _ = self._vec.reset()
-        self.time = np.float64(0.0)
-        self.counter = 0
-        return np.asarray(obs[0], dtype=np.float32).copy(), {}
-
-    def step(self, action):
-        a = np.asarray(action, dtype=np.float32).reshape(1, 7)
-        obs, reward, term, trunc, infos = self._vec.step(a)
-        self.time = np.float64(infos["time"][0])
-        self.counter += 1
-        return (
-            np.asarray(obs[0], dtype=np.float32).copy(),
-            float(reward[0]),
-            bool(term[0]),
-            bool(trunc[0]),
-            {"time": self.time, "TimeLimit.truncated": bool(infos["TimeLimit.truncated"][0])},
-        )
-
-    def get_state(self):
-        """Current observation (arm_single_env.py:186-224); like the reference's, a call moves the
-        `prev_kappa_state` / `prev_com_state` the rate entries are taken against."""
-        obs = self._vec.backend.observe(None)
-        return np.asarray(obs[0].cpu().numpy() if hasattr(obs, "cpu") else obs[0], dtype=np.float32).copy()
-
-    def summary(self):
-        """As the reference's summary() (octopus/arm_single_env.py:116-133)."""
-        print(
-            f"""
-        {self.final_time=}
-        {self.time_step=}
-        {self.total_steps=}
-        {self.step_skip=}
-        simulation time per action: {1.0/self.step_skip=}
-        max number of action per episode: {self.total_steps / self.step_skip}
-
-        {self.n_elems=}
-        {self.action_space=}
-        {self.observation_space=}
-        {self.reward_range=}
-        """
-        )
-
-    def save_data(self, filename_video, fps):
-        """The reference renders `rod_parameters_dict` to a video here (arm_single_env.py); drawing is out of
-        scope: the data is in `rod_parameters_dict`, nothing is written."""
-        if getattr(self._vec, "config_generate_video", False):
-            raise NotImplementedError("video generation is outside the hot path; use rod_parameters_dict")
-
-    def render(self):
-        """None without a render mode; an (H, W, 3) uint8 frame for "rgb_array" (render.py)."""
-        from ..render import render_env
-
-        return render_env(self)
-
-    def close(self):
-        from ..render import close_env
-
-        close_env(self)
-        self._vec.close()

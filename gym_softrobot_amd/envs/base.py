@@ -78,6 +78,157 @@ class SingleEnvContact:
                 "kinetic_mu": c["kinetic_mu"][0].copy(), "static_mu": c["static_mu"][0].copy()}
 
 
+class SingleRodEnv(GymEnv):
+    """The N = 1 drop-in classes' common shell: one env of the reference's Gymnasium surface over a one-env batch
+    `_vec` (numpy_output=True).  reset / step / get_state / render / close / save_data live here, once; a class adds
+    its constructor (the reference's keywords, spaces and attributes) and overrides the hooks it needs:
+
+      _action_row(action)   the caller's action -> the batch's (1, action_dim) float32 row
+      _obs(rows)            the batch's (1, obs_dim) NumPy observation -> what the class hands back
+      _book_reset()         the host counters of a fresh episode (also sets them up at construction)
+      _book_step(...)       the host counters after a step; returns step's `info`
+
+    `shares_rng`: reset hands env.np_random to the batch, so what the env's build draws advances the env's own stream
+    (soft_pendulum.py:114,123); False where the build draws nothing.  `obs_dtype`: the observation space's dtype."""
+
+    shares_rng = True
+    obs_dtype = np.float32
+    mirrored = ("final_time", "time_step", "total_steps", "recording_fps", "step_skip")   # the batch's, kept on the env too
+
+    def __init__(self, render_mode, vec_class, /, *args, **kwargs):
+        """`vec_class(1, *args, numpy_output=True, **kwargs)` is the one-env batch."""
+        super().__init__()
+        if render_mode not in {None, *self.metadata["render_modes"]}:
+            raise ValueError(f"Unsupported render mode: {render_mode}")
+        self.render_mode = render_mode
+        self._vec = vec_class(1, *args, numpy_output=True, **kwargs)
+        self._book_reset()
+        for k in self.mirrored:
+            setattr(self, k, getattr(self._vec, k))
+
+    # -- hooks ---------------------------------------------------------------------
+    def _action_row(self, action):
+        return np.asarray(action, dtype=np.float32).reshape(1, self._vec.action_dim)
+
+    def _obs(self, rows):
+        return np.array(rows[0], dtype=self.obs_dtype)        # always the caller's own copy
+
+    def _book_reset(self) -> None:
+        self.time = np.float64(0.0)
+        self.counter = 0
+
+    def _book_step(self, action, row, infos, terminated) -> Dict[str, Any]:
+        self.time = np.float64(infos["time"][0])
+        self.counter += 1
+        return {"time": self.time, "TimeLimit.truncated": bool(infos["TimeLimit.truncated"][0])}
+
+    # -- API -----------------------------------------------------------------------
+    def reset(self, *, seed: Optional[int] = None, options: Optional[dict] = None):
+        super().reset(seed=seed)
+        if self.shares_rng:
+            self._vec._rngs[0] = self.np_random
+        obs, _ = self._vec.reset(seed=None)
+        self._book_reset()
+        return self._obs(obs), {}
+
+    def step(self, action):
+        row = self._action_row(action)
+        obs, reward, term, trunc, infos = self._vec.step(row)
+        terminated = bool(term[0])
+        info = self._book_step(action, row, infos, terminated)
+        return self._obs(obs), float(reward[0]), terminated, bool(trunc[0]), info
+
+    def get_state(self):
+        """Current observation (the reference's get_state).  ArmSingleEnv: like the reference's
+        (arm_single_env.py:186-224), a call moves the `prev_kappa_state` / `prev_com_state` the rate entries are
+        taken against."""
+        obs = self._vec.backend.observe(None)
+        return self._obs(obs.cpu().numpy() if hasattr(obs, "cpu") else obs)
+
+    def save_data(self, filename_video, fps):
+        """The reference renders `rod_parameters_dict` to a video here (soft_pendulum.py:253-256, flat_env.py:410-420);
+        drawing is out of scope: the data is in `rod_parameters_dict`, nothing is written."""
+        if getattr(self._vec, "config_generate_video", False):
+            raise NotImplementedError("video generation is outside the hot path; use rod_parameters_dict")
+
+    def render(self):
+        """None without a render mode; an (H, W, 3) uint8 frame for "rgb_array" (render.py)."""
+        from ..render import render_env
+
+        return render_env(self)
+
+    def close(self):
+        from ..render import close_env
+
+        close_env(self)
+        self._vec.close()
+
+
+class SingleEnvSummary:
+    """summary() of the two single envs whose reference class has one."""
+
+    def summary(self):
+        """As the reference's summary() (octopus/arm_single_env.py:116-133, octopus/flat_env.py:153-170)."""
+        print(
+            f"""
+        {self.final_time=}
+        {self.time_step=}
+        {self.total_steps=}
+        {self.step_skip=}
+        simulation time per action: {1.0/self.step_skip=}
+        max number of action per episode: {self.total_steps / self.step_skip}
+
+        {self.n_elems=}
+        {self.action_space=}
+        {self.observation_space=}
+        {self.reward_range=}
+        """
+        )
+
+
+def _as_numpy(v) -> np.ndarray:
+    """A NumPy view or copy of a scalar, a sequence, an array or a CPU / device torch tensor."""
+    if hasattr(v, "detach"):
+        v = v.detach().cpu().numpy()
+    return np.asarray(v)
+
+
+def _per_env(v, n: int, name: str) -> Optional[np.ndarray]:
+    """A scalar or an (n,) array -> (n,) float64; None stays None."""
+    if v is None:
+        return None
+    a = _as_numpy(v).astype(np.float64)
+    if a.ndim == 0:
+        a = np.full(n, float(a))
+    if a.shape != (n,):
+        raise ValueError(f"{name}: expected a scalar or shape ({n},), got {a.shape}")
+    return a
+
+
+def _per_env3(v, n: int, name: str) -> Optional[np.ndarray]:
+    """A scalar, a (3,) or an (n, 3) array -> (n, 3) float64; None stays None."""
+    if v is None:
+        return None
+    a = _as_numpy(v).astype(np.float64)
+    if a.ndim == 0:
+        a = np.full((n, 3), float(a))
+    elif a.shape == (3,):
+        a = np.tile(a, (n, 1))
+    if a.shape != (n, 3):
+        raise ValueError(f"{name}: expected a scalar, shape (3,) or ({n}, 3), got {a.shape}")
+    return a
+
+
+def _env_mask(mask, n: int) -> np.ndarray:
+    """None (every env) or an (n,) mask -> (n,) bool."""
+    if mask is None:
+        return np.ones(n, bool)
+    sel = _as_numpy(mask).astype(bool).reshape(-1)
+    if sel.shape != (n,):
+        raise ValueError(f"mask: expected shape ({n},), got {sel.shape}")
+    return sel
+
+
 def time_table(cfg: _capi.SoftrodConfig, n_steps: int) -> np.ndarray:
     """float64 simulated time after k env.steps, accumulated exactly as
     `self.time = self.do_step(self.simulator, self.time, self.time_step)` does
@@ -157,6 +308,14 @@ class VecRodEnvBase:
         # `record_envs` set before reset).
         self.record_envs = (0,)
         self.recorder = None
+
+    def _set_timing(self, final_time, time_step, recording_fps) -> None:
+        """The reference's timing attributes (soft_pendulum.py:74-78), for the envs whose constructor takes them."""
+        self.final_time = final_time
+        self.time_step = time_step
+        self.total_steps = int(self.final_time / self.time_step)
+        self.recording_fps = recording_fps
+        self.step_skip = int(1.0 / (recording_fps * time_step))
 
     spec = None      # set by gymnasium.make_vec (`env.unwrapped.spec = ...`)
 
@@ -464,31 +623,11 @@ class VecRodEnvBase:
         if why is not None:
             raise NotImplementedError(why)
         n = self.num_envs
-
-        def col(v, name):
-            if v is None:
-                return None
-            if hasattr(v, "detach"):
-                v = v.detach().cpu().numpy()
-            a = np.asarray(v, dtype=np.float64)
-            if a.ndim == 0:
-                a = np.full(n, float(a))
-            if a.shape != (n,):
-                raise ValueError(f"{name}: expected a scalar or shape ({n},), got {a.shape}")
-            return a
-
-        cols = [col(v, k) for v, k in zip((youngs_modulus, shear_modulus, density, damping_constant),
-                                          self._MATERIAL_KEYS)]
+        cols = [_per_env(v, n, k) for v, k in zip((youngs_modulus, shear_modulus, density, damping_constant),
+                                                  self._MATERIAL_KEYS)]
         if cols[0] is not None and cols[1] is None:
             cols[1] = cols[0] / 3.0
-        if mask is None:
-            sel = np.ones(n, bool)
-        else:
-            if hasattr(mask, "detach"):
-                mask = mask.detach().cpu().numpy()
-            sel = np.asarray(mask, dtype=bool).reshape(-1)
-            if sel.shape != (n,):
-                raise ValueError(f"mask: expected shape ({n},), got {sel.shape}")
+        sel = _env_mask(mask, n)
         m = be.env_material()
         for j, c in enumerate(cols):
             if c is not None:
@@ -537,42 +676,14 @@ class VecRodEnvBase:
         if why is not None:
             raise NotImplementedError(why)
         n = self.num_envs
-
-        def arr(v):
-            if hasattr(v, "detach"):
-                v = v.detach().cpu().numpy()
-            return np.asarray(v)
-
-        def col(v, name):
-            if v is None:
-                return None
-            a = arr(v).astype(np.float64)
-            if a.ndim == 0:
-                a = np.full(n, float(a))
-            if a.shape != (n,):
-                raise ValueError(f"{name}: expected a scalar or shape ({n},), got {a.shape}")
-            return a
-
-        def mu3(v, name):
-            if v is None:
-                return None
-            a = arr(v).astype(np.float64)
-            if a.ndim == 0:
-                a = np.full((n, 3), float(a))
-            elif a.shape == (3,):
-                a = np.tile(a, (n, 1))
-            if a.shape != (n, 3):
-                raise ValueError(f"{name}: expected a scalar, shape (3,) or ({n}, 3), got {a.shape}")
-            return a
-
-        k, nu = col(contact_k, "contact_k"), col(contact_nu, "contact_nu")
-        kin, stat = mu3(kinetic_mu, "kinetic_mu"), mu3(static_mu, "static_mu")
+        k, nu = _per_env(contact_k, n, "contact_k"), _per_env(contact_nu, n, "contact_nu")
+        kin, stat = _per_env3(kinetic_mu, n, "kinetic_mu"), _per_env3(static_mu, n, "static_mu")
         if friction_multiplier is not None or friction_symmetry is not None:
             if kin is not None or stat is not None:
                 raise ValueError("friction_multiplier / friction_symmetry recompute both mu arrays: "
                                  "not together with kinetic_mu / static_mu")
-            mult = col(1.0 if friction_multiplier is None else friction_multiplier, "friction_multiplier")
-            sym = arr(False if friction_symmetry is None else friction_symmetry)
+            mult = _per_env(1.0 if friction_multiplier is None else friction_multiplier, n, "friction_multiplier")
+            sym = _as_numpy(False if friction_symmetry is None else friction_symmetry)
             if sym.dtype.kind not in "bui":
                 raise ValueError(f"friction_symmetry: expected a bool or ({n},) bools, got dtype {sym.dtype}")
             sym = np.broadcast_to(sym.astype(bool), (n,)) if sym.ndim == 0 else sym.astype(bool)
@@ -583,14 +694,7 @@ class VecRodEnvBase:
                 kin[i], stat[i] = _capi.friction_mu_arrays(self.cfg, float(mult[i]), bool(sym[i]))
         elif kin is not None and stat is None:
             stat = 2 * kin
-        if mask is None:
-            sel = np.ones(n, bool)
-        else:
-            if hasattr(mask, "detach"):
-                mask = mask.detach().cpu().numpy()
-            sel = np.asarray(mask, dtype=bool).reshape(-1)
-            if sel.shape != (n,):
-                raise ValueError(f"mask: expected shape ({n},), got {sel.shape}")
+        sel = _env_mask(mask, n)
         c = be.env_contact()
         for sl, v in ((slice(0, 1), k), (slice(1, 2), nu), (slice(2, 5), kin), (slice(5, 8), stat)):
             if v is not None:

@@ -22,8 +22,7 @@ import numpy as np
 from .. import _capi
 from ..spaces import Box
 from .arm_push import PARITY_LABEL
-from .base import GymEnv as _GymEnv
-from .base import VecRodEnvBase
+from .base import SingleRodEnv, VecRodEnvBase
 
 
 class _VecMuscleOctopusEnv(VecRodEnvBase):
@@ -54,11 +53,7 @@ class _VecMuscleOctopusEnv(VecRodEnvBase):
                                           recording_fps=recording_fps, n_elems=n_elems, math_mode=math_mode)
         super().__init__(num_envs, cfg, render_mode=render_mode, config_generate_video=False, device=device,
                          numpy_output=numpy_output, autoreset=autoreset, backend=backend)
-        self.final_time = final_time
-        self.time_step = time_step
-        self.total_steps = int(self.final_time / self.time_step)
-        self.recording_fps = recording_fps
-        self.step_skip = int(1.0 / (recording_fps * time_step))
+        self._set_timing(final_time, time_step, recording_fps)
         self.n_arm = int(cfg.n_arm)
         self.n_elems = n_elems
         self.n_seg = n_elems - 1
@@ -155,7 +150,7 @@ class VecReachEnv(_VecMuscleOctopusEnv):
         return dict(n_actions=self.n_action, n_agents=8)
 
 
-class _MuscleOctopusEnv(_GymEnv):
+class _MuscleOctopusEnv(SingleRodEnv):
     parity_label = PARITY_LABEL
     metadata = {"render_modes": ["rgb_array"], "render_fps": 25}
     vec_class = None
@@ -163,24 +158,17 @@ class _MuscleOctopusEnv(_GymEnv):
     def __init__(self, final_time: Optional[float] = None, time_step: float = 5.0e-5, recording_fps: int = 25,
                  n_elems: int = 20, render_mode: Optional[str] = None, *, device: int = 0,
                  math_mode: int = _capi.MATH_FAST, backend=None, **kw):
-        super().__init__()
-        if render_mode not in {None, *self.metadata["render_modes"]}:
-            raise ValueError(f"Unsupported render mode: {render_mode}")
-        self.render_mode = render_mode
         final_time = self.vec_class.default_final_time if final_time is None else final_time
-        self._vec = self.vec_class(1, final_time, time_step, recording_fps, n_elems, render_mode=None, device=device,
-                                   math_mode=math_mode, numpy_output=True, backend=backend, **kw)
+        # the env-owned stream is the batch's: ReachEnv draws its target from it, CrawlEnv its final_time
+        super().__init__(render_mode, self.vec_class, final_time, time_step, recording_fps, n_elems, render_mode=None,
+                         device=device, math_mode=math_mode, backend=backend, **kw)
         v = self._vec
-        self.final_time, self.time_step, self.recording_fps = final_time, time_step, recording_fps
-        self.total_steps, self.step_skip = v.total_steps, v.step_skip
         self.n_arm, self.n_elems, self.n_seg, self.n_action = v.n_arm, v.n_elems, v.n_seg, v.n_action
         self.action_space = Box(0.0, 1.0, shape=(self.n_arm * self.n_action,), dtype=np.float32)
         self._observation_size = (v.obs_dim,)
         self.observation_space = Box(-np.inf, np.inf, shape=self._observation_size, dtype=np.float32)
         self.reward_range = 100.0
         self._prev_action = np.zeros(list(self.action_space.shape), dtype=self.action_space.dtype)
-        self.time = np.float64(0.0)
-        self.counter = 0
 
     @property
     def _target(self):
@@ -190,37 +178,9 @@ class _MuscleOctopusEnv(_GymEnv):
     def get_env_info(self):
         return self._vec.get_env_info()
 
-    def reset(self, *, seed: Optional[int] = None, options: Optional[dict] = None):
-        super().reset(seed=seed)
-        self._vec._rngs[0] = self.np_random               # env-owned stream (ReachEnv draws its target from it)
-        obs, _ = self._vec.reset(seed=None)
-        self.time = np.float64(0.0)
-        self.counter = 0
-        return np.asarray(obs[0], dtype=np.float32).copy(), {}
-
-    def get_state(self):
-        obs = self._vec.backend.observe(None)
-        return np.asarray(obs[0].cpu().numpy() if hasattr(obs, "cpu") else obs[0], dtype=np.float32).copy()
-
-    def step(self, action):
-        a = np.asarray(action, dtype=np.float32).reshape(1, self.n_arm * self.n_action)
-        obs, reward, term, trunc, infos = self._vec.step(a)
-        self._prev_action = np.reshape(a[0], [self.n_arm, self.n_action])
-        self.time = np.float64(infos["time"][0])
-        self.counter += 1
-        return (np.asarray(obs[0], dtype=np.float32).copy(), float(reward[0]), bool(term[0]), bool(trunc[0]),
-                {"time": self.time, "TimeLimit.truncated": bool(infos["TimeLimit.truncated"][0])})
-
-    def render(self):
-        from ..render import render_env
-
-        return render_env(self)
-
-    def close(self):
-        from ..render import close_env
-
-        close_env(self)
-        self._vec.close()
+    def _book_step(self, action, row, infos, terminated):
+        self._prev_action = np.reshape(row[0], [self.n_arm, self.n_action])
+        return super()._book_step(action, row, infos, terminated)
 
 
 class CrawlEnv(_MuscleOctopusEnv):
@@ -236,10 +196,9 @@ class CrawlEnv(_MuscleOctopusEnv):
         self.n_agent = self.n_arm
         self.config_random_final_time = config_random_final_time
 
-    def reset(self, *, seed=None, options=None):
-        out = super().reset(seed=seed, options=options)
+    def _book_reset(self):
+        super()._book_reset()
         self.final_time = float(self._vec.final_times[0])          # crawl_env.py:135-136
-        return out
 
     @property
     def agent_id(self):

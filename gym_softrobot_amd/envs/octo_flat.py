@@ -17,8 +17,7 @@ import numpy as np
 
 from .. import _capi
 from ..spaces import Box, Dict
-from .base import GymEnv as _GymEnv
-from .base import SingleEnvContact, VecRodEnvBase
+from .base import SingleEnvContact, SingleEnvSummary, SingleRodEnv, VecRodEnvBase
 
 
 class VecOctoFlatEnv(VecRodEnvBase):
@@ -60,11 +59,7 @@ class VecOctoFlatEnv(VecRodEnvBase):
         super().__init__(num_envs, cfg, render_mode=render_mode,
                          config_generate_video=config_generate_video, device=device,
                          numpy_output=numpy_output, autoreset=autoreset, backend=backend)
-        self.final_time = final_time
-        self.time_step = time_step
-        self.total_steps = int(self.final_time / self.time_step)
-        self.recording_fps = recording_fps
-        self.step_skip = int(1.0 / (recording_fps * time_step))
+        self._set_timing(final_time, time_step, recording_fps)
         self.n_arm = n_arm
         self.n_elems = n_elems
         self.n_seg = n_elems - 1
@@ -107,8 +102,9 @@ class VecOctoFlatEnv(VecRodEnvBase):
         return {"individual": ind, "shared": obs[:, na * w:]}
 
 
-class FlatEnv(SingleEnvContact, _GymEnv):
-    """Drop-in for gym_softrobot's FlatEnv (octopus/flat_env.py:40-408), N = 1."""
+class FlatEnv(SingleEnvContact, SingleEnvSummary, SingleRodEnv):
+    """Drop-in for gym_softrobot's FlatEnv (octopus/flat_env.py:40-408), N = 1; the observation dict of get_state
+    :231-286, summary :153-170.  The target draw advances env.np_random (:171,221)."""
 
     metadata = {"render_modes": ["rgb_array", "human"], "render_fps": 5}
 
@@ -129,20 +125,9 @@ class FlatEnv(SingleEnvContact, _GymEnv):
         math_mode: int = _capi.MATH_FAST,
         backend=None,
     ):
-        super().__init__()
-        if render_mode not in {None, *self.metadata["render_modes"]}:
-            raise ValueError(f"Unsupported render mode: {render_mode}")
-        self.render_mode = render_mode
-        self._vec = VecOctoFlatEnv(
-            1, final_time, time_step, recording_fps, n_elems, n_arm, n_action, config_generate_video,
-            config_save_head_data, policy_mode, None, device=device, math_mode=math_mode,
-            numpy_output=True, backend=backend,
-        )
-        self.final_time = final_time
-        self.time_step = time_step
-        self.total_steps = self._vec.total_steps
-        self.recording_fps = recording_fps
-        self.step_skip = self._vec.step_skip
+        super().__init__(render_mode, VecOctoFlatEnv, final_time, time_step, recording_fps, n_elems, n_arm, n_action,
+                         config_generate_video, config_save_head_data, policy_mode, None, device=device,
+                         math_mode=math_mode, backend=backend)
         self.n_arm = n_arm
         self.n_elems = n_elems
         self.n_seg = n_elems - 1
@@ -164,72 +149,14 @@ class FlatEnv(SingleEnvContact, _GymEnv):
             "shared": Box(-np.inf, np.inf, shape=(13,), dtype=np.float32),
         })
         self.reward_range = 100.0
-        self.time = np.float64(0.0)
-        self.counter = 0
 
     @property
     def _target(self):
         return self._vec.targets[0]
 
-    def _state(self, obs):
-        d = self._vec.split_obs(np.asarray(obs, dtype=np.float32))
+    def _obs(self, rows):
+        d = self._vec.split_obs(np.asarray(rows, dtype=np.float32))
         return {"individual": d["individual"][0].copy(), "shared": d["shared"][0].copy()}
-
-    def reset(self, *, seed: Optional[int] = None, options: Optional[dict] = None):
-        super().reset(seed=seed)
-        self._vec._rngs[0] = self.np_random   # env-owned stream: the target draw advances env.np_random (flat_env.py:171,221)
-        obs, _ = self._vec.reset(seed=None)
-        self.time = np.float64(0.0)
-        self.counter = 0
-        return self._state(obs), {}
-
-    def step(self, action):
-        a = np.asarray(action, dtype=np.float32).reshape(1, self.n_arm * self.n_action)
-        obs, reward, term, trunc, infos = self._vec.step(a)
-        self.time = np.float64(infos["time"][0])
-        self.counter += 1
-        return (
-            self._state(obs),
-            float(reward[0]),
-            bool(term[0]),
-            bool(trunc[0]),
-            {"time": self.time, "TimeLimit.truncated": bool(infos["TimeLimit.truncated"][0])},
-        )
-
-    def get_state(self):
-        """Current observation dict (flat_env.py:231-286)."""
-        obs = self._vec.backend.observe(None)
-        return self._state(obs.cpu().numpy() if hasattr(obs, "cpu") else obs)
-
-    def summary(self):
-        """As the reference's summary() (octopus/flat_env.py:153-170)."""
-        print(
-            f"""
-        {self.final_time=}
-        {self.time_step=}
-        {self.total_steps=}
-        {self.step_skip=}
-        simulation time per action: {1.0/self.step_skip=}
-        max number of action per episode: {self.total_steps / self.step_skip}
-
-        {self.n_elems=}
-        {self.action_space=}
-        {self.observation_space=}
-        {self.reward_range=}
-        """
-        )
-
-    def save_data(self, filename_video, fps):
-        """The reference renders `rod_parameters_dict` to a video here (flat_env.py:410-420); drawing is out of
-        scope: the data is in `rod_parameters_dict`, nothing is written."""
-        if getattr(self._vec, "config_generate_video", False):
-            raise NotImplementedError("video generation is outside the hot path; use rod_parameters_dict")
-
-    def render(self):
-        """None without a render mode; an (H, W, 3) uint8 frame for "rgb_array" (render.py)."""
-        from ..render import render_env
-
-        return render_env(self)
 
     @property
     def rod_parameters_dict_list(self):
@@ -240,9 +167,3 @@ class FlatEnv(SingleEnvContact, _GymEnv):
     def head_dict(self):
         """The head's RigidCylinderCallBack dict (flat_env.py:199-206), with config_save_head_data=True."""
         return self._vec.head_dict
-
-    def close(self):
-        from ..render import close_env
-
-        close_env(self)
-        self._vec.close()

@@ -21,8 +21,7 @@ import numpy as np
 
 from .. import _capi
 from ..spaces import Box
-from .base import GymEnv as _GymEnv
-from .base import VecRodEnvBase
+from .base import SingleRodEnv, VecRodEnvBase
 
 
 def target_trajectory(final_time: float, sim_dt: float, target_v_scale: float, rng, every: int = 1):
@@ -125,23 +124,21 @@ class VecSoftArmTrackingEnv(VecRodEnvBase):
         return {"time": times, "ctime": times, "TimeLimit.truncated": ticks * self.sim_dt >= self.max_episode_final_time}
 
 
-class SoftArmTrackingEnv(_GymEnv):
-    """Drop-in for gym_softrobot's SoftArmTrackingEnv (soft_arm/soft_arm_tracking.py:104-548), N = 1."""
+class SoftArmTrackingEnv(SingleRodEnv):
+    """Drop-in for gym_softrobot's SoftArmTrackingEnv (soft_arm/soft_arm_tracking.py:104-548), N = 1; get_state
+    :160-207.  The env's stream is the batch's (:402-407); its host clock is `tick` / `time_tracker`."""
 
     metadata = {"render_modes": ["rgb_array", "human"], "render_fps": 30}
+    obs_dtype = np.float64                            # widened straight from the C-ABI's float32 (module docstring)
+    mirrored = ("num_steps_per_update",)              # the batch has none of the final_time / time_step family
 
     def __init__(self, game_mode: int = 1, render_mode: Optional[str] = None, *, device: int = 0,
                  math_mode: int = _capi.MATH_FAST, backend=None):
-        super().__init__()
-        if render_mode not in {None, *self.metadata["render_modes"]}:
-            raise ValueError(f"Unsupported render mode: {render_mode}")
-        self.render_mode = render_mode
-        self._vec = VecSoftArmTrackingEnv(1, game_mode, None, device=device, math_mode=math_mode,
-                                          numpy_output=True, backend=backend)
+        super().__init__(render_mode, VecSoftArmTrackingEnv, game_mode, None, device=device, math_mode=math_mode,
+                         backend=backend)
         self.n_elem = 40
         self.sim_dt = 2.0e-4
         self.RL_update_interval = 0.01
-        self.num_steps_per_update = self._vec.num_steps_per_update
         self.youngs_modulus = 2e6
         self.torque_scale = 10
         self.max_episode_final_time = 5
@@ -154,38 +151,12 @@ class SoftArmTrackingEnv(_GymEnv):
         self.target_v_scale = 0.1
         self.action_space = Box(-1.0, 1.0, shape=(8,), dtype=np.float64)
         self.observation_space = Box(-np.inf, np.inf, shape=(14,), dtype=np.float64)
+
+    def _book_reset(self):
         self.tick = 0
         self.time_tracker = np.float64(0.0)
 
-    def reset(self, *, seed: Optional[int] = None, options: Optional[dict] = None):
-        super().reset(seed=seed)
-        self._vec._rngs[0] = self.np_random       # env-owned stream, as soft_arm_tracking.py:402-407
-        obs, _ = self._vec.reset(seed=None)
-        self.tick = 0
-        self.time_tracker = np.float64(0.0)
-        return np.asarray(obs[0], dtype=np.float64), {}
-
-    def step(self, action):
-        a = np.asarray(action, dtype=np.float32).reshape(1, 8)
-        obs, reward, term, trunc, infos = self._vec.step(a)
+    def _book_step(self, action, row, infos, terminated):
         self.tick += self.num_steps_per_update
         self.time_tracker = np.float64(infos["time"][0])
-        return (np.asarray(obs[0], dtype=np.float64), float(reward[0]), bool(term[0]), bool(trunc[0]),
-                {"ctime": self.time_tracker})
-
-    def get_state(self):
-        """Current observation (soft_arm_tracking.py:160-207)."""
-        obs = self._vec.backend.observe(None)
-        return np.asarray(obs[0].cpu().numpy() if hasattr(obs, "cpu") else obs[0], dtype=np.float64)
-
-    def render(self):
-        """None without a render mode; an (H, W, 3) uint8 frame for "rgb_array" (render.py)."""
-        from ..render import render_env
-
-        return render_env(self)
-
-    def close(self):
-        from ..render import close_env
-
-        close_env(self)
-        self._vec.close()
+        return {"ctime": self.time_tracker}

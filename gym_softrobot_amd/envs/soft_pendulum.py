@@ -22,8 +22,7 @@ import numpy as np
 from .. import _capi
 from ..seeding import initial_angle
 from ..spaces import Box
-from .base import GymEnv as _GymEnv
-from .base import SingleEnvMaterial, VecRodEnvBase
+from .base import SingleEnvMaterial, SingleRodEnv, VecRodEnvBase
 from .base import time_table as _time_table  # noqa: F401  (re-exported for tests)
 
 
@@ -57,11 +56,7 @@ class VecSoftPendulumEnv(VecRodEnvBase):
         super().__init__(num_envs, cfg, render_mode=render_mode,
                          config_generate_video=config_generate_video, device=device,
                          numpy_output=numpy_output, autoreset=autoreset, backend=backend)
-        self.final_time = final_time
-        self.time_step = time_step
-        self.total_steps = int(self.final_time / self.time_step)
-        self.recording_fps = recording_fps
-        self.step_skip = int(1.0 / (recording_fps * time_step))
+        self._set_timing(final_time, time_step, recording_fps)
         self.n_elems = n_elems
         self.n_seg = n_elems - 1
 
@@ -81,11 +76,11 @@ class VecSoftPendulumEnv(VecRodEnvBase):
         self.backend.queue_push(th, counts)
 
 
-class SoftPendulumEnv(SingleEnvMaterial, _GymEnv):
+class SoftPendulumEnv(SingleEnvMaterial, SingleRodEnv):
     """Drop-in for gym_softrobot's SoftPendulumEnv (soft_pendulum.py:45-322), N = 1.
 
     Same constructor keywords (soft_pendulum.py:59-67), spaces (:84-94), return
-    types (:241-251).  `render()` and video generation are outside the hot path.
+    types (:241-251), get_state (:149-161).  `render()` and video generation are outside the hot path.
     """
 
     metadata = {"render_modes": ["rgb_array"], "render_fps": 25}
@@ -103,19 +98,8 @@ class SoftPendulumEnv(SingleEnvMaterial, _GymEnv):
         math_mode: int = _capi.MATH_FAST,
         backend=None,
     ):
-        super().__init__()
-        if render_mode not in {None, *self.metadata["render_modes"]}:
-            raise ValueError(f"Unsupported render mode: {render_mode}")
-        self.render_mode = render_mode
-        self._vec = VecSoftPendulumEnv(
-            1, final_time, time_step, recording_fps, n_elems, config_generate_video,
-            None, device=device, math_mode=math_mode, numpy_output=True, backend=backend,
-        )
-        self.final_time = final_time
-        self.time_step = time_step
-        self.total_steps = self._vec.total_steps
-        self.recording_fps = recording_fps
-        self.step_skip = self._vec.step_skip
+        super().__init__(render_mode, VecSoftPendulumEnv, final_time, time_step, recording_fps, n_elems,
+                         config_generate_video, None, device=device, math_mode=math_mode, backend=backend)
         self.n_elems = n_elems
         self.n_seg = n_elems - 1
         self.n_action = 1
@@ -123,57 +107,14 @@ class SoftPendulumEnv(SingleEnvMaterial, _GymEnv):
         self.observation_space = Box(-np.inf, np.inf, shape=(4,), dtype=np.float32)
         self.reward_range = 100.0
         self.config_generate_video = config_generate_video
-        self.time = np.float64(0.0)
-        self.counter = 0
 
-    def reset(self, *, seed: Optional[int] = None, options: Optional[dict] = None):
-        super().reset(seed=seed)
-        self._vec._rngs[0] = self.np_random  # env-owned stream, as soft_pendulum.py:114,123
-        obs, _ = self._vec.reset(seed=None)
-        self.time = np.float64(0.0)
-        self.counter = 0
-        return np.asarray(obs[0], dtype=np.float32).copy(), {}
-
-    def step(self, action):
-        a = np.asarray(action, dtype=np.float32).reshape(1)
-        obs, reward, term, trunc, infos = self._vec.step(a)
-        self.time = np.float64(infos["time"][0])
-        self.counter += 1
-        info = {"time": self.time, "TimeLimit.truncated": bool(infos["TimeLimit.truncated"][0])}
-        if bool(term[0]):
+    def _book_step(self, action, row, infos, terminated):
+        info = super()._book_step(action, row, infos, terminated)
+        if terminated:
             print(f" Nan detected in, exiting simulation now. {self.time=}")  # soft_pendulum.py:206
-        return (
-            np.asarray(obs[0], dtype=np.float32).copy(),
-            float(reward[0]),
-            bool(term[0]),
-            bool(trunc[0]),
-            info,
-        )
+        return info
 
     @property
     def rod_parameters_dict(self):
         """RodCallBack's samples (soft_pendulum.py:117-126) when config_generate_video=True."""
         return self._vec.rod_parameters_dict
-
-    def get_state(self):
-        """Current observation (soft_pendulum.py:149-161)."""
-        obs = self._vec.backend.observe(None)
-        return np.asarray(obs[0].cpu().numpy() if hasattr(obs, "cpu") else obs[0], dtype=np.float32).copy()
-
-    def save_data(self, filename_video, fps):
-        """The reference renders `rod_parameters_dict` to a video here (soft_pendulum.py:253-256); drawing is out of
-        scope: the data is in `rod_parameters_dict`, nothing is written."""
-        if getattr(self._vec, "config_generate_video", False):
-            raise NotImplementedError("video generation is outside the hot path; use rod_parameters_dict")
-
-    def render(self):
-        """None without a render mode; an (H, W, 3) uint8 frame for "rgb_array" (render.py)."""
-        from ..render import render_env
-
-        return render_env(self)
-
-    def close(self):
-        from ..render import close_env
-
-        close_env(self)
-        self._vec.close()

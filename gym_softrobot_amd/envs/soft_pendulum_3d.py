@@ -14,8 +14,7 @@ import numpy as np
 
 from .. import _capi
 from ..spaces import Box
-from .base import GymEnv as _GymEnv
-from .base import SingleEnvMaterial, VecRodEnvBase
+from .base import SingleEnvMaterial, SingleRodEnv, VecRodEnvBase
 
 
 def initial_tilt(rng: np.random.Generator) -> float:
@@ -52,11 +51,7 @@ class VecSoftPendulum3DEnv(VecRodEnvBase):
         super().__init__(num_envs, cfg, render_mode=render_mode,
                          config_generate_video=config_generate_video, device=device,
                          numpy_output=numpy_output, autoreset=autoreset, backend=backend)
-        self.final_time = final_time
-        self.time_step = time_step
-        self.total_steps = int(self.final_time / self.time_step)
-        self.recording_fps = recording_fps
-        self.step_skip = int(1.0 / (recording_fps * time_step))
+        self._set_timing(final_time, time_step, recording_fps)
         self.n_elems = n_elems
         self.base_step = 1e-3
         self.base_limit = 0.5
@@ -99,8 +94,8 @@ class VecSoftPendulum3DEnv(VecRodEnvBase):
         return {"time": times, "tilt": self._out(self.backend.aux[:, 0])}
 
 
-class SoftPendulum3DEnv(SingleEnvMaterial, _GymEnv):
-    """Drop-in for gym_softrobot's SoftPendulum3DEnv (soft_pendulum_3d.py:20-174), N = 1."""
+class SoftPendulum3DEnv(SingleEnvMaterial, SingleRodEnv):
+    """Drop-in for gym_softrobot's SoftPendulum3DEnv (soft_pendulum_3d.py:20-174), N = 1; get_state :93-98."""
 
     metadata = {"render_modes": ["rgb_array"], "render_fps": 25}
 
@@ -117,64 +112,21 @@ class SoftPendulum3DEnv(SingleEnvMaterial, _GymEnv):
         math_mode: int = _capi.MATH_FAST,
         backend=None,
     ):
-        super().__init__()
-        if render_mode not in {None, *self.metadata["render_modes"]}:
-            raise ValueError(f"Unsupported render mode: {render_mode}")
-        self.render_mode = render_mode
-        self._vec = VecSoftPendulum3DEnv(
-            1, final_time, time_step, recording_fps, n_elems, config_generate_video, None,
-            device=device, math_mode=math_mode, numpy_output=True, backend=backend,
-        )
-        self.final_time = final_time
-        self.time_step = time_step
-        self.total_steps = self._vec.total_steps
-        self.recording_fps = recording_fps
-        self.step_skip = self._vec.step_skip
+        super().__init__(render_mode, VecSoftPendulum3DEnv, final_time, time_step, recording_fps, n_elems,
+                         config_generate_video, None, device=device, math_mode=math_mode, backend=backend)
         self.n_elems = n_elems
         self.n_action = 2
         self.action_space = Box(-1.0, 1.0, shape=(2,), dtype=np.float32)
         self.observation_space = Box(-np.inf, np.inf, shape=(9,), dtype=np.float32)
         self.base_step = 1e-3
         self.base_limit = 0.5
-        self.time = np.float64(0.0)
-        self.counter = 0
 
-    def reset(self, *, seed: Optional[int] = None, options: Optional[dict] = None):
-        super().reset(seed=seed)
-        self._vec._rngs[0] = self.np_random
-        obs, _ = self._vec.reset(seed=None)
-        self.time = np.float64(0.0)
-        self.counter = 0
-        return np.asarray(obs[0], dtype=np.float32).copy(), {}
-
-    def step(self, action):
+    def _action_row(self, action):
         if not self.action_space.contains(action):  # soft_pendulum_3d.py:116-117
             raise ValueError(f"Action {action!r} is outside {self.action_space}")
-        a = np.asarray(action, dtype=np.float32).reshape(1, 2)
-        obs, reward, term, trunc, infos = self._vec.step(a)
+        return super()._action_row(action)
+
+    def _book_step(self, action, row, infos, terminated):
         self.time = np.float64(infos["time"][0])
         self.counter += 1
-        return (
-            np.asarray(obs[0], dtype=np.float32).copy(),
-            float(reward[0]),
-            bool(term[0]),
-            bool(trunc[0]),
-            {"time": self.time, "tilt": float(infos["tilt"][0])},
-        )
-
-    def get_state(self):
-        """Current observation (soft_pendulum_3d.py:93-98)."""
-        obs = self._vec.backend.observe(None)
-        return np.asarray(obs[0].cpu().numpy() if hasattr(obs, "cpu") else obs[0], dtype=np.float32).copy()
-
-    def render(self):
-        """None without a render mode; an (H, W, 3) uint8 frame for "rgb_array" (render.py)."""
-        from ..render import render_env
-
-        return render_env(self)
-
-    def close(self):
-        from ..render import close_env
-
-        close_env(self)
-        self._vec.close()
+        return {"time": self.time, "tilt": float(infos["tilt"][0])}     # no TimeLimit.truncated, as :163-171

@@ -8,6 +8,8 @@ import pytest
 import gym_softrobot_amd as gsa
 from gym_softrobot_amd.spaces import Box
 
+from .single_env_table import NAMES, TABLE, check_api
+
 pytestmark = pytest.mark.gpu
 ENV_IDS = sorted(gsa.registered())
 
@@ -91,3 +93,14 @@ def test_make_vec_covers_every_registered_id(hip_lib, env_id):
     assert float(r[0]) == float(r1[0]) and bool(te[0]) == bool(te1[0]) and bool(tr[0]) == bool(tr1[0])
     vec.close()
     one.close()
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_single_env_class_keeps_its_api_table_on_the_hip_backend(hip_lib, name):
+    """Each of the ten N = 1 classes at its registered defaults: reset(seed=0), two steps and get_state give the
+    types, shapes, info keys and host counters of tests/single_env_table.py — the table the CPU test
+    (tests/test_single_env_shell.py) checks on the oracle-backed double."""
+    env = gsa.make(TABLE[name]["id"])
+    assert type(env._vec.backend).__name__ == "HipRodBackend" and env._vec.num_envs == 1
+    check_api(env, name, seed=0)
+    env.close()
