@@ -788,6 +788,23 @@ def env_contact_refusal(cfg: "SoftrodConfig", tapered: bool = False):
     return None
 
 
+def ground_reaction_refusal(cfg: "SoftrodConfig"):
+    """Why softrod_ground_reaction would refuse a handle of `cfg` (None: it would not), in the library's own words:
+    the read-out serves handles with plane contact, without COOMM muscles, with rods of up to 63 elements."""
+    kind, feats = int(cfg.env_kind), int(cfg.features)
+    if kind in MUSCLE_OCTOPUS_ENVS or kind == ENV_ARM_PULL_WEIGHT or feats & FEAT_COOMM_MUSCLES:
+        return "ground reaction: not for the muscle envs"
+    if not feats & FEAT_PLANE_CONTACT_ANISO:
+        return "ground reaction: this env has no plane contact"
+    if feats & FEAT_OCTO_HEAD and kind != ENV_OCTO_FLAT:
+        return "ground reaction: of the rigid-head envs OctoFlat and OctoFlatLite only"
+    if feats & (FEAT_POINT_FORCE_NODE0_X | FEAT_SPLINE_MUSCLE_TORQUES):
+        return "ground reaction: not with a point force or spline muscle torques (loads that are not in the resident state)"
+    if int(cfg.n_elem) > 63:
+        return "ground reaction: rods of up to 63 elements only (not the two-slot or windowed long rods)"
+    return None
+
+
 def env_contact_defaults(cfg: "SoftrodConfig") -> "np.ndarray":
     """(8,) float64: the config's own contact_k, contact_nu, kinetic_mu[3], static_mu[3] (forward, backward,
     sideways)."""
@@ -860,6 +877,7 @@ _EXPORTS = {
     "softrod_exchange_free": (C.c_int, [C.c_int, _VP]),
     "softrod_observe": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_rod_energies": (C.c_int, [_VP, _VP, _VP]),
+    "softrod_ground_reaction": (C.c_int, [_VP, _VP, _VP]),
     "softrod_set_env_material": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_set_env_contact": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_substeps": (C.c_int, [_VP, _VP, C.c_int, _VP]),

@@ -311,6 +311,19 @@ class HipRodBackend:
         check(self._lib.softrod_rod_energies(self._h, self._energies.data_ptr(), self._stream()), self._h)
         return self._energies
 
+    def ground_reaction(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """softrod_ground_reaction: (force, torque) float64 device tensors — force (n_envs, rods_per_env, 3, n_elem + 1),
+        the lab-frame force RodPlaneContactWithAnisotropicFriction adds to every node; torque (n_envs, rods_per_env, 3,
+        n_elem), the material-frame torque it adds to every element — from ONE fresh force evaluation at the resident
+        state (not the value the last substep applied: include/softrod.h).  Views of one buffer allocated on first
+        use and overwritten by the next call."""
+        if getattr(self, "_reaction", None) is None:
+            rods = int(self.cfg.n_arm) if int(self.cfg.env_kind) == _capi.ENV_OCTO_FLAT else 1
+            self._reaction = torch.empty((self.n_envs, rods, 6, int(self.cfg.n_elem) + 1), dtype=torch.float64,
+                                         device=self.device)
+        check(self._lib.softrod_ground_reaction(self._h, self._reaction.data_ptr(), self._stream()), self._h)
+        return self._reaction[:, :, :3], self._reaction[:, :, 3:, :-1]
+
     def time_limit(self) -> torch.Tensor:
         """early_termination handles: the last step's time-limit flag per env (row 0 of softrod_state_view.env_aux)
         as a bool device tensor — info["TimeLimit.truncated"], which `truncated` no longer is."""

@@ -471,6 +471,19 @@ const char* contact_why_not(const softrod_handle* h) {
     if (h->tapered) return "per-env contact: not for a tapered rod (softrod_set_radius_profile)";
     return "per-env contact: rods of up to 63 elements only (not the two-slot or windowed long rods)";
 }
+// softrod_ground_reaction's scope: the first reason that applies, nullptr when the handle is served (the Python copy
+// is ground_reaction_refusal in _capi.py).
+const char* ground_reaction_why_not(const softrod_handle* h) {
+    const unsigned f = h->cfg.features;
+    if (is_mocto(h) || is_pull(h) || (f & SOFTROD_FEAT_COOMM_MUSCLES)) return "ground reaction: not for the muscle envs";
+    if (!(f & SOFTROD_FEAT_PLANE_CONTACT_ANISO)) return "ground reaction: this env has no plane contact";
+    if ((f & SOFTROD_FEAT_OCTO_HEAD) && !is_flat(h)) return "ground reaction: of the rigid-head envs OctoFlat and OctoFlatLite only";
+    if (f & (SOFTROD_FEAT_POINT_FORCE_NODE0_X | SOFTROD_FEAT_SPLINE_MUSCLE_TORQUES))
+        return "ground reaction: not with a point force or spline muscle torques (loads that are not in the resident state)";
+    if (h->cfg.n_elem > 63)          // (up to 63 elements a rod has one slot per lane and no windows: softrod_create)
+        return "ground reaction: rods of up to 63 elements only (not the two-slot or windowed long rods)";
+    return nullptr;
+}
 const char* why_no_row(const softrod_handle* h, unsigned opts) {
     if ((opts & kOptEarlyTerm) && h->cfg.math_mode == SOFTROD_MATH_FAST && !is_pull(h) &&
         !(h->tapered && h->cfg.features == SOFTROD_FEATURES_ARM_PUSH && h->cfg.env_kind == SOFTROD_ENV_ARM_PUSH))
@@ -1856,6 +1869,20 @@ int softrod_rod_energies(softrod_handle* h, double* out, void* stream) {
     else
         hipLaunchKernelGGL(softrod_rod_energies_kernel<1>, grid, block, 0, (hipStream_t)stream, h->P, h->S, rods,
                            lane_stride, arm_stride, out);
+    SR_HIP(h, hipGetLastError());
+    return SOFTROD_OK;
+}
+
+int softrod_ground_reaction(softrod_handle* h, double* out, void* stream) {
+    if (!h || !out) return fail(h, SOFTROD_EINVAL, "null argument");
+    if (const char* why = ground_reaction_why_not(h)) return fail(h, SOFTROD_EINVAL, why);
+    SR_ON_DEVICE(h);
+    // the rods of an env with a rigid head (the kernel's own test: SOFTROD_FEAT_OCTO_HEAD; of those only OctoFlat is in scope)
+    const int rods = is_octo(h) ? h->cfg.n_arm : 1;
+    const int lane_stride = kLanes * h->epl * h->nw, arm_stride = is_octo(h) ? h->P.seg : 0;
+    const dim3 grid((unsigned)(h->cfg.n_envs * rods)), block(kLanes);
+    hipLaunchKernelGGL(softrod_ground_reaction_kernel, grid, block, 0, (hipStream_t)stream, h->P, h->S, rods, lane_stride,
+                       arm_stride, out);
     SR_HIP(h, hipGetLastError());
     return SOFTROD_OK;
 }

@@ -19,7 +19,8 @@
 //
 // File map: softrod_contact.hpp (rod-plane contact), softrod_fast.hpp (the default step
 // kernel), softrod_planar.hpp (SoftPendulum's planar substep), softrod_octo.hpp (OctoFlat: one
-// env per workgroup), softrod_window.hpp (64..102-element arms on two overlapping windows);
+// env per workgroup), softrod_window.hpp (64..102-element arms on two overlapping windows),
+// softrod_reaction.hpp (the ground-reaction read-out, a cold kernel);
 // this file holds the state layout, the env prologues/epilogues, the reset /
 // observe / auto-reset kernels and the LIBM kernel.
 //
@@ -2206,3 +2207,4 @@ softrod_rod_energies_kernel(const RodParams P, const StatePtrs S, const int rods
 #include "softrod_fast.hpp"
 #include "softrod_octo.hpp"
 #include "softrod_window.hpp"
+#include "softrod_reaction.hpp"

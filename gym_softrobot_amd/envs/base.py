@@ -145,6 +145,12 @@ class SingleRodEnv(GymEnv):
         obs = self._vec.backend.observe(None)
         return self._obs(obs.cpu().numpy() if hasattr(obs, "cpu") else obs)
 
+    def ground_reaction(self):
+        """VecRodEnvBase.ground_reaction of this env, without the env axis: force (rods, 3, n_elem + 1) and torque
+        (rods, 3, n_elem) as NumPy arrays; NotImplementedError for an env without plane contact."""
+        force, torque = self._vec.ground_reaction()
+        return force[0], torque[0]
+
     def save_data(self, filename_video, fps):
         """The reference renders `rod_parameters_dict` to a video here (soft_pendulum.py:253-256, flat_env.py:410-420);
         drawing is out of scope: the data is in `rod_parameters_dict`, nothing is written."""
@@ -595,6 +601,27 @@ class VecRodEnvBase:
         per arm (rigid bodies have none).  A device tensor overwritten by the next call (NumPy with
         numpy_output=True)."""
         return self._out(self.backend.rod_energies())
+
+    def ground_reaction(self):
+        """(force, torque): what the ground does to the body.  force (N, rods_per_env, 3, n_elem + 1) is the
+        lab-frame force RodPlaneContactWithAnisotropicFriction adds to every node — plane response with its elastic
+        and damping terms plus kinetic and static friction, axial and rolling —, torque (N, rods_per_env, 3, n_elem)
+        the material-frame torque it adds to every element.  The reference evaluates both in every substep and
+        returns neither.  THE INSTANT: one fresh force evaluation at the state as it stands (no half kinematic
+        step), with the external loads gathered in the substep's order; not the value the last substep applied,
+        which depends on that substep's pre-update rates (include/softrod.h softrod_ground_reaction).  Per-env
+        contact, per-env material and a radius profile are honoured.  OctoArmSingle (up to 63 elements), OctoFlat
+        and OctoFlatLite on the HIP backend; elsewhere NotImplementedError.  Device tensors, views of one buffer
+        overwritten by the next call (NumPy copies with numpy_output=True).  Inside a capture_policy_step graph
+        only if the policy itself calls it: the captured step does not."""
+        be = self.backend
+        if not hasattr(be, "ground_reaction"):
+            raise NotImplementedError(f"ground reaction needs the HIP backend, not {type(be).__name__}")
+        why = _capi.ground_reaction_refusal(self.cfg)
+        if why is not None:
+            raise NotImplementedError(why)
+        force, torque = be.ground_reaction()
+        return self._out(force), self._out(torque)
 
     # -- per-env material (domain randomisation) ----------------------------------------
     _MATERIAL_KEYS = ("youngs_modulus", "shear_modulus", "density", "damping_constant")

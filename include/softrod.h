@@ -658,6 +658,34 @@ int softrod_observe(softrod_handle* h, const float* prev_action, float* obs,
  *   shear          1/2 sum_e sigma_e . S_e sigma_e  l^_e           (rest sigma 0)  */
 int softrod_rod_energies(softrod_handle* h, double* out, void* stream);
 
+/* Ground reaction: what RodPlaneContactWithAnisotropicFriction.apply_contact (registered by
+ * octopus/build.py:193-200,274-283; the law as recalled from pyelastica 1.0.0, softrod_contact.hpp) adds to
+ * external_forces and external_torques of every rod of every env.  The reference evaluates it in every substep
+ * and returns none of it.  out: device [n_envs][rods_per_env][6][n_elem + 1] float64, rods_per_env = n_arm for
+ * OctoFlat, else 1:
+ *   rows 0-2  the lab-frame force added to each node: the sum of the five contributions after
+ *             elements_to_nodes — plane response with its elastic and damping terms, kinetic axial, kinetic
+ *             rolling, static axial, static rolling friction
+ *   rows 3-5  the material-frame torque added to each element (the two rolling frictions); column n_elem is 0.
+ * Asynchronous on `stream`, like softrod_rod_energies; capturable.
+ * THE INSTANT: ONE FRESH force evaluation at the state as it stands in device memory — x, v, Q, omega,
+ * rest_kappa — with no half kinematic step and no constrain_values before it.  Internal forces and torques are
+ * computed from that state; the external loads are gathered in the substep's own order (FixedJoint2Rigid on node
+ * 0 / element 0 of each OctoFlat arm first, then the forcing group and the contact in the order
+ * contact_before_forcing says), and `out` is what the contact operator added (its static friction reads
+ * f_int + f_ext, t_int + t_ext of that moment).  It is NOT the value the last substep applied: that one was
+ * evaluated at the mid-substep configuration with the pre-update rates, and the law depends on those rates
+ * (normal damping, slip velocities, the static / kinetic blend), so it cannot be recovered from the end state.
+ * ARITHMETIC: float64 as written (IEEE division and sqrt, libm acos / sin / cos; no fast-math forms), the same
+ * kernel for SOFTROD_MATH_LIBM and SOFTROD_MATH_FAST handles, any plane normal.  The per-env tables of
+ * softrod_set_env_contact / softrod_set_env_material and the radius profile of a tapered arm are honoured.
+ * Scope: handles with SOFTROD_FEAT_PLANE_CONTACT_ANISO, without COOMM muscles, rods of up to 63 elements:
+ * SOFTROD_ENV_ARM_SINGLE (uniform or tapered) and SOFTROD_ENV_OCTO_FLAT (OctoFlat, OctoFlatLite; every wave shape).
+ * Anything else (envs without contact, the muscle envs, the two-slot and windowed arms of 64 or more elements,
+ * a feature set with a point force or spline muscle torques) -> SOFTROD_EINVAL with "ground reaction: <reason>"
+ * in softrod_last_error.                                                                                       */
+int softrod_ground_reaction(softrod_handle* h, double* out, void* stream);
+
 /* Per-env rod material, for domain randomisation of single-rod envs.  Upstream has no counterpart: there
  * every env builds its rod with CosseratRod.straight_rod(..., density, youngs_modulus, shear_modulus) and
  * AnalyticalLinearDamper(damping_constant, ...), and a batch of them shares one softrod_config.  This call
