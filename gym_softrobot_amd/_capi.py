@@ -878,6 +878,7 @@ _EXPORTS = {
     "softrod_observe": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_rod_energies": (C.c_int, [_VP, _VP, _VP]),
     "softrod_ground_reaction": (C.c_int, [_VP, _VP, _VP]),
+    "softrod_rod_strains": (C.c_int, [_VP, _VP, _VP]),
     "softrod_set_env_material": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_set_env_contact": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_substeps": (C.c_int, [_VP, _VP, C.c_int, _VP]),

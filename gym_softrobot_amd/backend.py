@@ -11,6 +11,7 @@ import torch
 
 from . import _capi
 from ._capi import LANE_STRIDE, SoftrodConfig, SoftrodStateView, check, load_library
+from .diagnostics import RodStrains, rod_strains_views
 
 
 class _DevArray:
@@ -323,6 +324,19 @@ class HipRodBackend:
                                          device=self.device)
         check(self._lib.softrod_ground_reaction(self._h, self._reaction.data_ptr(), self._stream()), self._h)
         return self._reaction[:, :, :3], self._reaction[:, :, 3:, :-1]
+
+    def rod_strains(self) -> RodStrains:
+        """softrod_rod_strains: RodStrains(sigma, kappa, dilatation, voronoi_dilatation, internal_force,
+        internal_couple) of float64 device tensors — (n_envs, rods_per_env, 3, n_elem), (.., 3, n_elem - 1),
+        (.., n_elem), (.., n_elem - 1), (.., 3, n_elem), (.., 3, n_elem - 1) — RodCallBack's strain fields and the
+        passive elastic loads S sigma, B (kappa - rest_kappa), at the instant of rod_energies() (include/softrod.h).
+        Views of one (n_envs, rods_per_env, 14, n_elem) buffer allocated on first use and overwritten by the next
+        call."""
+        if getattr(self, "_strains", None) is None:
+            self._strains = torch.empty((self.n_envs, _capi.config_rods_per_env(self.cfg), 14, int(self.cfg.n_elem)),
+                                        dtype=torch.float64, device=self.device)
+        check(self._lib.softrod_rod_strains(self._h, self._strains.data_ptr(), self._stream()), self._h)
+        return rod_strains_views(self._strains)
 
     def time_limit(self) -> torch.Tensor:
         """early_termination handles: the last step's time-limit flag per env (row 0 of softrod_state_view.env_aux)

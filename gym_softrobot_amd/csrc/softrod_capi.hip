@@ -1887,6 +1887,25 @@ int softrod_ground_reaction(softrod_handle* h, double* out, void* stream) {
     return SOFTROD_OK;
 }
 
+int softrod_rod_strains(softrod_handle* h, double* out, void* stream) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "rod strains: null handle");
+    if (!out) return fail(h, SOFTROD_EINVAL, "rod strains: null output buffer");
+    SR_ON_DEVICE(h);
+    // softrod_rod_energies' launch: every handle's resident rows have this layout, so there is no refusal list
+    const bool arms = is_flat(h) || is_mocto(h);
+    const int rods = arms ? h->cfg.n_arm : 1;
+    const int lane_stride = kLanes * h->epl * h->nw, arm_stride = arms ? h->P.seg : 0;
+    const dim3 grid((unsigned)(h->cfg.n_envs * rods)), block(kLanes);
+    if (h->epl == 2)
+        hipLaunchKernelGGL(softrod_rod_strains_kernel<2>, grid, block, 0, (hipStream_t)stream, h->P, h->S, rods,
+                           lane_stride, arm_stride, out);
+    else
+        hipLaunchKernelGGL(softrod_rod_strains_kernel<1>, grid, block, 0, (hipStream_t)stream, h->P, h->S, rods,
+                           lane_stride, arm_stride, out);
+    SR_HIP(h, hipGetLastError());
+    return SOFTROD_OK;
+}
+
 int softrod_state_view_get(softrod_handle* h, softrod_state_view* out) {
     if (!h || !out) return fail(h, SOFTROD_EINVAL, "null argument");
     out->n_envs = h->cfg.n_envs;

@@ -20,7 +20,8 @@
 // File map: softrod_contact.hpp (rod-plane contact), softrod_fast.hpp (the default step
 // kernel), softrod_planar.hpp (SoftPendulum's planar substep), softrod_octo.hpp (OctoFlat: one
 // env per workgroup), softrod_window.hpp (64..102-element arms on two overlapping windows),
-// softrod_reaction.hpp (the ground-reaction read-out, a cold kernel);
+// softrod_reaction.hpp (the ground-reaction read-out, a cold kernel), softrod_strains.hpp (the
+// strain and internal-load read-out, a cold kernel);
 // this file holds the state layout, the env prologues/epilogues, the reset /
 // observe / auto-reset kernels and the LIBM kernel.
 //
@@ -2208,3 +2209,4 @@ softrod_rod_energies_kernel(const RodParams P, const StatePtrs S, const int rods
 #include "softrod_octo.hpp"
 #include "softrod_window.hpp"
 #include "softrod_reaction.hpp"
+#include "softrod_strains.hpp"

@@ -24,7 +24,7 @@ that.  Rendering itself (matplotlib / POV-Ray) stays out of scope; this is what 
 from __future__ import annotations
 
 from collections import defaultdict
-from typing import Dict, List, Sequence
+from typing import Dict, List, NamedTuple, Sequence
 
 import numpy as np
 
@@ -140,6 +140,44 @@ def rod_energies_host(x, v, Q, w, time: float, cfg, material, rest_kappa=None, f
     bend = 0.5 * ((material["bend"] * dk * dk).sum(0) * material["rest_voronoi"]).sum()
     shear = 0.5 * ((material["shear"] * s["sigma"] * s["sigma"]).sum(0) * rl).sum()
     return np.array([trans, rot, bend, shear])
+
+
+class RodStrains(NamedTuple):
+    """What softrod_rod_strains / rod_strains() return (include/softrod.h): sigma (.., 3, n_elem), kappa
+    (.., 3, n_elem - 1; not reduced by the rest curvature), dilatation (.., n_elem), voronoi_dilatation
+    (.., n_elem - 1), internal_force S sigma (.., 3, n_elem), internal_couple B (kappa - rest_kappa) (.., 3, n_elem - 1)."""
+    sigma: object
+    kappa: object
+    dilatation: object
+    voronoi_dilatation: object
+    internal_force: object
+    internal_couple: object
+
+
+def rod_strains_views(buf) -> RodStrains:
+    """The six fields as views of softrod_rod_strains' buffer (.., 14, n_elem): the Voronoi rows without their
+    last (zero) column."""
+    return RodStrains(buf[..., 0:3, :], buf[..., 3:6, :-1], buf[..., 6, :], buf[..., 7, :-1], buf[..., 8:11, :],
+                      buf[..., 11:14, :-1])
+
+
+def rod_strains_host(x, v, Q, w, time: float, cfg, material, rest_kappa=None, fixed_pos=None, fixed_dir=None,
+                     base_xy=None) -> RodStrains:
+    """NumPy twin of softrod_rod_strains for one rod, at rod_energies_host's instant: the strains of the mid-substep
+    configuration (mid_substep_configuration, then constrain_values_host); time == 0 (a reset) uses the state as
+    it stands.  internal_force = S sigma and internal_couple = B (kappa - rest_kappa) are the passive elastic loads
+    (no muscle layers), so that 1/2 sum sigma . n l^ and 1/2 sum (kappa - rest_kappa) . m D^ are rod_energies_host's
+    shear and bending entries.  material: rod_material_host(...); rest_kappa (3, n-1) or None (zero)."""
+    x, Q = np.array(x, np.float64), np.array(Q, np.float64)
+    v, w = np.asarray(v, np.float64), np.asarray(w, np.float64)
+    if time != 0.0:
+        x, Q = mid_substep_configuration(x, v, Q, w, float(cfg.dt), float(cfg.eps_rot_axis))
+        if fixed_pos is not None:
+            constrain_values_host(int(cfg.features), x, Q, fixed_pos, fixed_dir, base_xy)
+    s = rod_strains(x, Q, material["rest_length"], 1.0, float(cfg.acos_shift), float(cfg.eps_sin))
+    dk = s["kappa"] if rest_kappa is None else s["kappa"] - rest_kappa
+    return RodStrains(s["sigma"], s["kappa"], s["dilatation"], s["voronoi_dilatation"], material["shear"] * s["sigma"],
+                      material["bend"] * dk)
 
 
 class RodRecorder:

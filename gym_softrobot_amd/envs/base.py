@@ -151,6 +151,13 @@ class SingleRodEnv(GymEnv):
         force, torque = self._vec.ground_reaction()
         return force[0], torque[0]
 
+    def rod_strains(self):
+        """VecRodEnvBase.rod_strains of this env, without the env axis, as NumPy arrays: RodStrains(sigma (rods, 3,
+        n_elem), kappa (rods, 3, n_elem - 1), dilatation (rods, n_elem), voronoi_dilatation (rods, n_elem - 1),
+        internal_force (rods, 3, n_elem), internal_couple (rods, 3, n_elem - 1))."""
+        r = self._vec.rod_strains()
+        return type(r)(*(t[0] for t in r))
+
     def save_data(self, filename_video, fps):
         """The reference renders `rod_parameters_dict` to a video here (soft_pendulum.py:253-256, flat_env.py:410-420);
         drawing is out of scope: the data is in `rod_parameters_dict`, nothing is written."""
@@ -622,6 +629,24 @@ class VecRodEnvBase:
             raise NotImplementedError(why)
         force, torque = be.ground_reaction()
         return self._out(force), self._out(torque)
+
+    def rod_strains(self):
+        """RodStrains(sigma, kappa, dilatation, voronoi_dilatation, internal_force, internal_couple) of every rod:
+        the strain fields the reference's RodCallBack records once per env.step (callback_func.py:23-41) and the
+        passive elastic loads they stand for — what curvature and strain gauges along the arm would sense — without
+        leaving the device.  sigma (N, rods_per_env, 3, n_elem) and kappa (N, rods_per_env, 3, n_elem - 1; not
+        reduced by the rest curvature) in the material frame, dilatation (N, rods_per_env, n_elem),
+        voronoi_dilatation (N, rods_per_env, n_elem - 1), internal_force S sigma (.., 3, n_elem), internal_couple
+        B (kappa - rest_kappa) (.., 3, n_elem - 1); on the COOMM muscle envs the loads exclude the muscle layers'
+        force and couple.  THE INSTANT is rod_energies()': the caches of the last force evaluation, or the reset
+        state for an env just reset, per env (include/softrod.h softrod_rod_strains).  Every env kind, rods of up
+        to 126 elements, tapered rods and per-env material on the HIP backend; elsewhere NotImplementedError.
+        Device tensors, views of one buffer overwritten by the next call (NumPy copies with numpy_output=True)."""
+        be = self.backend
+        if not hasattr(be, "rod_strains"):
+            raise NotImplementedError(f"rod strains need the HIP backend, not {type(be).__name__}")
+        r = be.rod_strains()
+        return type(r)(*(self._out(t) for t in r))
 
     # -- per-env material (domain randomisation) ----------------------------------------
     _MATERIAL_KEYS = ("youngs_modulus", "shear_modulus", "density", "damping_constant")

@@ -686,6 +686,38 @@ int softrod_rod_energies(softrod_handle* h, double* out, void* stream);
  * in softrod_last_error.                                                                                       */
 int softrod_ground_reaction(softrod_handle* h, double* out, void* stream);
 
+/* Rod strains: the fields the reference's diagnostic callback records once per env.step (RodCallBack,
+ * utils/custom_elastica/callback_func.py:23-41: sigma, kappa, dilatation, voronoi_dilatation — the interface this
+ * call replaces) and the internal loads they stand for, for every rod of every env, on the device: what a
+ * curvature or strain gauge senses, for a policy, a reward term or a logger that lives there.  THE FORMS are our
+ * recollection of pyelastica 1.0.0 (not on disk).  out: device [n_envs][rods_per_env][14][n_elem] float64,
+ * rods_per_env as for softrod_rod_energies (n_arm for OctoFlat and the muscle octopus, else 1; rigid bodies have
+ * no rows):
+ *   rows 0-2    sigma, the shear / stretch strain in the material frame: e Q t - (0, 0, 1)
+ *   rows 3-5    kappa = -log(Q_{k+1} Q_k^T) / D^, material frame, NOT reduced by the rest curvature
+ *   row  6      dilatation e = l / l^
+ *   row  7      voronoi_dilatation (l_k + l_{k+1}) / (2 D^)
+ *   rows 8-10   internal force n = S sigma, material frame; S from the config, the env's row of
+ *               softrod_set_env_material or the tapered rod's table (softrod_set_radius_profile), as
+ *               softrod_rod_energies picks it
+ *   rows 11-13  internal couple m = B (kappa - rest_kappa); rest_kappa only with SOFTROD_FEAT_REST_KAPPA_ACTION
+ * Rows 0-2, 6 and 8-10 hold n_elem values; rows 3-5, 7 and 11-13 live on the n_elem - 1 Voronoi vertices and
+ * their last column is written as 0.  Every column of every row is written by every call.
+ * Rows 8-13 are the PASSIVE elastic loads: on the COOMM muscle envs they exclude the muscle layers' force and
+ * couple — that law stays labelled data (DESIGN.md §3 "Muscles").  With them 1/2 sum sigma . n l^ and
+ * 1/2 sum (kappa - rest_kappa) . m D^ are the shear and bending energies of softrod_rod_energies.
+ * THE INSTANT is the one softrod_rod_energies documents, the reference's: the caches of the last force
+ * evaluation, i.e. the mid-substep configuration x - dt/2 v, R(dt/2 omega)^T Q followed by the boundary
+ * condition's constrain_values; an env whose time is 0 (just reset) is evaluated at its state as it stands.  The
+ * choice is made per env, so a batch may hold both after a masked reset.
+ * ARITHMETIC: float64 as written (IEEE division and sqrt, libm acos / sin / cos), one kernel for
+ * SOFTROD_MATH_LIBM and SOFTROD_MATH_FAST handles, the statements softrod_rod_energies evaluates.
+ * Asynchronous on `stream`, like softrod_rod_energies; capturable.  It reads the state and writes `out` only.
+ * Scope: every handle softrod_create accepts — one-slot rods up to 63 elements, two-slot rods up to 126
+ * (windowed arms included), tapered rods, every OctoFlat wave shape, per-env material.  The only errors are a
+ * null handle or a null `out`: SOFTROD_EINVAL with "rod strains: <reason>" in softrod_last_error.            */
+int softrod_rod_strains(softrod_handle* h, double* out, void* stream);
+
 /* Per-env rod material, for domain randomisation of single-rod envs.  Upstream has no counterpart: there
  * every env builds its rod with CosseratRod.straight_rod(..., density, youngs_modulus, shear_modulus) and
  * AnalyticalLinearDamper(damping_constant, ...), and a batch of them shares one softrod_config.  This call
