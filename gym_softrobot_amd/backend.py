@@ -75,6 +75,7 @@ class HipRodBackend:
         # per-handle physics tables that live outside softrod_config (action basis, spline table,
         # radius profile): their bytes go into config_fingerprint()
         self._tables: Dict[str, bytes] = {}
+        self._readouts: Dict[str, torch.Tensor] = {}     # rod_energies / ground_reaction / rod_strains buffers (_readout)
         check(self._lib.softrod_create(C.byref(self.cfg), self.device_index, C.byref(self._h)))
         if self.cfg.features & _capi.FEAT_REST_KAPPA_ACTION:
             if self.is_octo:
@@ -302,15 +303,20 @@ class HipRodBackend:
 
     supports_early_termination = True     # softrod_config.early_termination runs in the step kernels' epilogue
 
+    def _readout(self, entry: str, rods: int, *tail: int) -> torch.Tensor:
+        """One per-rod read-out softrod_<entry>: its (n_envs, rods, *tail) float64 device buffer, allocated on first
+        use and filled by the call."""
+        buf = self._readouts.get(entry)
+        if buf is None:
+            buf = self._readouts[entry] = torch.empty((self.n_envs, rods, *tail), dtype=torch.float64, device=self.device)
+        check(getattr(self._lib, "softrod_" + entry)(self._h, buf.data_ptr(), self._stream()), self._h)
+        return buf
+
     def rod_energies(self) -> torch.Tensor:
         """softrod_rod_energies: (n_envs, rods_per_env, 4) float64 device tensor — translational, rotational,
         bending, shear energy of every rod at PyElastica's instant (the mid-substep strains of the last force
         evaluation with the end-of-step rates; the state itself right after a reset).  Overwritten by the next call."""
-        if getattr(self, "_energies", None) is None:
-            self._energies = torch.empty((self.n_envs, _capi.config_rods_per_env(self.cfg), 4), dtype=torch.float64,
-                                         device=self.device)
-        check(self._lib.softrod_rod_energies(self._h, self._energies.data_ptr(), self._stream()), self._h)
-        return self._energies
+        return self._readout("rod_energies", _capi.config_rods_per_env(self.cfg), 4)
 
     def ground_reaction(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """softrod_ground_reaction: (force, torque) float64 device tensors — force (n_envs, rods_per_env, 3, n_elem + 1),
@@ -318,12 +324,9 @@ class HipRodBackend:
         n_elem), the material-frame torque it adds to every element — from ONE fresh force evaluation at the resident
         state (not the value the last substep applied: include/softrod.h).  Views of one buffer allocated on first
         use and overwritten by the next call."""
-        if getattr(self, "_reaction", None) is None:
-            rods = int(self.cfg.n_arm) if int(self.cfg.env_kind) == _capi.ENV_OCTO_FLAT else 1
-            self._reaction = torch.empty((self.n_envs, rods, 6, int(self.cfg.n_elem) + 1), dtype=torch.float64,
-                                         device=self.device)
-        check(self._lib.softrod_ground_reaction(self._h, self._reaction.data_ptr(), self._stream()), self._h)
-        return self._reaction[:, :, :3], self._reaction[:, :, 3:, :-1]
+        rods = int(self.cfg.n_arm) if int(self.cfg.env_kind) == _capi.ENV_OCTO_FLAT else 1
+        out = self._readout("ground_reaction", rods, 6, int(self.cfg.n_elem) + 1)
+        return out[:, :, :3], out[:, :, 3:, :-1]
 
     def rod_strains(self) -> RodStrains:
         """softrod_rod_strains: RodStrains(sigma, kappa, dilatation, voronoi_dilatation, internal_force,
@@ -332,11 +335,8 @@ class HipRodBackend:
         passive elastic loads S sigma, B (kappa - rest_kappa), at the instant of rod_energies() (include/softrod.h).
         Views of one (n_envs, rods_per_env, 14, n_elem) buffer allocated on first use and overwritten by the next
         call."""
-        if getattr(self, "_strains", None) is None:
-            self._strains = torch.empty((self.n_envs, _capi.config_rods_per_env(self.cfg), 14, int(self.cfg.n_elem)),
-                                        dtype=torch.float64, device=self.device)
-        check(self._lib.softrod_rod_strains(self._h, self._strains.data_ptr(), self._stream()), self._h)
-        return rod_strains_views(self._strains)
+        rods = _capi.config_rods_per_env(self.cfg)
+        return rod_strains_views(self._readout("rod_strains", rods, 14, int(self.cfg.n_elem)))
 
     def time_limit(self) -> torch.Tensor:
         """early_termination handles: the last step's time-limit flag per env (row 0 of softrod_state_view.env_aux)

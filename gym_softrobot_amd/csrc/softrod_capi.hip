@@ -44,6 +44,7 @@ struct softrod_handle {
     std::string tier;                     // softrod_kernel_tier
     RodParams P{};
     StatePtrs S{};
+    std::vector<void*> owned;     // every device buffer that lives as long as the handle (alloc_owned), for softrod_destroy
     double* d_init = nullptr;     // [N][18] staging for reset
     uint8_t* d_mask = nullptr;    // [N]
     double* d_basis = nullptr;    // [(n_elem-1)][7] action basis (zero until set)
@@ -53,11 +54,6 @@ struct softrod_handle {
     StatePtrs* d_state = nullptr;   // device copy of S (re-uploaded whenever S changes)
     double* d_time_tab = nullptr;   // clock after k env.steps from a reset (clock_after, softrod_fast.hpp)
     double* d_mat = nullptr;        // [kMatRows][64 * epl] material table of a tapered rod
-    double* d_sucker = nullptr;     // [SOFTROD_MAX_SUCKERS][N]
-    int* d_sucker_idx = nullptr;    // [SOFTROD_MAX_SUCKERS][N]
-    double* d_aux = nullptr;        // [8][N] the muscle octopus envs' target and xposbefore
-    float* d_prev_kappa = nullptr;  // [N][n_arm * (n_elem - 1)] ArmTwoEnv._prev_kappa
-    double* d_mact = nullptr;       // [SOFTROD_MAX_MUSCLES][N][64] muscle activations (SOFTROD_FEAT_COOMM_MUSCLES)
     double* d_mtab = nullptr;       // [SOFTROD_MAX_MUSCLES][4][64 * epl] ratio_position x, y, z, strength
     bool muscles_set = false;
     unsigned* d_ticket = nullptr;   // softrod_scatter_rows: blocks that have finished storing (tagged form)
@@ -271,6 +267,24 @@ bool is_pull(const softrod_handle* h) { return h->cfg.env_kind == SOFTROD_ENV_AR
 // the muscle octopus envs (softrod_mocto.hpp): FlatEnv's host API (arm frames + target), the muscle arm's tables
 bool mocto_kind(int e) { return e == SOFTROD_ENV_CRAWL || e == SOFTROD_ENV_ARM_TWO || e == SOFTROD_ENV_REACH; }
 bool is_mocto(const softrod_handle* h) { return mocto_kind(h->cfg.env_kind); }
+// the one- or the two-slot instantiation of a kernel, by the handle's slots per lane
+template <class K> K by_epl(const softrod_handle* h, K one, K two) { return h->epl == 2 ? two : one; }
+// A device buffer whose lifetime is the handle's: allocated, zero-filled and recorded for softrod_destroy.
+// On failure p stays null exactly when the allocation itself failed.
+template <class T>
+hipError_t alloc_owned(softrod_handle* h, T*& p, size_t bytes) {
+    const hipError_t e = hipMalloc((void**)&p, bytes);
+    if (e != hipSuccess) { p = nullptr; return e; }
+    h->owned.push_back(p);
+    return hipMemset(p, 0, bytes);
+}
+// Where a handle's rods lie in its resident rows (softrod_state_view): rods per env, the width of an env's row,
+// the slots between two arms of an env.
+struct RodLayout { int rods, lane_stride, arm_stride; };
+RodLayout rod_layout(const softrod_handle* h) {
+    const bool arms = is_flat(h) || is_mocto(h);
+    return {arms ? h->cfg.n_arm : 1, kLanes * h->epl * h->nw, arms ? h->P.seg : 0};
+}
 // One row of the per-env table: fill_params itself on the config with this env's (E, G, rho, nu).
 void env_material_row(const softrod_config& c, const double m[4], EnvMaterial& R) {
     softrod_config ci = c;
@@ -304,10 +318,9 @@ int launch_autoreset(softrod_handle* h, float* obs, double* reward, uint8_t* ter
     const dim3 grid((unsigned)h->cfg.n_envs), block(kLanes * h->nw);
     if (is_octo(h))
         hipLaunchKernelGGL(softrod_octo_autoreset_kernel, grid, block, 0, st, h->P, h->S, obs, reward, term, trunc, pack);
-    else if (h->epl == 2)
-        hipLaunchKernelGGL(softrod_autoreset_kernel<2>, grid, block, 0, st, h->P, h->S, obs, reward, term, trunc, aux, pack);
     else
-        hipLaunchKernelGGL(softrod_autoreset_kernel<1>, grid, block, 0, st, h->P, h->S, obs, reward, term, trunc, aux, pack);
+        hipLaunchKernelGGL(by_epl(h, softrod_autoreset_kernel<1>, softrod_autoreset_kernel<2>), grid, block, 0, st, h->P, h->S,
+                           obs, reward, term, trunc, aux, pack);
     SR_HIP(h, hipGetLastError());
     return SOFTROD_OK;
 }
@@ -604,10 +617,9 @@ int upload_and_reset(softrod_handle* h, hipStream_t st, bool use_mask) {
     if (is_octo(h)) {
         OctoResetArgs OA{h->d_init, h->d_init + N * (size_t)h->cfg.n_arm * 18, use_mask ? h->d_mask : nullptr};   // (targets: 2 numbers per env, 4 for the muscle octopus)
         hipLaunchKernelGGL(softrod_octo_reset_kernel, dim3((unsigned)N), dim3(kLanes * h->nw), 0, st, h->P, h->S, OA);
-    } else if (h->epl == 2)
-        hipLaunchKernelGGL(softrod_reset_kernel<2>, dim3((unsigned)N), dim3(kLanes), 0, st, h->P, h->S, A);
-    else
-        hipLaunchKernelGGL(softrod_reset_kernel<1>, dim3((unsigned)N), dim3(kLanes), 0, st, h->P, h->S, A);
+    } else
+        hipLaunchKernelGGL(by_epl(h, softrod_reset_kernel<1>, softrod_reset_kernel<2>), dim3((unsigned)N), dim3(kLanes), 0, st,
+                           h->P, h->S, A);
     SR_HIP(h, hipGetLastError());
     SR_HIP(h, hipEventRecord(h->ev_reset, st));
     h->was_reset = true;
@@ -654,6 +666,171 @@ void config_common(softrod_config* cfg, int n_envs) {
     cfg->eps_sin = 1e-14;
     cfg->time_two_half_adds = 1;
     cfg->damp_before_constrain = 0;   // constrain() is registered before dampen() in both builds
+}
+
+// softrod_create's checks of the config, in order: the first reason to refuse it, nullptr when there is none.  No HIP
+// call and no handle: what is refused here is refused on a host without a device too.
+const char* config_why_not(const softrod_config& c) {
+    if (c.n_envs < 1 || c.n_elem < 2 || c.n_elem > 2 * kLanes - 2)
+        return "need n_envs >= 1 and 2 <= n_elem <= 126";
+    if (c.n_elem > kLanes - 1 && c.math_mode != SOFTROD_MATH_FAST)
+        return "rods longer than 63 elements (two per lane) exist for SOFTROD_MATH_FAST only";
+    if (c.n_substeps < 0 || !(c.dt > 0.0))
+        return "need n_substeps >= 0 and dt > 0";
+    if (c.math_mode != SOFTROD_MATH_LIBM && c.math_mode != SOFTROD_MATH_FAST)
+        return "unknown math_mode";
+    if (c.env_kind < SOFTROD_ENV_NONE || c.env_kind > SOFTROD_ENV_REACH)
+        return "unknown env_kind";
+    if (c.features & SOFTROD_FEAT_COOMM_MUSCLES) {
+        // two slots per lane (64..126 elements): the tapered ArmPush arm's own instantiations only
+        const bool two_slot_push = c.features == SOFTROD_FEATURES_ARM_PUSH && c.env_kind == SOFTROD_ENV_ARM_PUSH &&
+                                   c.math_mode == SOFTROD_MATH_FAST;
+        if (c.n_muscles < 1 || c.n_muscles > SOFTROD_MAX_MUSCLES || c.muscle_fl_degree < 0 ||
+            c.muscle_fl_degree >= SOFTROD_MAX_FL_COEF || (c.n_elem > kLanes - 1 && !two_slot_push) ||
+            ((c.features & SOFTROD_FEAT_OCTO_HEAD) && c.env_kind != SOFTROD_ENV_ARM_PULL_WEIGHT && !mocto_kind(c.env_kind)))
+            return "COOMM muscles: 1 <= n_muscles <= 4, 0 <= muscle_fl_degree <= 7, one rod of up to 63 elements per env";
+        for (int m = 0; m < c.n_muscles; ++m)
+            if (c.muscle_kind[m] != SOFTROD_MUSCLE_LONGITUDINAL && c.muscle_kind[m] != SOFTROD_MUSCLE_TRANSVERSE)
+                return "muscle_kind: SOFTROD_MUSCLE_LONGITUDINAL or SOFTROD_MUSCLE_TRANSVERSE";
+        if ((c.muscle_equiv_load_form | 1) != 1 || (c.muscle_position_current_radius | 1) != 1 ||
+            (c.muscle_tm_length_law | 1) != 1)
+            return "muscle_equiv_load_form, muscle_position_current_radius, muscle_tm_length_law: 0 or 1";
+    }
+    if ((c.features & SOFTROD_FEAT_COOMM_MUSCLES) && c.math_mode == SOFTROD_MATH_FAST &&
+        !((c.features == SOFTROD_FEATURES_ARM_PUSH && c.env_kind == SOFTROD_ENV_ARM_PUSH) ||
+          (c.features == SOFTROD_FEATURES_ARM_PULL_WEIGHT && (c.env_kind == SOFTROD_ENV_ARM_PULL_WEIGHT || mocto_kind(c.env_kind))) ||
+          (c.features == kFeaturesMuscleRod && c.env_kind == SOFTROD_ENV_NONE)))
+        return "SOFTROD_MATH_FAST compiles the COOMM muscles for SOFTROD_FEATURES_ARM_PUSH with SOFTROD_ENV_ARM_PUSH "
+                    "(tapered) and for FIXED_BC | ANALYTICAL_DAMPER | COOMM_MUSCLES with SOFTROD_ENV_NONE (uniform rod); "
+                    "use SOFTROD_MATH_LIBM for any other mix";
+    if (c.env_kind == SOFTROD_ENV_ARM_PULL_WEIGHT &&
+        (c.features != SOFTROD_FEATURES_ARM_PULL_WEIGHT || c.math_mode != SOFTROD_MATH_FAST || c.n_arm != 1 ||
+         !(c.head_length > 0.0) || !(c.head_radius > 0.0) || !(c.head_density > 0.0)))
+        return "SOFTROD_ENV_ARM_PULL_WEIGHT: SOFTROD_FEATURES_ARM_PULL_WEIGHT, SOFTROD_MATH_FAST, n_arm = 1, "
+                                             "head_length / head_radius / head_density > 0";
+    if (c.env_kind == SOFTROD_ENV_ARM_PUSH || c.env_kind == SOFTROD_ENV_ARM_PULL_WEIGHT) {
+        const unsigned need = SOFTROD_FEAT_COOMM_MUSCLES | SOFTROD_FEAT_SUCKER_CONSTRAINT;
+        if ((c.features & need) != need || c.n_muscles < 3 || (c.arm_push_mode != 0 && c.arm_push_mode != 1))
+            return "SOFTROD_ENV_ARM_PUSH needs the sucker constraint, three muscle layers and arm_push_mode 0 or 1";
+    }
+    if (c.damper_protocol != 0 && c.damper_protocol != 1)
+        return "damper_protocol: 0 (per unit mass) or 1 (uniform)";
+    // The fast kernels expand theta / sin(theta + eps_sin) as (theta / sin theta)(1 - eps_sin cot theta)
+    // (eps_sin_factor, softrod_fast.hpp; the bke * rsq(D^2 + two_shift) term of softrod_planar.hpp), which
+    // holds while eps_sin << theta_min = sqrt(2 acos_shift), the smallest angle acos(.. - acos_shift)
+    // returns.  The reference's values (1e-14 against 1.4e-5) sit nine orders inside; a config outside
+    // — acos_shift = 0 with a straight joint sends cot theta to 1e150 and flips the sign of the bending
+    // stiffness — is refused here rather than integrated wrongly (the libm kernel evaluates the
+    // quotient as written and takes any values).
+    if (c.math_mode == SOFTROD_MATH_FAST &&
+        !(c.acos_shift > 0.0 && c.eps_sin >= 0.0 && c.eps_sin <= 1.0e-3 * std::sqrt(2.0 * c.acos_shift)))
+        return "SOFTROD_MATH_FAST needs acos_shift > 0 and 0 <= eps_sin <= 1e-3 sqrt(2 acos_shift); "
+                    "use SOFTROD_MATH_LIBM for other values";
+    {
+        const bool muscles = (c.features & SOFTROD_FEAT_SPLINE_MUSCLE_TORQUES) != 0;
+        if (muscles != (c.env_kind == SOFTROD_ENV_SOFT_ARM))
+            return "SOFTROD_FEAT_SPLINE_MUSCLE_TORQUES and SOFTROD_ENV_SOFT_ARM go together";
+        if (muscles && (c.math_mode != SOFTROD_MATH_FAST || c.n_ctrl < 1 || c.n_ctrl > 4 ||
+                        c.n_spline_pieces < 1 || c.n_spline_pieces > SOFTROD_MAX_SPLINE_PIECES ||
+                        c.n_elem - 1 < c.n_ctrl || !(c.max_activation_rate > 0.0)))
+            return "spline muscles need SOFTROD_MATH_FAST, 1 <= n_ctrl <= 4, 1 <= n_spline_pieces <= 8, "
+                        "max_activation_rate > 0";
+    }
+    const bool octo = (c.features & SOFTROD_FEAT_OCTO_HEAD) != 0;
+    const bool pull = c.env_kind == SOFTROD_ENV_ARM_PULL_WEIGHT;
+    const bool mocto = mocto_kind(c.env_kind);
+    if (octo != (c.env_kind == SOFTROD_ENV_OCTO_FLAT || pull || mocto))
+        return "SOFTROD_FEAT_OCTO_HEAD goes with SOFTROD_ENV_OCTO_FLAT, SOFTROD_ENV_ARM_PULL_WEIGHT "
+                                             "or the muscle octopus envs";
+    if (mocto) {
+        // n_arm * 32 slots = 1 or 4 whole waves, so that every slot of the block belongs to an arm
+        if (c.features != SOFTROD_FEATURES_ARM_PULL_WEIGHT || c.math_mode != SOFTROD_MATH_FAST)
+            return "the muscle octopus exists for SOFTROD_FEATURES_ARM_PULL_WEIGHT and SOFTROD_MATH_FAST only";
+        if (c.n_elem < 16 || c.n_elem > 31 || (c.n_arm != 2 && c.n_arm != 8) || c.n_muscles != 3)
+            return "the muscle octopus needs 16 <= n_elem <= 31, n_arm = 2 or 8, three muscle layers";
+        const int nk = c.env_kind == SOFTROD_ENV_CRAWL ? 3 : (c.env_kind == SOFTROD_ENV_ARM_TWO ? 9 : 3 * c.n_elem);
+        if (c.n_knots != nk || (c.env_kind == SOFTROD_ENV_ARM_TWO && c.n_suckers != 3) ||
+            (c.env_kind == SOFTROD_ENV_CRAWL && c.n_suckers != 1) || (c.env_kind == SOFTROD_ENV_REACH && c.n_suckers != 0))
+            return "the muscle octopus: n_knots (actions per arm) 3 / 9 / 3 n_elem and n_suckers 1 / 3 / 0 "
+                                                 "for CRAWL / ARM_TWO / REACH";
+        if (!(c.head_radius > 0.0) || !(c.head_density > 0.0) || !(c.head_length > 0.0))
+            return "the muscle octopus needs head_radius, head_density, head_length > 0";
+    }
+    if (octo && !pull && !mocto) {
+        if (c.features != SOFTROD_FEATURES_OCTO_FLAT || c.math_mode != SOFTROD_MATH_FAST)
+            return "OctoFlat exists for SOFTROD_FEATURES_OCTO_FLAT and SOFTROD_MATH_FAST only";
+        if (c.n_elem > kLanes - 1 || c.n_arm < 1 || c.n_knots < 1 || c.n_knots > c.n_elem ||
+            (c.n_elem - 1) * c.n_knots > 2 * kLanes * 7)
+            return "OctoFlat needs n_elem <= 63, n_arm >= 1, 1 <= n_knots <= n_elem";
+        const int seg = c.n_elem <= 15 ? 16 : (c.n_elem <= 31 ? 32 : 64);
+        if (c.n_arm * seg > 8 * kLanes)
+            return "OctoFlat: n_arm * slots-per-arm must not exceed 512";
+        if (!(c.head_radius > 0.0) || !(c.head_density > 0.0))
+            return "OctoFlat needs head_radius > 0 and head_density > 0";
+    }
+    if (c.features & SOFTROD_FEAT_SUCKER_CONSTRAINT) {
+        if ((octo && !pull && !mocto) || c.n_suckers < (mocto ? 0 : 1) || c.n_suckers > SOFTROD_MAX_SUCKERS)
+            return "ControllableFixConstraint: 1 <= n_suckers <= 4, not with OctoFlat";
+        for (int j = 0; j < c.n_suckers; ++j)
+            if (c.sucker_index[j] < 0 || c.sucker_index[j] >= c.n_elem)
+                return "ControllableFixConstraint: 0 <= sucker_index < n_elem";
+    }
+    if ((c.features & SOFTROD_FEAT_LAPLACE_FILTER) && (c.filter_order < 1 || c.n_elem < 3))
+        return "LaplaceDissipationFilter needs filter_order >= 1";
+    if (c.early_termination != 0 && c.early_termination != 1)
+        return "early_termination is 0 or 1";
+    if (c.early_termination && c.env_kind != SOFTROD_ENV_ARM_PUSH && c.env_kind != SOFTROD_ENV_ARM_PULL_WEIGHT)
+        return "early_termination (ArmPushEnv's Hamiltonian cut-off) exists for SOFTROD_ENV_ARM_PUSH / ARM_PULL_WEIGHT only";
+    {
+        const unsigned bcs = c.features & (SOFTROD_FEAT_PENDULUM_BC | SOFTROD_FEAT_FIXED_BC |
+                                              SOFTROD_FEAT_MOVING_BASE_BC);
+        if (bcs & (bcs - 1)) return "at most one boundary condition";
+    }
+    return nullptr;
+}
+
+// The clock after k env.steps from a reset, k = 0..1023, as `self.time = self.do_step(self.simulator, self.time,
+// self.time_step)` accumulates it (soft_pendulum.py:183-184): same additions, same order, IEEE doubles -> bit-identical
+std::vector<double> clock_table(const softrod_config& c) {
+    std::vector<double> tab(1024);
+    double t = 0.0;
+    const double half = 0.5 * c.dt;
+    for (double& at : tab) {
+        at = t;
+        for (int s = 0; s < c.n_substeps; ++s) {
+            if (c.time_two_half_adds) { t = t + half; t = t + half; }
+            else t = t + c.dt;
+        }
+    }
+    return tab;
+}
+
+// What follows from the config alone: RodParams, slots per lane, waves per env, the reset record, the two-window form.
+void shape_handle(softrod_handle* h) {
+    const softrod_config* cfg = &h->cfg;
+    h->epl = cfg->n_elem > kLanes - 1 ? 2 : 1;
+    fill_params(h->cfg, h->P);
+    if (is_octo(h)) {
+        h->nw = (cfg->n_arm * h->P.seg + kLanes - 1) / kLanes;
+        h->init_stride = (size_t)cfg->n_arm * 18 + (is_mocto(h) ? 4 : 2);
+    }
+    // A/B switches for profiling and tests.  A product library must not change its kernel tier because of a
+    // stray environment variable: they are read only when SOFTROD_DEBUG_SWITCHES=1 is set as well
+    // (tests/test_gpu_debug_switches.py), and softrod_kernel_tier() reports what was selected.
+    const char* dbg = std::getenv("SOFTROD_DEBUG_SWITCHES");
+    const bool debug_switches = dbg && dbg[0] == '1';
+    auto debug_env = [&](const char* name) -> const char* { return debug_switches ? std::getenv(name) : nullptr; };
+    if (const char* one = debug_env("SOFTROD_WINDOW_PAIRED"))              // softrod_window.hpp
+        h->window_paired = one[0] != '0';
+    {   // two-window form: ArmSingle with the e_z contact, 64..102 elements
+        const int halo = kLanes - (cfg->n_elem + 2) / 2;     // the narrower of the two halos
+        const char* off = debug_env("SOFTROD_NO_WINDOW");
+        if (h->epl == 2 && cfg->features == SOFTROD_FEATURES_ARM_SINGLE && cfg->env_kind == SOFTROD_ENV_ARM_SINGLE &&
+            cfg->math_mode == SOFTROD_MATH_FAST && (h->P.features & kFeatPlaneZup) && !(off && off[0] == '1') &&
+            halo >= 3 * kWindowRho)
+            h->window_refresh = halo / kWindowRho;    // the front (< 3.25 nodes per substep) stays in the halo
+        if (const char* r = debug_env("SOFTROD_WINDOW_REFRESH")) if (h->window_refresh > 0) h->window_refresh = std::atoi(r);
+    }
 }
 
 }  // namespace
@@ -917,130 +1094,7 @@ int softrod_create(const softrod_config* cfg, int device, softrod_handle** out) 
     *out = nullptr;
     if (cfg->struct_size != sizeof(softrod_config))
         return fail(nullptr, SOFTROD_EINVAL, "softrod_config.struct_size mismatch");
-    if (cfg->n_envs < 1 || cfg->n_elem < 2 || cfg->n_elem > 2 * kLanes - 2)
-        return fail(nullptr, SOFTROD_EINVAL, "need n_envs >= 1 and 2 <= n_elem <= 126");
-    if (cfg->n_elem > kLanes - 1 && cfg->math_mode != SOFTROD_MATH_FAST)
-        return fail(nullptr, SOFTROD_EINVAL,
-                    "rods longer than 63 elements (two per lane) exist for SOFTROD_MATH_FAST only");
-    if (cfg->n_substeps < 0 || !(cfg->dt > 0.0))
-        return fail(nullptr, SOFTROD_EINVAL, "need n_substeps >= 0 and dt > 0");
-    if (cfg->math_mode != SOFTROD_MATH_LIBM && cfg->math_mode != SOFTROD_MATH_FAST)
-        return fail(nullptr, SOFTROD_EINVAL, "unknown math_mode");
-    if (cfg->env_kind < SOFTROD_ENV_NONE || cfg->env_kind > SOFTROD_ENV_REACH)
-        return fail(nullptr, SOFTROD_EINVAL, "unknown env_kind");
-    if (cfg->features & SOFTROD_FEAT_COOMM_MUSCLES) {
-        // two slots per lane (64..126 elements): the tapered ArmPush arm's own instantiations only
-        const bool two_slot_push = cfg->features == SOFTROD_FEATURES_ARM_PUSH && cfg->env_kind == SOFTROD_ENV_ARM_PUSH &&
-                                   cfg->math_mode == SOFTROD_MATH_FAST;
-        if (cfg->n_muscles < 1 || cfg->n_muscles > SOFTROD_MAX_MUSCLES || cfg->muscle_fl_degree < 0 ||
-            cfg->muscle_fl_degree >= SOFTROD_MAX_FL_COEF || (cfg->n_elem > kLanes - 1 && !two_slot_push) ||
-            ((cfg->features & SOFTROD_FEAT_OCTO_HEAD) && cfg->env_kind != SOFTROD_ENV_ARM_PULL_WEIGHT && !mocto_kind(cfg->env_kind)))
-            return fail(nullptr, SOFTROD_EINVAL,
-                        "COOMM muscles: 1 <= n_muscles <= 4, 0 <= muscle_fl_degree <= 7, one rod of up to 63 elements per env");
-        for (int m = 0; m < cfg->n_muscles; ++m)
-            if (cfg->muscle_kind[m] != SOFTROD_MUSCLE_LONGITUDINAL && cfg->muscle_kind[m] != SOFTROD_MUSCLE_TRANSVERSE)
-                return fail(nullptr, SOFTROD_EINVAL, "muscle_kind: SOFTROD_MUSCLE_LONGITUDINAL or SOFTROD_MUSCLE_TRANSVERSE");
-        if ((cfg->muscle_equiv_load_form | 1) != 1 || (cfg->muscle_position_current_radius | 1) != 1 ||
-            (cfg->muscle_tm_length_law | 1) != 1)
-            return fail(nullptr, SOFTROD_EINVAL, "muscle_equiv_load_form, muscle_position_current_radius, muscle_tm_length_law: 0 or 1");
-    }
-    if ((cfg->features & SOFTROD_FEAT_COOMM_MUSCLES) && cfg->math_mode == SOFTROD_MATH_FAST &&
-        !((cfg->features == SOFTROD_FEATURES_ARM_PUSH && cfg->env_kind == SOFTROD_ENV_ARM_PUSH) ||
-          (cfg->features == SOFTROD_FEATURES_ARM_PULL_WEIGHT && (cfg->env_kind == SOFTROD_ENV_ARM_PULL_WEIGHT || mocto_kind(cfg->env_kind))) ||
-          (cfg->features == kFeaturesMuscleRod && cfg->env_kind == SOFTROD_ENV_NONE)))
-        return fail(nullptr, SOFTROD_EINVAL,
-                    "SOFTROD_MATH_FAST compiles the COOMM muscles for SOFTROD_FEATURES_ARM_PUSH with SOFTROD_ENV_ARM_PUSH "
-                    "(tapered) and for FIXED_BC | ANALYTICAL_DAMPER | COOMM_MUSCLES with SOFTROD_ENV_NONE (uniform rod); "
-                    "use SOFTROD_MATH_LIBM for any other mix");
-    if (cfg->env_kind == SOFTROD_ENV_ARM_PULL_WEIGHT &&
-        (cfg->features != SOFTROD_FEATURES_ARM_PULL_WEIGHT || cfg->math_mode != SOFTROD_MATH_FAST || cfg->n_arm != 1 ||
-         !(cfg->head_length > 0.0) || !(cfg->head_radius > 0.0) || !(cfg->head_density > 0.0)))
-        return fail(nullptr, SOFTROD_EINVAL, "SOFTROD_ENV_ARM_PULL_WEIGHT: SOFTROD_FEATURES_ARM_PULL_WEIGHT, SOFTROD_MATH_FAST, n_arm = 1, "
-                                             "head_length / head_radius / head_density > 0");
-    if (cfg->env_kind == SOFTROD_ENV_ARM_PUSH || cfg->env_kind == SOFTROD_ENV_ARM_PULL_WEIGHT) {
-        const unsigned need = SOFTROD_FEAT_COOMM_MUSCLES | SOFTROD_FEAT_SUCKER_CONSTRAINT;
-        if ((cfg->features & need) != need || cfg->n_muscles < 3 || (cfg->arm_push_mode != 0 && cfg->arm_push_mode != 1))
-            return fail(nullptr, SOFTROD_EINVAL,
-                        "SOFTROD_ENV_ARM_PUSH needs the sucker constraint, three muscle layers and arm_push_mode 0 or 1");
-    }
-    if (cfg->damper_protocol != 0 && cfg->damper_protocol != 1)
-        return fail(nullptr, SOFTROD_EINVAL, "damper_protocol: 0 (per unit mass) or 1 (uniform)");
-    // The fast kernels expand theta / sin(theta + eps_sin) as (theta / sin theta)(1 - eps_sin cot theta)
-    // (eps_sin_factor, softrod_fast.hpp; the bke * rsq(D^2 + two_shift) term of softrod_planar.hpp), which
-    // holds while eps_sin << theta_min = sqrt(2 acos_shift), the smallest angle acos(.. - acos_shift)
-    // returns.  The reference's values (1e-14 against 1.4e-5) sit nine orders inside; a config outside
-    // — acos_shift = 0 with a straight joint sends cot theta to 1e150 and flips the sign of the bending
-    // stiffness — is refused here rather than integrated wrongly (the libm kernel evaluates the
-    // quotient as written and takes any values).
-    if (cfg->math_mode == SOFTROD_MATH_FAST &&
-        !(cfg->acos_shift > 0.0 && cfg->eps_sin >= 0.0 && cfg->eps_sin <= 1.0e-3 * std::sqrt(2.0 * cfg->acos_shift)))
-        return fail(nullptr, SOFTROD_EINVAL,
-                    "SOFTROD_MATH_FAST needs acos_shift > 0 and 0 <= eps_sin <= 1e-3 sqrt(2 acos_shift); "
-                    "use SOFTROD_MATH_LIBM for other values");
-    {
-        const bool muscles = (cfg->features & SOFTROD_FEAT_SPLINE_MUSCLE_TORQUES) != 0;
-        if (muscles != (cfg->env_kind == SOFTROD_ENV_SOFT_ARM))
-            return fail(nullptr, SOFTROD_EINVAL,
-                        "SOFTROD_FEAT_SPLINE_MUSCLE_TORQUES and SOFTROD_ENV_SOFT_ARM go together");
-        if (muscles && (cfg->math_mode != SOFTROD_MATH_FAST || cfg->n_ctrl < 1 || cfg->n_ctrl > 4 ||
-                        cfg->n_spline_pieces < 1 || cfg->n_spline_pieces > SOFTROD_MAX_SPLINE_PIECES ||
-                        cfg->n_elem - 1 < cfg->n_ctrl || !(cfg->max_activation_rate > 0.0)))
-            return fail(nullptr, SOFTROD_EINVAL,
-                        "spline muscles need SOFTROD_MATH_FAST, 1 <= n_ctrl <= 4, 1 <= n_spline_pieces <= 8, "
-                        "max_activation_rate > 0");
-    }
-    const bool octo = (cfg->features & SOFTROD_FEAT_OCTO_HEAD) != 0;
-    const bool pull = cfg->env_kind == SOFTROD_ENV_ARM_PULL_WEIGHT;
-    const bool mocto = mocto_kind(cfg->env_kind);
-    if (octo != (cfg->env_kind == SOFTROD_ENV_OCTO_FLAT || pull || mocto))
-        return fail(nullptr, SOFTROD_EINVAL, "SOFTROD_FEAT_OCTO_HEAD goes with SOFTROD_ENV_OCTO_FLAT, SOFTROD_ENV_ARM_PULL_WEIGHT "
-                                             "or the muscle octopus envs");
-    if (mocto) {
-        // n_arm * 32 slots = 1 or 4 whole waves, so that every slot of the block belongs to an arm
-        if (cfg->features != SOFTROD_FEATURES_ARM_PULL_WEIGHT || cfg->math_mode != SOFTROD_MATH_FAST)
-            return fail(nullptr, SOFTROD_EINVAL, "the muscle octopus exists for SOFTROD_FEATURES_ARM_PULL_WEIGHT and SOFTROD_MATH_FAST only");
-        if (cfg->n_elem < 16 || cfg->n_elem > 31 || (cfg->n_arm != 2 && cfg->n_arm != 8) || cfg->n_muscles != 3)
-            return fail(nullptr, SOFTROD_EINVAL, "the muscle octopus needs 16 <= n_elem <= 31, n_arm = 2 or 8, three muscle layers");
-        const int nk = cfg->env_kind == SOFTROD_ENV_CRAWL ? 3 : (cfg->env_kind == SOFTROD_ENV_ARM_TWO ? 9 : 3 * cfg->n_elem);
-        if (cfg->n_knots != nk || (cfg->env_kind == SOFTROD_ENV_ARM_TWO && cfg->n_suckers != 3) ||
-            (cfg->env_kind == SOFTROD_ENV_CRAWL && cfg->n_suckers != 1) || (cfg->env_kind == SOFTROD_ENV_REACH && cfg->n_suckers != 0))
-            return fail(nullptr, SOFTROD_EINVAL, "the muscle octopus: n_knots (actions per arm) 3 / 9 / 3 n_elem and n_suckers 1 / 3 / 0 "
-                                                 "for CRAWL / ARM_TWO / REACH");
-        if (!(cfg->head_radius > 0.0) || !(cfg->head_density > 0.0) || !(cfg->head_length > 0.0))
-            return fail(nullptr, SOFTROD_EINVAL, "the muscle octopus needs head_radius, head_density, head_length > 0");
-    }
-    if (octo && !pull && !mocto) {
-        if (cfg->features != SOFTROD_FEATURES_OCTO_FLAT || cfg->math_mode != SOFTROD_MATH_FAST)
-            return fail(nullptr, SOFTROD_EINVAL,
-                        "OctoFlat exists for SOFTROD_FEATURES_OCTO_FLAT and SOFTROD_MATH_FAST only");
-        if (cfg->n_elem > kLanes - 1 || cfg->n_arm < 1 || cfg->n_knots < 1 || cfg->n_knots > cfg->n_elem ||
-            (cfg->n_elem - 1) * cfg->n_knots > 2 * kLanes * 7)
-            return fail(nullptr, SOFTROD_EINVAL, "OctoFlat needs n_elem <= 63, n_arm >= 1, 1 <= n_knots <= n_elem");
-        const int seg = cfg->n_elem <= 15 ? 16 : (cfg->n_elem <= 31 ? 32 : 64);
-        if (cfg->n_arm * seg > 8 * kLanes)
-            return fail(nullptr, SOFTROD_EINVAL, "OctoFlat: n_arm * slots-per-arm must not exceed 512");
-        if (!(cfg->head_radius > 0.0) || !(cfg->head_density > 0.0))
-            return fail(nullptr, SOFTROD_EINVAL, "OctoFlat needs head_radius > 0 and head_density > 0");
-    }
-    if (cfg->features & SOFTROD_FEAT_SUCKER_CONSTRAINT) {
-        if ((octo && !pull && !mocto) || cfg->n_suckers < (mocto ? 0 : 1) || cfg->n_suckers > SOFTROD_MAX_SUCKERS)
-            return fail(nullptr, SOFTROD_EINVAL, "ControllableFixConstraint: 1 <= n_suckers <= 4, not with OctoFlat");
-        for (int j = 0; j < cfg->n_suckers; ++j)
-            if (cfg->sucker_index[j] < 0 || cfg->sucker_index[j] >= cfg->n_elem)
-                return fail(nullptr, SOFTROD_EINVAL, "ControllableFixConstraint: 0 <= sucker_index < n_elem");
-    }
-    if ((cfg->features & SOFTROD_FEAT_LAPLACE_FILTER) && (cfg->filter_order < 1 || cfg->n_elem < 3))
-        return fail(nullptr, SOFTROD_EINVAL, "LaplaceDissipationFilter needs filter_order >= 1");
-    if (cfg->early_termination != 0 && cfg->early_termination != 1)
-        return fail(nullptr, SOFTROD_EINVAL, "early_termination is 0 or 1");
-    if (cfg->early_termination && cfg->env_kind != SOFTROD_ENV_ARM_PUSH && cfg->env_kind != SOFTROD_ENV_ARM_PULL_WEIGHT)
-        return fail(nullptr, SOFTROD_EINVAL,
-                    "early_termination (ArmPushEnv's Hamiltonian cut-off) exists for SOFTROD_ENV_ARM_PUSH / ARM_PULL_WEIGHT only");
-    {
-        const unsigned bcs = cfg->features & (SOFTROD_FEAT_PENDULUM_BC | SOFTROD_FEAT_FIXED_BC |
-                                              SOFTROD_FEAT_MOVING_BASE_BC);
-        if (bcs & (bcs - 1)) return fail(nullptr, SOFTROD_EINVAL, "at most one boundary condition");
-    }
+    if (const char* why = config_why_not(*cfg)) return fail(nullptr, SOFTROD_EINVAL, why);
     int ndev = 0;
     const hipError_t cnt_err = hipGetDeviceCount(&ndev);
     if (cnt_err != hipSuccess || ndev < 1)
@@ -1052,132 +1106,83 @@ int softrod_create(const softrod_config* cfg, int device, softrod_handle** out) 
     if (!h) return fail(nullptr, SOFTROD_ENOMEM, "host allocation failed");
     h->cfg = *cfg;
     h->device = device;
-    h->epl = cfg->n_elem > kLanes - 1 ? 2 : 1;
-    fill_params(h->cfg, h->P);
+    shape_handle(h);
+    const bool mocto = is_mocto(h);
     const size_t N = (size_t)cfg->n_envs;
-    if (octo) {
-        h->nw = (cfg->n_arm * h->P.seg + kLanes - 1) / kLanes;
-        h->init_stride = (size_t)cfg->n_arm * 18 + (mocto ? 4 : 2);
-    }
-    // A/B switches for profiling and tests.  A product library must not change its kernel tier because of a
-    // stray environment variable: they are read only when SOFTROD_DEBUG_SWITCHES=1 is set as well
-    // (tests/test_gpu_debug_switches.py), and softrod_kernel_tier() reports what was selected.
-    const char* dbg = std::getenv("SOFTROD_DEBUG_SWITCHES");
-    const bool debug_switches = dbg && dbg[0] == '1';
-    auto debug_env = [&](const char* name) -> const char* { return debug_switches ? std::getenv(name) : nullptr; };
-    if (const char* one = debug_env("SOFTROD_WINDOW_PAIRED"))              // softrod_window.hpp
-        h->window_paired = one[0] != '0';
-    {   // two-window form: ArmSingle with the e_z contact, 64..102 elements
-        const int halo = kLanes - (cfg->n_elem + 2) / 2;     // the narrower of the two halos
-        const char* off = debug_env("SOFTROD_NO_WINDOW");
-        if (h->epl == 2 && cfg->features == SOFTROD_FEATURES_ARM_SINGLE && cfg->env_kind == SOFTROD_ENV_ARM_SINGLE &&
-            cfg->math_mode == SOFTROD_MATH_FAST && (h->P.features & kFeatPlaneZup) && !(off && off[0] == '1') &&
-            halo >= 3 * kWindowRho)
-            h->window_refresh = halo / kWindowRho;    // the front (< 3.25 nodes per substep) stays in the halo
-        if (const char* r = debug_env("SOFTROD_WINDOW_REFRESH")) if (h->window_refresh > 0) h->window_refresh = std::atoi(r);
-    }
     const size_t adim = (size_t)softrod_config_action_dim(cfg);
     const size_t rowb = N * kLanes * h->epl * h->nw * sizeof(double);
     int rc = SOFTROD_OK;
-    auto alloc = [&](void** p, size_t bytes) {
-        if (rc != SOFTROD_OK) return;
-        if (hipMalloc(p, bytes) != hipSuccess) { rc = SOFTROD_ENOMEM; return; }
-        if (hipMemset(*p, 0, bytes) != hipSuccess) rc = SOFTROD_EHIP;
+    auto alloc = [&](auto*& p, size_t bytes) {
+        if (rc == SOFTROD_OK && alloc_owned(h, p, bytes) != hipSuccess) rc = p ? SOFTROD_EHIP : SOFTROD_ENOMEM;
+    };
+    auto upload = [&](void* dst, const void* src, size_t bytes) {
+        if (rc == SOFTROD_OK && hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = SOFTROD_EHIP;
     };
     DeviceGuard guard_(device);
     if (guard_.err != hipSuccess) rc = SOFTROD_EHIP;
-    alloc((void**)&h->S.pos, 3 * rowb);
-    alloc((void**)&h->S.vel, 3 * rowb);
-    alloc((void**)&h->S.dir, 9 * rowb);
-    alloc((void**)&h->S.omg, 3 * rowb);
-    alloc((void**)&h->S.tan, 3 * rowb);
-    alloc((void**)&h->S.time, N * sizeof(double));
-    alloc((void**)&h->S.bc, 12 * N * sizeof(double));
-    alloc((void**)&h->S.ctrl, 4 * N * sizeof(double));
-    alloc((void**)&h->S.kap, 3 * rowb);
-    alloc((void**)&h->S.rkap, 3 * rowb);
-    alloc((void**)&h->S.envmem, rowb);
-    alloc((void**)&h->S.prev_action, N * (adim > 7 ? adim : 7) * sizeof(float));
-    alloc((void**)&h->S.head, 20 * N * sizeof(double));
-    alloc((void**)&h->d_spline, (size_t)(SOFTROD_MAX_SPLINE_PIECES + 1 + SOFTROD_MAX_SPLINE_PIECES * 4 * 4) * sizeof(double));
+    alloc(h->S.pos, 3 * rowb);
+    alloc(h->S.vel, 3 * rowb);
+    alloc(h->S.dir, 9 * rowb);
+    alloc(h->S.omg, 3 * rowb);
+    alloc(h->S.tan, 3 * rowb);
+    alloc(h->S.time, N * sizeof(double));
+    alloc(h->S.bc, 12 * N * sizeof(double));
+    alloc(h->S.ctrl, 4 * N * sizeof(double));
+    alloc(h->S.kap, 3 * rowb);
+    alloc(h->S.rkap, 3 * rowb);
+    alloc(h->S.envmem, rowb);
+    alloc(h->S.prev_action, N * (adim > 7 ? adim : 7) * sizeof(float));
+    alloc(h->S.head, 20 * N * sizeof(double));
+    alloc(h->d_spline, (size_t)(SOFTROD_MAX_SPLINE_PIECES + 1 + SOFTROD_MAX_SPLINE_PIECES * 4 * 4) * sizeof(double));
     h->P.spline = h->d_spline;
-    alloc((void**)&h->d_ticket, sizeof(unsigned));    // softrod_scatter_rows' arrival counter, zero
-    alloc((void**)&h->d_params, sizeof(RodParams));
-    if (rc == SOFTROD_OK && hipMemcpy(h->d_params, &h->P, sizeof(RodParams), hipMemcpyHostToDevice) != hipSuccess)
-        rc = SOFTROD_EHIP;
+    alloc(h->d_ticket, sizeof(unsigned));    // softrod_scatter_rows' arrival counter, zero
+    alloc(h->d_params, sizeof(RodParams));
     h->S.params = h->d_params;
-    alloc((void**)&h->d_state, sizeof(StatePtrs));
+    alloc(h->d_state, sizeof(StatePtrs));
     h->S.self = h->d_state;
-    if (rc == SOFTROD_OK && cfg->n_substeps > 0) {
-        // the clock as `self.time = self.do_step(self.simulator, self.time, self.time_step)` accumulates it
-        // (soft_pendulum.py:183-184): same additions, same order, IEEE doubles -> bit-identical
-        constexpr int kTab = 1024;
-        std::vector<double> tab((size_t)kTab);
-        double t = 0.0;
-        const double half = 0.5 * cfg->dt;
-        for (int k = 0; k < kTab; ++k) {
-            tab[(size_t)k] = t;
-            for (int s = 0; s < cfg->n_substeps; ++s) {
-                if (cfg->time_two_half_adds) { t = t + half; t = t + half; }
-                else t = t + cfg->dt;
-            }
-        }
-        alloc((void**)&h->d_time_tab, tab.size() * sizeof(double));
-        if (rc == SOFTROD_OK && hipMemcpy(h->d_time_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-            rc = SOFTROD_EHIP;
+    if (cfg->n_substeps > 0) {
+        const std::vector<double> tab = clock_table(*cfg);
+        alloc(h->d_time_tab, tab.size() * sizeof(double));
+        upload(h->d_time_tab, tab.data(), tab.size() * sizeof(double));
         h->S.time_tab = h->d_time_tab;
-        h->P.tab_len = kTab;
+        h->P.tab_len = (int)tab.size();
         h->P.tab_n_sub = cfg->n_substeps;
         h->P.inv_step_time = 1.0 / ((double)cfg->n_substeps * cfg->dt);
-        if (rc == SOFTROD_OK && hipMemcpy(h->d_params, &h->P, sizeof(RodParams), hipMemcpyHostToDevice) != hipSuccess)
-            rc = SOFTROD_EHIP;
     }
+    upload(h->d_params, &h->P, sizeof(RodParams));
     const size_t NS = N * (size_t)(mocto ? cfg->n_arm : 1);      // SuckerControllers: per env, per ARM of the muscle octopus
-    alloc((void**)&h->d_sucker, (size_t)SOFTROD_MAX_SUCKERS * NS * sizeof(double));
-    h->S.sucker = h->d_sucker;
-    alloc((void**)&h->d_sucker_idx, (size_t)SOFTROD_MAX_SUCKERS * NS * sizeof(int));
-    h->S.sucker_idx = h->d_sucker_idx;
-    if (cfg->early_termination) {     // row 0: the step's time-limit flag (softrod_state_view.env_aux)
-        alloc((void**)&h->d_aux, (size_t)8 * N * sizeof(double));
-        h->S.aux = h->d_aux;
-    }
-    if (mocto) {
-        alloc((void**)&h->d_aux, (size_t)8 * N * sizeof(double));
-        alloc((void**)&h->d_prev_kappa, N * (size_t)cfg->n_arm * (size_t)(cfg->n_elem - 1) * sizeof(float));
-        h->S.aux = h->d_aux;
-        h->S.prev_kappa = h->d_prev_kappa;
-    }
-    if (rc == SOFTROD_OK) {
+    alloc(h->S.sucker, (size_t)SOFTROD_MAX_SUCKERS * NS * sizeof(double));
+    alloc(h->S.sucker_idx, (size_t)SOFTROD_MAX_SUCKERS * NS * sizeof(int));
+    // [8][N] row 0: the step's time-limit flag (softrod_state_view.env_aux); the muscle octopus envs' target and xposbefore
+    if (cfg->early_termination || mocto) alloc(h->S.aux, (size_t)8 * N * sizeof(double));
+    if (mocto) alloc(h->S.prev_kappa, N * (size_t)cfg->n_arm * (size_t)(cfg->n_elem - 1) * sizeof(float));
+    {
         std::vector<int> idx((size_t)SOFTROD_MAX_SUCKERS * NS, 0);
         for (int j = 0; j < SOFTROD_MAX_SUCKERS; ++j)
             for (size_t e = 0; e < NS; ++e) idx[(size_t)j * NS + e] = cfg->sucker_index[j];
-        if (hipMemcpy(h->d_sucker_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
-            rc = SOFTROD_EHIP;
+        upload(h->S.sucker_idx, idx.data(), idx.size() * sizeof(int));
     }
     if (cfg->features & SOFTROD_FEAT_COOMM_MUSCLES) {
-        alloc((void**)&h->d_mact, (size_t)SOFTROD_MAX_MUSCLES * rowb);
-        alloc((void**)&h->d_mtab, (size_t)SOFTROD_MAX_MUSCLES * 4 * kLanes * h->epl * sizeof(double));
-        h->S.mact = h->d_mact;
+        alloc(h->S.mact, (size_t)SOFTROD_MAX_MUSCLES * rowb);
+        alloc(h->d_mtab, (size_t)SOFTROD_MAX_MUSCLES * 4 * kLanes * h->epl * sizeof(double));
         h->S.mtab = h->d_mtab;
     }
-    if (rc == SOFTROD_OK && (cfg->features & SOFTROD_FEAT_SUCKER_CONSTRAINT)) {
+    if (cfg->features & SOFTROD_FEAT_SUCKER_CONSTRAINT) {
         // the controllers are switched on after finalize (arm_push_env.py:222): effective ratio = the configured one
         std::vector<double> init((size_t)SOFTROD_MAX_SUCKERS * NS, 0.0);
         for (int j = 0; j < cfg->n_suckers; ++j)
             for (size_t e = 0; e < NS; ++e) init[(size_t)j * NS + e] = cfg->sucker_reduction_ratio;
-        if (hipMemcpy(h->d_sucker, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-            rc = SOFTROD_EHIP;
+        upload(h->S.sucker, init.data(), init.size() * sizeof(double));
     }
-    alloc((void**)&h->d_basis, (size_t)2 * kLanes * 7 * sizeof(double));
+    alloc(h->d_basis, (size_t)2 * kLanes * 7 * sizeof(double));
     h->S.basis = h->d_basis;
-    alloc((void**)&h->d_init, N * h->init_stride * sizeof(double));
-    alloc((void**)&h->d_mask, N);
+    alloc(h->d_init, N * h->init_stride * sizeof(double));
+    alloc(h->d_mask, N);
     if (rc == SOFTROD_OK && hipHostMalloc((void**)&h->h_init, N * h->init_stride * sizeof(double)) != hipSuccess) rc = SOFTROD_ENOMEM;
     if (rc == SOFTROD_OK && hipHostMalloc((void**)&h->h_mask, N) != hipSuccess) rc = SOFTROD_ENOMEM;
     if (rc == SOFTROD_OK && hipEventCreateWithFlags(&h->ev_reset, hipEventDisableTiming) != hipSuccess)
         rc = SOFTROD_EHIP;
-    if (rc == SOFTROD_OK && hipMemcpy(h->d_state, &h->S, sizeof(StatePtrs), hipMemcpyHostToDevice) != hipSuccess)
-        rc = SOFTROD_EHIP;
+    upload(h->d_state, &h->S, sizeof(StatePtrs));
     if (rc != SOFTROD_OK) {
         softrod_destroy(h);
         return fail(nullptr, rc, "device allocation failed");
@@ -1582,7 +1587,7 @@ int softrod_set_radius_profile(softrod_handle* h, const double* radius) {
     }
     for (int row = 0; row < kMatRows; ++row)
         for (int k = period; k < W; ++k) T[(size_t)row * W + k] = T[(size_t)row * W + (k % period)];
-    if (!h->d_mat) SR_HIP(h, hipMalloc((void**)&h->d_mat, T.size() * sizeof(double)));
+    if (!h->d_mat) SR_HIP(h, alloc_owned(h, h->d_mat, T.size() * sizeof(double)));
     SR_HIP(h, hipMemcpy(h->d_mat, T.data(), T.size() * sizeof(double), hipMemcpyHostToDevice));
     h->S.mat = h->d_mat;
     h->P.mass_total = ms;
@@ -1846,72 +1851,53 @@ int softrod_observe(softrod_handle* h, const float* prev_action, float* obs, voi
     } else if (is_octo(h) && !is_pull(h))
         hipLaunchKernelGGL(softrod_octo_observe_kernel, grid, dim3(kLanes * h->nw), 0, (hipStream_t)stream,
                            h->P, h->S, prev_action, obs);
-    else if (h->epl == 2)
-        hipLaunchKernelGGL(softrod_observe_kernel<2>, grid, block, 0, (hipStream_t)stream, h->P, h->S,
-                           prev_action, obs);
     else
-        hipLaunchKernelGGL(softrod_observe_kernel<1>, grid, block, 0, (hipStream_t)stream, h->P, h->S,
-                           prev_action, obs);
+        hipLaunchKernelGGL(by_epl(h, softrod_observe_kernel<1>, softrod_observe_kernel<2>), grid, block, 0,
+                           (hipStream_t)stream, h->P, h->S, prev_action, obs);
     SR_HIP(h, hipGetLastError());
     return SOFTROD_OK;
 }
 
-int softrod_rod_energies(softrod_handle* h, double* out, void* stream) {
-    if (!h || !out) return fail(h, SOFTROD_EINVAL, "null argument");
+namespace {
+// The per-rod read-outs (softrod_readout.hpp): one wave per rod of the handle's layout.
+using ReadoutKernel = void (*)(RodParams, StatePtrs, int, int, int, double*);
+int launch_readout(softrod_handle* h, ReadoutKernel kernel, double* out, void* stream) {
     SR_ON_DEVICE(h);
-    const bool arms = is_flat(h) || is_mocto(h);
-    const int rods = arms ? h->cfg.n_arm : 1;
-    const int lane_stride = kLanes * h->epl * h->nw, arm_stride = arms ? h->P.seg : 0;
-    const dim3 grid((unsigned)(h->cfg.n_envs * rods)), block(kLanes);
-    if (h->epl == 2)
-        hipLaunchKernelGGL(softrod_rod_energies_kernel<2>, grid, block, 0, (hipStream_t)stream, h->P, h->S, rods,
-                           lane_stride, arm_stride, out);
-    else
-        hipLaunchKernelGGL(softrod_rod_energies_kernel<1>, grid, block, 0, (hipStream_t)stream, h->P, h->S, rods,
-                           lane_stride, arm_stride, out);
+    const RodLayout y = rod_layout(h);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(h->cfg.n_envs * y.rods)), dim3(kLanes), 0, (hipStream_t)stream, h->P, h->S,
+                       y.rods, y.lane_stride, y.arm_stride, out);
     SR_HIP(h, hipGetLastError());
     return SOFTROD_OK;
+}
+}  // namespace
+
+int softrod_rod_energies(softrod_handle* h, double* out, void* stream) {
+    if (!h || !out) return fail(h, SOFTROD_EINVAL, "null argument");
+    return launch_readout(h, by_epl(h, softrod_rod_energies_kernel<1>, softrod_rod_energies_kernel<2>), out, stream);
 }
 
 int softrod_ground_reaction(softrod_handle* h, double* out, void* stream) {
     if (!h || !out) return fail(h, SOFTROD_EINVAL, "null argument");
     if (const char* why = ground_reaction_why_not(h)) return fail(h, SOFTROD_EINVAL, why);
-    SR_ON_DEVICE(h);
-    // the rods of an env with a rigid head (the kernel's own test: SOFTROD_FEAT_OCTO_HEAD; of those only OctoFlat is in scope)
-    const int rods = is_octo(h) ? h->cfg.n_arm : 1;
-    const int lane_stride = kLanes * h->epl * h->nw, arm_stride = is_octo(h) ? h->P.seg : 0;
-    const dim3 grid((unsigned)(h->cfg.n_envs * rods)), block(kLanes);
-    hipLaunchKernelGGL(softrod_ground_reaction_kernel, grid, block, 0, (hipStream_t)stream, h->P, h->S, rods, lane_stride,
-                       arm_stride, out);
-    SR_HIP(h, hipGetLastError());
-    return SOFTROD_OK;
+    // The kernel's own test for an env of several rods is SOFTROD_FEAT_OCTO_HEAD; rod_layout's is OctoFlat or the muscle
+    // octopus.  For every handle that gets here the two agree: of the rigid-head envs only OctoFlat is let through.
+    return launch_readout(h, softrod_ground_reaction_kernel, out, stream);
 }
 
 int softrod_rod_strains(softrod_handle* h, double* out, void* stream) {
     if (!h) return fail(h, SOFTROD_EINVAL, "rod strains: null handle");
     if (!out) return fail(h, SOFTROD_EINVAL, "rod strains: null output buffer");
-    SR_ON_DEVICE(h);
-    // softrod_rod_energies' launch: every handle's resident rows have this layout, so there is no refusal list
-    const bool arms = is_flat(h) || is_mocto(h);
-    const int rods = arms ? h->cfg.n_arm : 1;
-    const int lane_stride = kLanes * h->epl * h->nw, arm_stride = arms ? h->P.seg : 0;
-    const dim3 grid((unsigned)(h->cfg.n_envs * rods)), block(kLanes);
-    if (h->epl == 2)
-        hipLaunchKernelGGL(softrod_rod_strains_kernel<2>, grid, block, 0, (hipStream_t)stream, h->P, h->S, rods,
-                           lane_stride, arm_stride, out);
-    else
-        hipLaunchKernelGGL(softrod_rod_strains_kernel<1>, grid, block, 0, (hipStream_t)stream, h->P, h->S, rods,
-                           lane_stride, arm_stride, out);
-    SR_HIP(h, hipGetLastError());
-    return SOFTROD_OK;
+    // every handle's resident rows have rod_layout's form, so there is no refusal list
+    return launch_readout(h, by_epl(h, softrod_rod_strains_kernel<1>, softrod_rod_strains_kernel<2>), out, stream);
 }
 
 int softrod_state_view_get(softrod_handle* h, softrod_state_view* out) {
     if (!h || !out) return fail(h, SOFTROD_EINVAL, "null argument");
     out->n_envs = h->cfg.n_envs;
     out->n_elem = h->cfg.n_elem;
-    out->lane_stride = kLanes * h->epl * h->nw;
-    out->arm_stride = (is_flat(h) || is_mocto(h)) ? h->P.seg : 0;
+    const RodLayout y = rod_layout(h);
+    out->lane_stride = y.lane_stride;
+    out->arm_stride = y.arm_stride;
     out->position = h->S.pos;
     out->velocity = h->S.vel;
     out->director = h->S.dir;
@@ -1926,11 +1912,11 @@ int softrod_state_view_get(softrod_handle* h, softrod_state_view* out) {
     out->head = h->S.head;
     out->bc_targets = h->S.bc;
     out->sucker_ratio = h->S.sucker;
-    out->muscle_activation = h->d_mact;
-    out->sucker_index = h->d_sucker_idx;
+    out->muscle_activation = h->S.mact;
+    out->sucker_index = h->S.sucker_idx;
     out->material = h->d_mat;
-    out->env_aux = h->d_aux;
-    out->prev_kappa = h->d_prev_kappa;
+    out->env_aux = h->S.aux;
+    out->prev_kappa = h->S.prev_kappa;
     return SOFTROD_OK;
 }
 
@@ -2001,9 +1987,7 @@ int softrod_destroy(softrod_handle* h) {
     DeviceGuard guard_(h->device);
     (void)hipDeviceSynchronize();
     autoreset_release(h);
-    void* bufs[] = {h->S.pos, h->S.vel, h->S.dir, h->S.omg, h->S.tan, h->S.time, h->S.bc,
-                    h->S.ctrl, h->S.kap, h->S.rkap, h->S.envmem, h->S.prev_action, h->S.head, h->d_params, h->d_state, h->d_time_tab, h->d_mat, h->d_sucker, h->d_sucker_idx, h->d_aux, h->d_prev_kappa, h->d_mact, h->d_mtab, h->d_basis, h->d_spline, h->d_init, h->d_mask, h->d_ticket};
-    for (void* p : bufs) (void)hipFree(p);
+    for (void* p : h->owned) (void)hipFree(p);
     if (h->h_init) (void)hipHostFree(h->h_init);
     h->env_mat.release();
     h->env_contact.release();

@@ -20,8 +20,8 @@
 // File map: softrod_contact.hpp (rod-plane contact), softrod_fast.hpp (the default step
 // kernel), softrod_planar.hpp (SoftPendulum's planar substep), softrod_octo.hpp (OctoFlat: one
 // env per workgroup), softrod_window.hpp (64..102-element arms on two overlapping windows),
-// softrod_reaction.hpp (the ground-reaction read-out, a cold kernel), softrod_strains.hpp (the
-// strain and internal-load read-out, a cold kernel);
+// and the three cold read-out kernels: softrod_readout.hpp (their shared addressing and load, the rod
+// energies), softrod_reaction.hpp (the ground reaction), softrod_strains.hpp (the strains and internal loads);
 // this file holds the state layout, the env prologues/epilogues, the reset /
 // observe / auto-reset kernels and the LIBM kernel.
 //
@@ -2155,58 +2155,11 @@ softrod_autoreset_kernel(const RodParams P, const StatePtrs S, float* __restrict
     }
 }
 
-// softrod_rod_energies: one wave per rod — env blockIdx.x / rods, arm blockIdx.x % rods, its slots
-// a * arm_stride .. a * arm_stride + n_elem of the env's row (`lane_stride` wide: the layouts of
-// softrod_state_view) — so every arm's sums are a plain wave reduction.  Slots past the rod are
-// never read.  out: [n_envs][rods][4].
-template <int EPL>
-__global__ void __launch_bounds__(kLanes)
-softrod_rod_energies_kernel(const RodParams P, const StatePtrs S, const int rods, const int lane_stride,
-                            const int arm_stride, double* __restrict__ out) {
-    const int rod = blockIdx.x, env = rod / rods, arm = rod - env * rods;
-    const int lane = threadIdx.x;
-    const size_t N = (size_t)P.n_envs, W = (size_t)lane_stride;
-    const size_t base = (size_t)env * W + (size_t)arm * (size_t)arm_stride;
-    const bool rk = (P.features & SOFTROD_FEAT_REST_KAPPA_ACTION) != 0;
-    LaneN<EPL> L;
-#pragma unroll
-    for (int s = 0; s < EPL; ++s) {
-        const int j = lane * EPL + s;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { L.x[s][c] = L.v[s][c] = L.w[s][c] = L.rk[s][c] = 0.0; }
-#pragma unroll
-        for (int c = 0; c < 9; ++c) L.Q[s][c] = 0.0;
-        if (j <= P.n_elem) {
-            const size_t i = base + (size_t)j;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                L.x[s][c] = S.pos[c * N * W + i];
-                L.v[s][c] = S.vel[c * N * W + i];
-                L.w[s][c] = S.omg[c * N * W + i];
-                if (rk) L.rk[s][c] = S.rkap[c * N * W + i];
-            }
-#pragma unroll
-            for (int c = 0; c < 9; ++c) L.Q[s][c] = S.dir[c * N * W + i];
-        }
-    }
-    BcTargets B;
-    const bool bc = (P.features & (SOFTROD_FEAT_PENDULUM_BC | SOFTROD_FEAT_FIXED_BC | SOFTROD_FEAT_MOVING_BASE_BC)) != 0;
-    if (bc) {
-        load_bc(S, N, env, B);
-        if (P.features & SOFTROD_FEAT_MOVING_BASE_BC) { B.pos[0] = S.ctrl[env]; B.pos[1] = S.ctrl[N + env]; }
-    }
-    double E[4];
-    rod_energies_m<EPL>(P, env_material_rt(P, S, env), S.mat, B, bc, lane, L, S.time[env], E);
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) out[(size_t)rod * 4 + i] = E[i];
-    }
-}
-
 }  // namespace softrod
 
 #include "softrod_fast.hpp"
 #include "softrod_octo.hpp"
 #include "softrod_window.hpp"
+#include "softrod_readout.hpp"
 #include "softrod_reaction.hpp"
 #include "softrod_strains.hpp"

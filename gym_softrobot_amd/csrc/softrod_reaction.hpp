@@ -1,10 +1,10 @@
 // softrod_reaction.hpp — softrod_ground_reaction: what RodPlaneContactWithAnisotropicFriction adds to
 // external_forces / external_torques of every rod of every env, evaluated ONCE on the resident state.
 //
-// A cold kernel beside the step kernels, like softrod_rod_energies_kernel: one wave per rod — env
-// blockIdx.x / rods, arm blockIdx.x % rods, its slots arm * arm_stride .. arm * arm_stride + n_elem of
-// the env's row (`lane_stride` wide: the layouts of softrod_state_view; for OctoFlat that is row
-// env * nw + wave at slot offset arm * seg) — node k, element k and Voronoi vertex k on lane k.
+// A cold kernel beside the step kernels, with softrod_rod_energies_kernel's addressing (readout_rod,
+// softrod_readout.hpp: one wave per rod; for OctoFlat the rod's slots are row env * nw + wave at slot
+// offset arm * seg) — node k, element k and Voronoi vertex k on lane k.  The load is its own: masked
+// per element and Voronoi vertex.
 // Neighbours come through the DPP shifts from_next / from_prev with their end rules (lane 63 / lane 0
 // read 0); no LDS, no atomics, no array indexed at run time.
 //
@@ -67,11 +67,11 @@ __global__ void __launch_bounds__(kLanes)
 softrod_ground_reaction_kernel(const RodParams P, const StatePtrs S, const int rods, const int lane_stride,
                                const int arm_stride, double* __restrict__ out) {
 #pragma clang fp contract(off)
-    const int rod = blockIdx.x, env = rod / rods, arm = rod - env * rods;
+    const ReadoutRod R = readout_rod(P, rods, lane_stride, arm_stride);
+    const int rod = R.rod, env = R.env, arm = R.arm;
     const int lane = threadIdx.x;
     const int n = P.n_elem;
     const size_t N = (size_t)P.n_envs, W = (size_t)lane_stride;
-    const size_t base = (size_t)env * W + (size_t)arm * (size_t)arm_stride;
     const bool node_valid = lane <= n, elem_valid = lane < n, vor_valid = lane < n - 1;
     const bool rk = (P.features & SOFTROD_FEAT_REST_KAPPA_ACTION) != 0;
     LaneN<1> L;
@@ -80,7 +80,7 @@ softrod_ground_reaction_kernel(const RodParams P, const StatePtrs S, const int r
 #pragma unroll
     for (int c = 0; c < 9; ++c) L.Q[0][c] = 0.0;
     if (node_valid) {                                  // slots past the rod are never read: n + 1 nodes, n elements,
-        const size_t i = base + (size_t)lane;          // n - 1 Voronoi vertices; the rest stay zero
+        const size_t i = R.base + (size_t)lane;        // n - 1 Voronoi vertices; the rest stay zero
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             L.x[0][c] = S.pos[c * N * W + i];

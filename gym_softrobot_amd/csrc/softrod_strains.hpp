@@ -2,9 +2,8 @@
 // (utils/custom_elastica/callback_func.py:23-41: sigma, kappa, dilatation, voronoi_dilatation) and the passive
 // elastic loads they stand for, for every rod of every env, on the device.
 //
-// A cold kernel beside the step kernels, of softrod_rod_energies_kernel's shape: one wave per rod — env
-// blockIdx.x / rods, arm blockIdx.x % rods, its slots arm * arm_stride .. arm * arm_stride + n_elem of the
-// env's row (`lane_stride` wide: the layouts of softrod_state_view) — slot j = lane * EPL + s holds node j,
+// A cold kernel beside the step kernels, of softrod_rod_energies_kernel's shape, addressing and load
+// (softrod_readout.hpp: one wave per rod) — slot j = lane * EPL + s holds node j,
 // element j and Voronoi vertex j, for one- and two-slot rods alike.  Neighbours come through shift_next (DPP wave
 // shifts; the out-of-range lane reads 0); no LDS, no atomics, no array indexed at run time.
 //
@@ -144,42 +143,16 @@ template <int EPL>
 __global__ void __launch_bounds__(kLanes)
 softrod_rod_strains_kernel(const RodParams P, const StatePtrs S, const int rods, const int lane_stride,
                            const int arm_stride, double* __restrict__ out) {
-    const int rod = blockIdx.x, env = rod / rods, arm = rod - env * rods;
+    const ReadoutRod R = readout_rod(P, rods, lane_stride, arm_stride);
     const int lane = threadIdx.x;
     const int n = P.n_elem;
-    const size_t N = (size_t)P.n_envs, W = (size_t)lane_stride;
-    const size_t base = (size_t)env * W + (size_t)arm * (size_t)arm_stride;
     const bool rk = (P.features & SOFTROD_FEAT_REST_KAPPA_ACTION) != 0;
     LaneN<EPL> L;
-#pragma unroll
-    for (int s = 0; s < EPL; ++s) {
-        const int j = lane * EPL + s;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { L.x[s][c] = L.v[s][c] = L.w[s][c] = L.rk[s][c] = 0.0; }
-#pragma unroll
-        for (int c = 0; c < 9; ++c) L.Q[s][c] = 0.0;
-        if (j <= n) {                                   // slots past the rod are never read
-            const size_t i = base + (size_t)j;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                L.x[s][c] = S.pos[c * N * W + i];
-                L.v[s][c] = S.vel[c * N * W + i];
-                L.w[s][c] = S.omg[c * N * W + i];
-                if (rk) L.rk[s][c] = S.rkap[c * N * W + i];
-            }
-#pragma unroll
-            for (int c = 0; c < 9; ++c) L.Q[s][c] = S.dir[c * N * W + i];
-        }
-    }
     BcTargets B;
-    const bool bc = (P.features & (SOFTROD_FEAT_PENDULUM_BC | SOFTROD_FEAT_FIXED_BC | SOFTROD_FEAT_MOVING_BASE_BC)) != 0;
-    if (bc) {
-        load_bc(S, N, env, B);
-        if (P.features & SOFTROD_FEAT_MOVING_BASE_BC) { B.pos[0] = S.ctrl[env]; B.pos[1] = S.ctrl[N + env]; }
-    }
-    const EnvMaterial M = env_material_rt(P, S, env);
+    const bool bc = readout_load<EPL>(P, S, R, lane, L, B);     // slots past the rod are never read
+    const EnvMaterial M = env_material_rt(P, S, R.env);
     double x[EPL][3], Q[EPL][9], xn[EPL][3], Qn[EPL][9];
-    rod_strain_config_n<EPL>(P, B, bc, lane, L, S.time[env], x, Q, xn, Qn);
+    rod_strain_config_n<EPL>(P, B, bc, lane, L, S.time[R.env], x, Q, xn, Qn);
 
     double l[EPL], e[EPL], sg[EPL][3], kp[EPL][3], fn[EPL][3], cm[EPL][3];
 #pragma unroll
@@ -206,7 +179,7 @@ softrod_rod_strains_kernel(const RodParams P, const StatePtrs S, const int rods,
     double ln[EPL];
     shift_next<EPL>(l, ln);                             // l_{k+1}: every lane takes part
 
-    double* o = out + (size_t)rod * kStrainRows * (size_t)n;
+    double* o = out + (size_t)R.rod * kStrainRows * (size_t)n;
 #pragma unroll
     for (int s = 0; s < EPL; ++s) {
         const int j = lane * EPL + s;
