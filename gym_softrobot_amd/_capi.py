@@ -805,6 +805,14 @@ def ground_reaction_refusal(cfg: "SoftrodConfig"):
     return None
 
 
+def muscle_loads_refusal(cfg: "SoftrodConfig"):
+    """Why softrod_muscle_loads would refuse a handle of `cfg` (None: it would not), in the library's own words: the
+    read-out serves the handles with COOMM muscle layers."""
+    if not int(cfg.features) & FEAT_COOMM_MUSCLES:
+        return "muscle loads: this handle has no COOMM muscles"
+    return None
+
+
 def env_contact_defaults(cfg: "SoftrodConfig") -> "np.ndarray":
     """(8,) float64: the config's own contact_k, contact_nu, kinetic_mu[3], static_mu[3] (forward, backward,
     sideways)."""
@@ -879,6 +887,7 @@ _EXPORTS = {
     "softrod_rod_energies": (C.c_int, [_VP, _VP, _VP]),
     "softrod_ground_reaction": (C.c_int, [_VP, _VP, _VP]),
     "softrod_rod_strains": (C.c_int, [_VP, _VP, _VP]),
+    "softrod_muscle_loads": (C.c_int, [_VP, _VP, _VP]),
     "softrod_set_env_material": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_set_env_contact": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_substeps": (C.c_int, [_VP, _VP, C.c_int, _VP]),

@@ -11,7 +11,7 @@ import torch
 
 from . import _capi
 from ._capi import LANE_STRIDE, SoftrodConfig, SoftrodStateView, check, load_library
-from .diagnostics import RodStrains, rod_strains_views
+from .diagnostics import MuscleLoads, RodStrains, muscle_loads_views, rod_strains_views
 
 
 class _DevArray:
@@ -75,7 +75,7 @@ class HipRodBackend:
         # per-handle physics tables that live outside softrod_config (action basis, spline table,
         # radius profile): their bytes go into config_fingerprint()
         self._tables: Dict[str, bytes] = {}
-        self._readouts: Dict[str, torch.Tensor] = {}     # rod_energies / ground_reaction / rod_strains buffers (_readout)
+        self._readouts: Dict[str, torch.Tensor] = {}     # rod_energies / ground_reaction / rod_strains / muscle_loads buffers (_readout)
         check(self._lib.softrod_create(C.byref(self.cfg), self.device_index, C.byref(self._h)))
         if self.cfg.features & _capi.FEAT_REST_KAPPA_ACTION:
             if self.is_octo:
@@ -337,6 +337,15 @@ class HipRodBackend:
         call."""
         rods = _capi.config_rods_per_env(self.cfg)
         return rod_strains_views(self._readout("rod_strains", rods, 14, int(self.cfg.n_elem)))
+
+    def muscle_loads(self) -> MuscleLoads:
+        """softrod_muscle_loads: MuscleLoads(layer_force, layer_length, internal_force, internal_couple,
+        external_force, external_couple) of float64 device tensors — (n_envs, rods_per_env, 4, n_elem), (.., 4, n_elem),
+        (.., 3, n_elem), (.., 3, n_elem - 1), (.., 3, n_elem + 1), (.., 3, n_elem) — what ApplyMuscles computes from the
+        resident activation rows at the instant of rod_strains() (include/softrod.h).  Views of one (n_envs,
+        rods_per_env, 20, n_elem + 1) buffer allocated on first use and overwritten by the next call."""
+        rods = _capi.config_rods_per_env(self.cfg)
+        return muscle_loads_views(self._readout("muscle_loads", rods, 20, int(self.cfg.n_elem) + 1))
 
     def time_limit(self) -> torch.Tensor:
         """early_termination handles: the last step's time-limit flag per env (row 0 of softrod_state_view.env_aux)

@@ -1891,6 +1891,14 @@ int softrod_rod_strains(softrod_handle* h, double* out, void* stream) {
     return launch_readout(h, by_epl(h, softrod_rod_strains_kernel<1>, softrod_rod_strains_kernel<2>), out, stream);
 }
 
+int softrod_muscle_loads(softrod_handle* h, double* out, void* stream) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "muscle loads: null handle");
+    if (!out) return fail(h, SOFTROD_EINVAL, "muscle loads: null output buffer");
+    if (!(h->cfg.features & SOFTROD_FEAT_COOMM_MUSCLES)) return fail(h, SOFTROD_EINVAL, "muscle loads: this handle has no COOMM muscles");
+    if (!h->muscles_set) return fail(h, SOFTROD_EINVAL, "muscle loads: softrod_set_muscle_layers has not been called");
+    return launch_readout(h, by_epl(h, softrod_muscle_loads_kernel<1>, softrod_muscle_loads_kernel<2>), out, stream);
+}
+
 int softrod_state_view_get(softrod_handle* h, softrod_state_view* out) {
     if (!h || !out) return fail(h, SOFTROD_EINVAL, "null argument");
     out->n_envs = h->cfg.n_envs;

@@ -2163,3 +2163,4 @@ softrod_autoreset_kernel(const RodParams P, const StatePtrs S, float* __restrict
 #include "softrod_readout.hpp"
 #include "softrod_reaction.hpp"
 #include "softrod_strains.hpp"
+#include "softrod_muscle_readout.hpp"

@@ -1,13 +1,13 @@
 // softrod_readout.hpp — what the per-rod read-out kernels share, and the first of them.
 //
 // The read-outs are cold kernels beside the step kernels: softrod_rod_energies_kernel (here),
-// softrod_rod_strains_kernel (softrod_strains.hpp) and softrod_ground_reaction_kernel (softrod_reaction.hpp).
-// All three run one wave per rod — env blockIdx.x / rods, arm blockIdx.x % rods, its slots
+// softrod_rod_strains_kernel (softrod_strains.hpp), softrod_ground_reaction_kernel (softrod_reaction.hpp) and
+// softrod_muscle_loads_kernel (softrod_muscle_readout.hpp).  All four run one wave per rod — env blockIdx.x / rods, arm blockIdx.x % rods, its slots
 // arm * arm_stride .. arm * arm_stride + n_elem of the env's row (`lane_stride` wide: the layouts of
 // softrod_state_view) — so every rod's sums are a plain wave reduction.  Slots past the rod are never read.
 //
 // readout_rod is that addressing; readout_load fills the wave's LaneN<EPL> from the resident rows and the
-// boundary-condition targets as the energies and the strains take them.  The reaction kernel takes only the
+// boundary-condition targets as the energies, the strains and the muscle loads take them.  The reaction kernel takes only the
 // addressing: its load is masked per element and Voronoi vertex and also clears kappa and the tangents.
 #pragma once
 

@@ -180,6 +180,103 @@ def rod_strains_host(x, v, Q, w, time: float, cfg, material, rest_kappa=None, fi
                       material["bend"] * dk)
 
 
+class MuscleLoads(NamedTuple):
+    """What softrod_muscle_loads / muscle_loads() return (include/softrod.h; PARITY UNPINNED like the muscle law
+    itself): layer_force (.., 4, n_elem) and layer_length (.., 4, n_elem) of the COOMM layers (zero rows for a layer
+    the config does not have), the muscle internal_force (.., 3, n_elem) and internal_couple (.., 3, n_elem - 1) in
+    the material frame, and the equivalent external_force (.., 3, n_elem + 1) on the nodes and external_couple
+    (.., 3, n_elem) on the elements that ApplyMuscles adds to the rod."""
+    layer_force: object
+    layer_length: object
+    internal_force: object
+    internal_couple: object
+    external_force: object
+    external_couple: object
+
+
+def muscle_loads_views(buf) -> MuscleLoads:
+    """The six fields as views of softrod_muscle_loads' buffer (.., 20, n_elem + 1): every row without its zero
+    columns."""
+    return MuscleLoads(buf[..., 0:4, :-1], buf[..., 4:8, :-1], buf[..., 8:11, :-1], buf[..., 11:14, :-2],
+                       buf[..., 14:17, :], buf[..., 17:20, :-1])
+
+
+def _cross(a, b):
+    return np.stack([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]])
+
+
+def _difference(a):
+    """(3, k) -> (3, k + 1): a padded with a zero column at both ends, differenced."""
+    out = np.zeros((3, a.shape[1] + 1))
+    out[:, :-1] += a
+    out[:, 1:] -= a
+    return out
+
+
+def muscle_loads_host(x, v, Q, w, time: float, cfg, material, layers, activation, radius=None, fixed_pos=None,
+                      fixed_dir=None, base_xy=None) -> MuscleLoads:
+    """NumPy twin of softrod_muscle_loads for one rod, at rod_strains_host's instant: the mid-substep configuration
+    (mid_substep_configuration, then constrain_values_host); time == 0 (a reset) uses the state as it stands.  The law
+    is the one csrc/softrod_muscle.hpp restates (Chang et al. 2023, section 2(c); PARITY UNPINNED), with the config's
+    muscle_kind, muscle_tm_length_law, muscle_equiv_load_form, muscle_position_current_radius, muscle_fl_degree /
+    muscle_fl_coef and n_muscles.  layers: (ratio_position (m, 3, n), strength (m, n)) as _capi.es_muscle_layers
+    returns them; activation (>= m, n): the resident activation rows of this rod; radius: the per-element rest radii
+    of a tapered rod, or None for cfg.base_radius; material: rod_material_host(...)."""
+    x, Q = np.array(x, np.float64), np.array(Q, np.float64)
+    v, w = np.asarray(v, np.float64), np.asarray(w, np.float64)
+    if time != 0.0:
+        x, Q = mid_substep_configuration(x, v, Q, w, float(cfg.dt), float(cfg.eps_rot_axis))
+        if fixed_pos is not None:
+            constrain_values_host(int(cfg.features), x, Q, fixed_pos, fixed_dir, base_xy)
+    n = Q.shape[2]
+    rl, rv = material["rest_length"], material["rest_voronoi"]
+    rest_radius = np.full(n, float(cfg.base_radius)) if radius is None else np.asarray(radius, np.float64).reshape(n)
+    s = rod_strains(x, Q, rl, rest_radius, float(cfg.acos_shift), float(cfg.eps_sin))
+    e, kappa = s["dilatation"], s["kappa"]
+    qt = np.einsum("ijk,jk->ik", Q, s["tangents"])
+    shear = e * qt                                               # sigma + (0, 0, 1)
+    kappa_e = np.zeros((3, n))                                   # Voronoi -> elements, half weights at both ends
+    kappa_e[:, :-1] += 0.5 * kappa
+    kappa_e[:, 1:] += 0.5 * kappa
+    rad = s["radius"] if int(cfg.muscle_position_current_radius) else rest_radius
+    ratio, strength = np.asarray(layers[0], np.float64), np.asarray(layers[1], np.float64)
+    activation = np.asarray(activation, np.float64)
+    degree = int(cfg.muscle_fl_degree)
+    layer_force, layer_length = np.zeros((4, n)), np.zeros((4, n))
+    f, c = np.zeros((3, n)), np.zeros((3, n))
+    for m in range(int(cfg.n_muscles)):
+        pos = rad * ratio[m]
+        nu = shear + _cross(kappa_e, pos)
+        norm = np.sqrt((nu * nu).sum(axis=0))
+        length = norm
+        if int(cfg.muscle_kind[m]) == 1 and int(cfg.muscle_tm_length_law) == 0:       # a transverse layer: radial fibres
+            length = 1.0 / np.sqrt(norm)
+        fl = np.zeros(n)
+        for p in range(degree, -1, -1):                          # Horner, as the kernels
+            fl = fl * length + float(cfg.muscle_fl_coef[p])
+        F = activation[m] * strength[m] * np.where(fl < 0.0, 0.0, fl)
+        g = F * (nu / norm)
+        layer_force[m], layer_length[m] = F, length
+        f += g
+        c += _cross(pos, g)
+    cv = 0.5 * (c[:, :-1] + c[:, 1:])
+    QT = np.transpose(Q, (1, 0, 2))
+    if int(cfg.muscle_equiv_load_form) == 0:    # F = D^h(Q^T f); tau = D^h(c_v) + A^h(kappa x c_v D^) + (e Q t) x f l^
+        ef = 1.0
+        ext_force = _difference(np.einsum("ijk,jk->ik", QT, f))
+        arm = shear
+    else:                                       # PyElastica's internal-load form: Q^T f / e, c_v / eps^3, (Q t) x f l^
+        ef = 1.0 / s["voronoi_dilatation"] ** 3
+        ext_force = _difference(np.einsum("ijk,jk->ik", QT, f) / e)
+        arm = qt
+    h3 = _cross(kappa, cv) * rv * ef
+    trapezoid = np.zeros((3, n))
+    trapezoid[:, :-1] += 0.5 * h3
+    trapezoid[:, 1:] += 0.5 * h3
+    ext_couple = _difference(cv * ef) + trapezoid + _cross(arm, f) * rl
+    return MuscleLoads(layer_force, layer_length, f, cv, ext_force, ext_couple)
+
+
 class RodRecorder:
     """Collects RodCallBack's fields for `env_indices` of a batch; one dict of lists per env,
     keyed like the reference's `rod_parameters_dict`."""

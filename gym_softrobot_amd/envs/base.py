@@ -158,6 +158,13 @@ class SingleRodEnv(GymEnv):
         r = self._vec.rod_strains()
         return type(r)(*(t[0] for t in r))
 
+    def muscle_loads(self):
+        """VecRodEnvBase.muscle_loads of this env, without the env axis, as NumPy arrays: MuscleLoads(layer_force
+        (rods, 4, n_elem), layer_length (rods, 4, n_elem), internal_force (rods, 3, n_elem), internal_couple (rods, 3,
+        n_elem - 1), external_force (rods, 3, n_elem + 1), external_couple (rods, 3, n_elem))."""
+        r = self._vec.muscle_loads()
+        return type(r)(*(t[0] for t in r))
+
     def save_data(self, filename_video, fps):
         """The reference renders `rod_parameters_dict` to a video here (soft_pendulum.py:253-256, flat_env.py:410-420);
         drawing is out of scope: the data is in `rod_parameters_dict`, nothing is written."""
@@ -646,6 +653,29 @@ class VecRodEnvBase:
         if not hasattr(be, "rod_strains"):
             raise NotImplementedError(f"rod strains need the HIP backend, not {type(be).__name__}")
         r = be.rod_strains()
+        return type(r)(*(self._out(t) for t in r))
+
+    def muscle_loads(self):
+        """MuscleLoads(layer_force, layer_length, internal_force, internal_couple, external_force, external_couple)
+        of every rod of a COOMM muscle env: what the reference's ApplyMuscles computes in every substep and returns
+        none of — muscle tension and length for proprioception, actuation effort for a reward — without leaving the
+        device.  layer_force (N, rods_per_env, 4, n_elem) = activation * strength * max(fl(length), 0) and
+        layer_length (N, rods_per_env, 4, n_elem) per layer (zero rows for layers the env does not have; the length
+        is defined whatever the activation is), the muscle internal_force (.., 3, n_elem) and internal_couple
+        (.., 3, n_elem - 1) in the material frame, the equivalent external_force (.., 3, n_elem + 1) on the nodes
+        (lab frame) and external_couple (.., 3, n_elem) on the elements.  THE INSTANT is rod_strains()'; the
+        activations are the resident rows as the last action left them, read per element (include/softrod.h
+        softrod_muscle_loads, which also names the one stepper that applies them differently).  The law is labelled
+        parity-unpinned, like the muscle envs themselves.  HIP backend only: elsewhere NotImplementedError; an env
+        without COOMM muscles raises ValueError.  Device tensors, views of one buffer overwritten by the next call
+        (NumPy copies with numpy_output=True)."""
+        be = self.backend
+        if not hasattr(be, "muscle_loads"):
+            raise NotImplementedError(f"muscle loads need the HIP backend, not {type(be).__name__}")
+        why = _capi.muscle_loads_refusal(self.cfg)
+        if why is not None:
+            raise ValueError(why)
+        r = be.muscle_loads()
         return type(r)(*(self._out(t) for t in r))
 
     # -- per-env material (domain randomisation) ----------------------------------------

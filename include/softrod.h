@@ -718,6 +718,43 @@ int softrod_ground_reaction(softrod_handle* h, double* out, void* stream);
  * null handle or a null `out`: SOFTROD_EINVAL with "rod strains: <reason>" in softrod_last_error.            */
 int softrod_rod_strains(softrod_handle* h, double* out, void* stream);
 
+/* Muscle loads: what the reference's ApplyMuscles computes in every substep and returns none of
+ * (gym_softrobot/envs/octopus/arm_push_env.py:197-212 over the layers of create_es_muscle_layers,
+ * octopus/build.py:295-338): every COOMM layer's force and length, the muscle internal force and couple, and the
+ * equivalent external loads they become, for every rod of every env, on the device — muscle length and tension
+ * for a policy's proprioception, actuation effort for a reward term.  It completes softrod_rod_strains, whose
+ * loads are the passive ones.  PARITY UNPINNED: the law is softrod_muscle.hpp's restatement of COOMM, which is not
+ * on disk; every recalled detail is a field of softrod_config (muscle_kind, muscle_tm_length_law,
+ * muscle_equiv_load_form, muscle_position_current_radius, muscle_fl_degree / muscle_fl_coef, n_muscles), all
+ * honoured here.  out: device [n_envs][rods_per_env][20][n_elem + 1] float64, rods_per_env as for
+ * softrod_rod_energies:
+ *   rows 0-3    layer force F_m = activation * strength * max(fl(l_m), 0), layers 0..3           n_elem columns
+ *   rows 4-7    layer length l_m: |nu_m|, or |nu_m|^-1/2 for a transverse layer under
+ *               muscle_tm_length_law 0; nu_m = e Q t + kappa_e x x_m                             n_elem
+ *   rows 8-10   muscle internal force f = sum F_m t_m, material frame                            n_elem
+ *   rows 11-13  muscle internal couple on the Voronoi vertices c_v = 1/2 (c_k + c_{k+1}),
+ *               c = sum x_m x F_m t_m, material frame                                            n_elem - 1
+ *   rows 14-16  equivalent external force on the nodes, lab frame: what ApplyMuscles adds to
+ *               external_forces                                                                  n_elem + 1
+ *   rows 17-19  equivalent external couple on the elements, material frame: what it adds to
+ *               external_torques                                                                 n_elem
+ * Every column of every row is written by every call: the columns past a row's range, and every row of a layer
+ * m >= n_muscles, as +0.0.  A layer is evaluated whatever its activation is (the step kernels skip a layer that is
+ * off in the whole rod): the length rows are always defined.
+ * THE INSTANT is the one softrod_rod_strains documents: the mid-substep configuration of the last force evaluation,
+ * or the state as it stands for an env whose time is 0, per env.
+ * THE ACTIVATIONS are the resident rows softrod_state_view.muscle_activation as they stand, read per element: after
+ * a step, what that step's action wrote.  For an env whose time is not 0 rows 14-19 are therefore the loads the last
+ * substep's force evaluation added, to rounding.  One exception: the SOFTROD_MATH_FAST OctoArmPush stepper in
+ * continuous mode applies element 0's value of the rows of layers 0 and 1 to every element, this call reads every
+ * element; the two agree where those rows are uniform over the elements, which is what a step leaves behind.
+ * ARITHMETIC: float64 as written (IEEE division and sqrt), one kernel for SOFTROD_MATH_LIBM and SOFTROD_MATH_FAST
+ * handles.  Asynchronous on `stream`, like softrod_rod_energies; capturable.  It reads the state and writes `out` only.
+ * Errors, each SOFTROD_EINVAL with its text in softrod_last_error: "muscle loads: null handle", "muscle loads: null
+ * output buffer", "muscle loads: this handle has no COOMM muscles" (no SOFTROD_FEAT_COOMM_MUSCLES), "muscle loads:
+ * softrod_set_muscle_layers has not been called".                                                               */
+int softrod_muscle_loads(softrod_handle* h, double* out, void* stream);
+
 /* Per-env rod material, for domain randomisation of single-rod envs.  Upstream has no counterpart: there
  * every env builds its rod with CosseratRod.straight_rod(..., density, youngs_modulus, shear_modulus) and
  * AnalyticalLinearDamper(damping_constant, ...), and a batch of them shares one softrod_config.  This call
