@@ -813,6 +813,14 @@ def muscle_loads_refusal(cfg: "SoftrodConfig"):
     return None
 
 
+def joint_loads_refusal(cfg: "SoftrodConfig"):
+    """Why softrod_joint_loads would refuse a handle of `cfg` (None: it would not), in the library's own words: the
+    read-out serves the handles whose arms are joined to a rigid body (FixedJoint2Rigid)."""
+    if not int(cfg.features) & FEAT_OCTO_HEAD:
+        return "joint loads: this handle has no rigid body"
+    return None
+
+
 def env_contact_defaults(cfg: "SoftrodConfig") -> "np.ndarray":
     """(8,) float64: the config's own contact_k, contact_nu, kinetic_mu[3], static_mu[3] (forward, backward,
     sideways)."""
@@ -888,6 +896,7 @@ _EXPORTS = {
     "softrod_ground_reaction": (C.c_int, [_VP, _VP, _VP]),
     "softrod_rod_strains": (C.c_int, [_VP, _VP, _VP]),
     "softrod_muscle_loads": (C.c_int, [_VP, _VP, _VP]),
+    "softrod_joint_loads": (C.c_int, [_VP, _VP, _VP]),
     "softrod_set_env_material": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_set_env_contact": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_substeps": (C.c_int, [_VP, _VP, C.c_int, _VP]),

@@ -11,7 +11,7 @@ import torch
 
 from . import _capi
 from ._capi import LANE_STRIDE, SoftrodConfig, SoftrodStateView, check, load_library
-from .diagnostics import MuscleLoads, RodStrains, muscle_loads_views, rod_strains_views
+from .diagnostics import JointLoads, MuscleLoads, RodStrains, joint_loads_views, muscle_loads_views, rod_strains_views
 
 
 class _DevArray:
@@ -75,7 +75,7 @@ class HipRodBackend:
         # per-handle physics tables that live outside softrod_config (action basis, spline table,
         # radius profile): their bytes go into config_fingerprint()
         self._tables: Dict[str, bytes] = {}
-        self._readouts: Dict[str, torch.Tensor] = {}     # rod_energies / ground_reaction / rod_strains / muscle_loads buffers (_readout)
+        self._readouts: Dict[str, torch.Tensor] = {}     # rod_energies / ground_reaction / rod_strains / muscle_loads / joint_loads buffers (_readout)
         check(self._lib.softrod_create(C.byref(self.cfg), self.device_index, C.byref(self._h)))
         if self.cfg.features & _capi.FEAT_REST_KAPPA_ACTION:
             if self.is_octo:
@@ -346,6 +346,16 @@ class HipRodBackend:
         rods_per_env, 20, n_elem + 1) buffer allocated on first use and overwritten by the next call."""
         rods = _capi.config_rods_per_env(self.cfg)
         return muscle_loads_views(self._readout("muscle_loads", rods, 20, int(self.cfg.n_elem) + 1))
+
+    def joint_loads(self) -> JointLoads:
+        """softrod_joint_loads: JointLoads(body_force, body_torque, arm_force, arm_torque, gap, gap_length, net_force,
+        net_torque, acceleration, angular_acceleration) of float64 device tensors — (n_envs, rods_per_env, 3) five
+        times, (n_envs, rods_per_env), (n_envs, 3) four times — what FixedJoint2Rigid exchanges between every arm and
+        the rigid body, and the body's net load and accelerations, from ONE evaluation at the resident state (not the
+        value the last substep applied: include/softrod.h).  Views of one (n_envs, rods_per_env + 1, 16) buffer
+        allocated on first use and overwritten by the next call."""
+        rods = _capi.config_rods_per_env(self.cfg)
+        return joint_loads_views(self._readout("joint_loads", rods + 1, 16))
 
     def time_limit(self) -> torch.Tensor:
         """early_termination handles: the last step's time-limit flag per env (row 0 of softrod_state_view.env_aux)

@@ -1859,12 +1859,15 @@ int softrod_observe(softrod_handle* h, const float* prev_action, float* obs, voi
 }
 
 namespace {
-// The per-rod read-outs (softrod_readout.hpp): one wave per rod of the handle's layout.
+// The read-outs: one wave per rod of the handle's layout (softrod_readout.hpp), or one wave per env, which finds its
+// rods itself (the joint read-out, softrod_joint_readout.hpp).
 using ReadoutKernel = void (*)(RodParams, StatePtrs, int, int, int, double*);
-int launch_readout(softrod_handle* h, ReadoutKernel kernel, double* out, void* stream) {
+enum class ReadoutGrid { kPerRod, kPerEnv };
+int launch_readout(softrod_handle* h, ReadoutKernel kernel, double* out, void* stream, ReadoutGrid grid = ReadoutGrid::kPerRod) {
     SR_ON_DEVICE(h);
     const RodLayout y = rod_layout(h);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(h->cfg.n_envs * y.rods)), dim3(kLanes), 0, (hipStream_t)stream, h->P, h->S,
+    const int waves = h->cfg.n_envs * (grid == ReadoutGrid::kPerEnv ? 1 : y.rods);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)waves), dim3(kLanes), 0, (hipStream_t)stream, h->P, h->S,
                        y.rods, y.lane_stride, y.arm_stride, out);
     SR_HIP(h, hipGetLastError());
     return SOFTROD_OK;
@@ -1897,6 +1900,13 @@ int softrod_muscle_loads(softrod_handle* h, double* out, void* stream) {
     if (!(h->cfg.features & SOFTROD_FEAT_COOMM_MUSCLES)) return fail(h, SOFTROD_EINVAL, "muscle loads: this handle has no COOMM muscles");
     if (!h->muscles_set) return fail(h, SOFTROD_EINVAL, "muscle loads: softrod_set_muscle_layers has not been called");
     return launch_readout(h, by_epl(h, softrod_muscle_loads_kernel<1>, softrod_muscle_loads_kernel<2>), out, stream);
+}
+
+int softrod_joint_loads(softrod_handle* h, double* out, void* stream) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "joint loads: null handle");
+    if (!out) return fail(h, SOFTROD_EINVAL, "joint loads: null output buffer");
+    if (!(h->cfg.features & SOFTROD_FEAT_OCTO_HEAD)) return fail(h, SOFTROD_EINVAL, "joint loads: this handle has no rigid body");
+    return launch_readout(h, softrod_joint_loads_kernel, out, stream, ReadoutGrid::kPerEnv);
 }
 
 int softrod_state_view_get(softrod_handle* h, softrod_state_view* out) {

@@ -277,6 +277,120 @@ def muscle_loads_host(x, v, Q, w, time: float, cfg, material, layers, activation
     return MuscleLoads(layer_force, layer_length, f, cv, ext_force, ext_couple)
 
 
+class JointLoads(NamedTuple):
+    """What softrod_joint_loads / joint_loads() return (include/softrod.h): per arm the load FixedJoint2Rigid exchanges
+    with the rigid body — body_force (.., rods, 3) = contact_force, added to the body (lab frame); body_torque
+    (.., rods, 3), added to the body (body frame); arm_force (.., rods, 3) = -contact_force, added to the arm's node 0;
+    arm_torque (.., rods, 3), added to the arm's element 0 (its material frame); gap (.., rods, 3) =
+    end_distance_vector and gap_length (.., rods) = end_distance — and for the body net_force, net_torque (.., 3), the
+    per-arm rows summed in arm order, with the linear acceleration (.., 3) and the body-frame angular_acceleration
+    (.., 3) they give it under its constraints."""
+    body_force: object
+    body_torque: object
+    arm_force: object
+    arm_torque: object
+    gap: object
+    gap_length: object
+    net_force: object
+    net_torque: object
+    acceleration: object
+    angular_acceleration: object
+
+
+def joint_loads_views(buf) -> JointLoads:
+    """The ten fields as views of softrod_joint_loads' buffer (.., rods + 1, 16): rows 0 .. rods - 1 the joints, the last
+    row the body."""
+    arms, body = buf[..., :-1, :], buf[..., -1, :]
+    return JointLoads(arms[..., 0:3], arms[..., 3:6], arms[..., 6:9], arms[..., 9:12], arms[..., 12:15], arms[..., 15],
+                      body[..., 0:3], body[..., 3:6], body[..., 6:9], body[..., 9:12])
+
+
+def _z_rotation(vector, theta):
+    """joint.py:7-17."""
+    theta = theta / 180.0 * np.pi
+    R = np.array([[np.cos(theta), -np.sin(theta), 0.0], [np.sin(theta), np.cos(theta), 0.0], [0.0, 0.0, 1.0]])
+    return np.dot(R, vector.T).T
+
+
+def joint_angles(cfg) -> np.ndarray:
+    """(n_arm,) degrees: the `angle` of every arm's FixedJoint2Rigid as softrod_create takes it from the config —
+    joint_angle0 + a * joint_angle_step, or 360 / n_arm * a for a config that leaves head_length at zero."""
+    na = int(cfg.n_arm)
+    if float(cfg.head_length) > 0.0:
+        return np.array([float(cfg.joint_angle0) + float(cfg.joint_angle_step) * a for a in range(na)])
+    return np.array([0.0 + 360 / float(na) * a for a in range(na)])
+
+
+def joint_loads_host(x, v, Q, head_x, head_v, head_Q, head_w, cfg, trig=None) -> JointLoads:
+    """NumPy twin of softrod_joint_loads for one env, written from the reference — FixedJoint2Rigid.apply_forces /
+    apply_torques (utils/custom_elastica/joint.py:47-219) arm by arm in arm order, then the rigid body's
+    update_accelerations and BodyBoundaryCondition.compute_constrain_rates as oracle/softrod_oracle_np.py transcribes
+    them (fixed_joint_to_rigid, NumpyCylinder.dynamic, constrain_rates) — at the state as it stands.  x (rods, 3, >= 2)
+    and v (rods, 3, >= 1): the arms' nodes (node 0 and node 1 are read); Q (rods, 3, 3, >= 1): their directors (element
+    0 is read); head_x, head_v, head_w (3,), head_Q (3, 3): the body.  cfg: joint_k / joint_nu / joint_kt, head_radius,
+    head_density, head_length, head_fixed, the joint angles (joint_angles) and the arms' rest length.  trig: in place
+    of the cosine and sine of each arm's angle, (rods, 2) — the band calibration of tests/joint_loads_ref.py."""
+    x, v, Q = (np.asarray(a, np.float64) for a in (x, v, Q))
+    head_x, head_v, head_w = (np.asarray(a, np.float64).reshape(3) for a in (head_x, head_v, head_w))
+    head_Q = np.asarray(head_Q, np.float64).reshape(3, 3)
+    rods = x.shape[0]
+    k, nu, kt, radius = float(cfg.joint_k), float(cfg.joint_nu), float(cfg.joint_kt), float(cfg.head_radius)
+    rest_length = float(cfg.base_length) / int(cfg.n_elem)
+    angles = joint_angles(cfg)
+    out = JointLoads(*(np.zeros((rods, 3)) for _ in range(5)), np.zeros(rods), *(np.zeros(3) for _ in range(4)))
+    for a in range(rods):
+        # apply_forces, :47-123
+        rigid_rod_pos = head_x.copy()
+        rigid_rod_pos[2] = 0.0
+        binormal = head_Q[1]
+        if trig is None:
+            connection_dir = -_z_rotation(binormal, angles[a])
+        else:
+            c, s = trig[a]
+            connection_dir = -np.dot(np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]]), binormal.T).T
+        rigid_rod_pos += connection_dir * radius
+        end_distance_vector = x[a, :, 0] - rigid_rod_pos
+        end_distance = np.sqrt(np.dot(end_distance_vector, end_distance_vector))
+        if end_distance <= np.finfo(np.float64).eps * 1e4:
+            normalized = np.array([0.0, 0.0, 0.0])
+        else:
+            normalized = end_distance_vector / end_distance
+        elastic_force = k * end_distance_vector
+        relative_velocity = v[a, :, 0] - head_v
+        damping_force = -nu * (np.dot(relative_velocity, normalized) * normalized)
+        contact_force = elastic_force + damping_force
+        # apply_torques, :125-219
+        link_direction = x[a, :, 1] - x[a, :, 0]
+        tgt_destination = rigid_rod_pos + rest_length * connection_dir
+        forcedirection = -kt * (x[a, :, 1] - tgt_destination)
+        torque = np.cross(link_direction, forcedirection)
+        for i in range(3):
+            for j in range(3):
+                out.body_torque[a, i] -= head_Q[i, j] * torque[j]
+                out.arm_torque[a, i] += Q[a, i, j, 0] * torque[j]
+        out.body_force[a] = contact_force
+        out.arm_force[a] = -contact_force
+        out.gap[a] = end_distance_vector
+        out.gap_length[a] = end_distance
+        out.net_force[:] += out.body_force[a]          # external_forces[..., index_one] += contact_force, arm after arm
+        out.net_torque[:] += out.body_torque[a]
+    if not int(cfg.head_fixed):
+        # Cylinder: mass and diagonal inertia as PyElastica allocates them; update_accelerations; constrain_rates
+        length = float(cfg.head_length) if float(cfg.head_length) > 0.0 else 2.0 * float(cfg.base_radius)
+        area = np.pi * radius * radius
+        mass = np.pi * radius * radius * length * float(cfg.head_density)
+        i1 = area * area / (4.0 * np.pi)
+        J = np.array([i1, i1, 2.0 * i1]) * float(cfg.head_density) * length
+        jw = J * head_w
+        gyro = np.array([jw[1] * head_w[2] - jw[2] * head_w[1], jw[2] * head_w[0] - jw[0] * head_w[2],
+                         jw[0] * head_w[1] - jw[1] * head_w[0]])
+        out.acceleration[:] = out.net_force / mass
+        out.angular_acceleration[:] = (1.0 / J) * (gyro + out.net_torque)
+        out.acceleration[2] = 0.0                      # compute_constrain_rates holds v_z, omega_x, omega_y
+        out.angular_acceleration[:2] = 0.0
+    return out
+
+
 class RodRecorder:
     """Collects RodCallBack's fields for `env_indices` of a batch; one dict of lists per env,
     keyed like the reference's `rod_parameters_dict`."""

@@ -165,6 +165,13 @@ class SingleRodEnv(GymEnv):
         r = self._vec.muscle_loads()
         return type(r)(*(t[0] for t in r))
 
+    def joint_loads(self):
+        """VecRodEnvBase.joint_loads of this env, without the env axis, as NumPy arrays: JointLoads(body_force (rods, 3),
+        body_torque (rods, 3), arm_force (rods, 3), arm_torque (rods, 3), gap (rods, 3), gap_length (rods,), net_force
+        (3,), net_torque (3,), acceleration (3,), angular_acceleration (3,))."""
+        r = self._vec.joint_loads()
+        return type(r)(*(t[0] for t in r))
+
     def save_data(self, filename_video, fps):
         """The reference renders `rod_parameters_dict` to a video here (soft_pendulum.py:253-256, flat_env.py:410-420);
         drawing is out of scope: the data is in `rod_parameters_dict`, nothing is written."""
@@ -676,6 +683,30 @@ class VecRodEnvBase:
         if why is not None:
             raise ValueError(why)
         r = be.muscle_loads()
+        return type(r)(*(self._out(t) for t in r))
+
+    def joint_loads(self):
+        """JointLoads(body_force, body_torque, arm_force, arm_torque, gap, gap_length, net_force, net_torque,
+        acceleration, angular_acceleration) of an env whose arms are joined to a rigid body (OctoFlat, OctoFlatLite,
+        OctoArmPullWeight, OctoCrawl, OctoArmTwo, OctoReach): what the reference's FixedJoint2Rigid computes in every
+        substep and returns none of — the pull on the weight, the propulsive force and turning moment the arms give the
+        head, what an IMU on the head would read — without leaving the device.  Per arm (N, rods_per_env, 3): body_force
+        = contact_force, added to the body (lab frame); body_torque, added to the body (body frame); arm_force =
+        -body_force, added to the arm's node 0; arm_torque, added to the arm's element 0 (its material frame); gap, node
+        0 minus its connection point, and gap_length (N, rods_per_env).  For the body (N, 3): net_force and net_torque,
+        summed over the arms in arm order; acceleration = net_force / head mass with a_z = 0; angular_acceleration =
+        (0, 0, net_torque_z / J_3), body frame; both zero for the held head of OctoReach.  THE INSTANT is
+        ground_reaction()'s: one evaluation at the resident state, not the value the last substep applied
+        (include/softrod.h softrod_joint_loads).  HIP backend only: elsewhere NotImplementedError; an env without a
+        rigid body raises ValueError.  Device tensors, views of one buffer overwritten by the next call (NumPy copies
+        with numpy_output=True)."""
+        be = self.backend
+        if not hasattr(be, "joint_loads"):
+            raise NotImplementedError(f"joint loads need the HIP backend, not {type(be).__name__}")
+        why = _capi.joint_loads_refusal(self.cfg)
+        if why is not None:
+            raise ValueError(why)
+        r = be.joint_loads()
         return type(r)(*(self._out(t) for t in r))
 
     # -- per-env material (domain randomisation) ----------------------------------------

@@ -755,6 +755,43 @@ int softrod_rod_strains(softrod_handle* h, double* out, void* stream);
  * softrod_set_muscle_layers has not been called".                                                               */
 int softrod_muscle_loads(softrod_handle* h, double* out, void* stream);
 
+/* Joint loads: what the reference's FixedJoint2Rigid (gym_softrobot/utils/custom_elastica/joint.py:47-219) computes in
+ * every substep and returns none of — _apply_forces returns contact_force and apply_forces drops it — for every arm
+ * of every env whose arms are joined to a rigid body, and what the body makes of their sum, on the device: the pull
+ * on the weight of OctoArmPullWeight, the propulsive force and turning moment the arms give the head of OctoFlat and
+ * OctoCrawl, the acceleration an IMU on the head would read.  out: device [n_envs][rods_per_env + 1][16] float64,
+ * rods_per_env as for softrod_rod_energies (n_arm for OctoFlat, OctoFlatLite and the muscle octopus, 1 for
+ * OctoArmPullWeight).
+ * Row a < rods_per_env is the joint of arm a, in the reference's words:
+ *   columns 0-2    contact_force: what the joint adds to the body's external_forces, lab frame
+ *   columns 3-5    -Q_body . torque: what it adds to the body's external_torques, body frame
+ *   columns 6-8    -contact_force: added to the arm's node 0; the exact negation of columns 0-2
+ *   columns 9-11   Q_arm[..., 0] . torque: added to the arm's element 0, that element's material frame
+ *   columns 12-14  end_distance_vector: the arm's node 0 minus its connection point, rigid_rod_pos (the body's
+ *                  position with z zeroed) plus rigid_rod_connection_dir * head_radius
+ *   column  15     end_distance
+ * Row rods_per_env is the body:
+ *   columns 0-2    net force: columns 0-2 summed over the arms in arm order 0, 1, ..., added left to right (the
+ *                  order of the reference's loop over its connections; bitwise the same from run to run)
+ *   columns 3-5    net torque, summed the same way
+ *   columns 6-8    linear acceleration f / head_mass under the body's constraints:
+ *                  BodyBoundaryCondition.compute_constrain_rates holds v_z, so a_z = +0.0
+ *   columns 9-11   angular acceleration in the body frame, (+0.0, +0.0, t_z / J_3).  The gyroscopic term (J w) x w of
+ *                  update_accelerations vanishes identically for the constrained body: its omega is held to
+ *                  (0, 0, w_z) and its inertia is diagonal, so J w is parallel to w
+ *   columns 12-15  +0.0
+ * With softrod_config.head_fixed (OneEndFixedBC on the body: OctoReach) columns 6-11 of the body's row are all +0.0;
+ * the forces and torques are still reported.  Every column of every row is written by every call.
+ * THE INSTANT is softrod_ground_reaction's: ONE evaluation at x, v, Q of the arms and of the body as they stand in
+ * memory — no half kinematic step, no constrain_values.  It is NOT the value the last substep applied, which was
+ * taken at the mid-substep configuration.
+ * ARITHMETIC: float64 as written (IEEE division and sqrt, no contraction), one kernel for SOFTROD_MATH_LIBM and
+ * SOFTROD_MATH_FAST handles.  Asynchronous on `stream`, like softrod_rod_energies; capturable.  It reads the state
+ * and writes `out` only.
+ * Errors, each SOFTROD_EINVAL with its text in softrod_last_error: "joint loads: null handle", "joint loads: null
+ * output buffer", "joint loads: this handle has no rigid body" (no SOFTROD_FEAT_OCTO_HEAD).                      */
+int softrod_joint_loads(softrod_handle* h, double* out, void* stream);
+
 /* Per-env rod material, for domain randomisation of single-rod envs.  Upstream has no counterpart: there
  * every env builds its rod with CosseratRod.straight_rod(..., density, youngs_modulus, shear_modulus) and
  * AnalyticalLinearDamper(damping_constant, ...), and a batch of them shares one softrod_config.  This call
