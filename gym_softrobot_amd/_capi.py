@@ -821,6 +821,25 @@ def joint_loads_refusal(cfg: "SoftrodConfig"):
     return None
 
 
+# what softrod_rod_dynamics answers to a null handle / a null `out`, before it looks at the handle
+ROD_DYNAMICS_ARGUMENT_ERRORS = ("rod dynamics: null handle", "rod dynamics: null output buffer")
+
+
+def rod_dynamics_refusal(cfg: "SoftrodConfig", muscles_set: bool = True):
+    """Why softrod_rod_dynamics would refuse a handle of `cfg` (None: it would not), in the library's own words: the
+    read-out serves every handle whose rods have one slot per lane (up to 63 elements) except SoftArmTracking's, whose
+    spline muscle torques are not in the resident state.  `muscles_set`: whether softrod_set_muscle_layers has been
+    called on a COOMM muscle handle (the backend calls it when it builds one)."""
+    feats = int(cfg.features)
+    if feats & FEAT_SPLINE_MUSCLE_TORQUES:
+        return "rod dynamics: not with spline muscle torques (loads that are not in the resident state)"
+    if int(cfg.n_elem) > 63:
+        return "rod dynamics: rods of up to 63 elements only (not the two-slot or windowed long rods)"
+    if feats & FEAT_COOMM_MUSCLES and not muscles_set:
+        return "rod dynamics: softrod_set_muscle_layers has not been called"
+    return None
+
+
 def env_contact_defaults(cfg: "SoftrodConfig") -> "np.ndarray":
     """(8,) float64: the config's own contact_k, contact_nu, kinetic_mu[3], static_mu[3] (forward, backward,
     sideways)."""
@@ -897,6 +916,7 @@ _EXPORTS = {
     "softrod_rod_strains": (C.c_int, [_VP, _VP, _VP]),
     "softrod_muscle_loads": (C.c_int, [_VP, _VP, _VP]),
     "softrod_joint_loads": (C.c_int, [_VP, _VP, _VP]),
+    "softrod_rod_dynamics": (C.c_int, [_VP, _VP, _VP]),
     "softrod_set_env_material": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_set_env_contact": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_substeps": (C.c_int, [_VP, _VP, C.c_int, _VP]),

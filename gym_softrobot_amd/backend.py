@@ -11,7 +11,8 @@ import torch
 
 from . import _capi
 from ._capi import LANE_STRIDE, SoftrodConfig, SoftrodStateView, check, load_library
-from .diagnostics import JointLoads, MuscleLoads, RodStrains, joint_loads_views, muscle_loads_views, rod_strains_views
+from .diagnostics import (JointLoads, MuscleLoads, RodDynamics, RodStrains, joint_loads_views, muscle_loads_views,
+                          rod_dynamics_views, rod_strains_views)
 
 
 class _DevArray:
@@ -75,7 +76,7 @@ class HipRodBackend:
         # per-handle physics tables that live outside softrod_config (action basis, spline table,
         # radius profile): their bytes go into config_fingerprint()
         self._tables: Dict[str, bytes] = {}
-        self._readouts: Dict[str, torch.Tensor] = {}     # rod_energies / ground_reaction / rod_strains / muscle_loads / joint_loads buffers (_readout)
+        self._readouts: Dict[str, torch.Tensor] = {}     # rod_energies / ground_reaction / rod_strains / muscle_loads / joint_loads / rod_dynamics buffers (_readout)
         check(self._lib.softrod_create(C.byref(self.cfg), self.device_index, C.byref(self._h)))
         if self.cfg.features & _capi.FEAT_REST_KAPPA_ACTION:
             if self.is_octo:
@@ -356,6 +357,16 @@ class HipRodBackend:
         allocated on first use and overwritten by the next call."""
         rods = _capi.config_rods_per_env(self.cfg)
         return joint_loads_views(self._readout("joint_loads", rods + 1, 16))
+
+    def rod_dynamics(self) -> RodDynamics:
+        """softrod_rod_dynamics: RodDynamics(internal_force, internal_torque, external_force, external_torque,
+        acceleration, angular_acceleration) of float64 device tensors — (n_envs, rods_per_env, 3, n_elem + 1) for the
+        three nodal fields (lab frame), (n_envs, rods_per_env, 3, n_elem) for the three per-element ones (material
+        frame) — every load the substep's force evaluation applies and the accelerations they give, from ONE
+        evaluation at the resident state (not the value the last substep applied: include/softrod.h).  Views of one
+        (n_envs, rods_per_env, 18, n_elem + 1) buffer allocated on first use and overwritten by the next call."""
+        rods = _capi.config_rods_per_env(self.cfg)
+        return rod_dynamics_views(self._readout("rod_dynamics", rods, 18, int(self.cfg.n_elem) + 1))
 
     def time_limit(self) -> torch.Tensor:
         """early_termination handles: the last step's time-limit flag per env (row 0 of softrod_state_view.env_aux)

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "softrod_kernels.hpp"
+#include "softrod_dynamics_readout.hpp"
 
 using namespace softrod;
 
@@ -495,6 +496,17 @@ const char* ground_reaction_why_not(const softrod_handle* h) {
         return "ground reaction: not with a point force or spline muscle torques (loads that are not in the resident state)";
     if (h->cfg.n_elem > 63)          // (up to 63 elements a rod has one slot per lane and no windows: softrod_create)
         return "ground reaction: rods of up to 63 elements only (not the two-slot or windowed long rods)";
+    return nullptr;
+}
+// softrod_rod_dynamics' scope, as ground_reaction_why_not (the Python copy is rod_dynamics_refusal in _capi.py).
+const char* rod_dynamics_why_not(const softrod_handle* h) {
+    const unsigned f = h->cfg.features;
+    if (f & SOFTROD_FEAT_SPLINE_MUSCLE_TORQUES)
+        return "rod dynamics: not with spline muscle torques (loads that are not in the resident state)";
+    if (h->cfg.n_elem > 63)          // (up to 63 elements a rod has one slot per lane and no windows: softrod_create)
+        return "rod dynamics: rods of up to 63 elements only (not the two-slot or windowed long rods)";
+    if ((f & SOFTROD_FEAT_COOMM_MUSCLES) && !h->muscles_set)
+        return "rod dynamics: softrod_set_muscle_layers has not been called";
     return nullptr;
 }
 const char* why_no_row(const softrod_handle* h, unsigned opts) {
@@ -1907,6 +1919,15 @@ int softrod_joint_loads(softrod_handle* h, double* out, void* stream) {
     if (!out) return fail(h, SOFTROD_EINVAL, "joint loads: null output buffer");
     if (!(h->cfg.features & SOFTROD_FEAT_OCTO_HEAD)) return fail(h, SOFTROD_EINVAL, "joint loads: this handle has no rigid body");
     return launch_readout(h, softrod_joint_loads_kernel, out, stream, ReadoutGrid::kPerEnv);
+}
+
+int softrod_rod_dynamics(softrod_handle* h, double* out, void* stream) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "rod dynamics: null handle");
+    if (!out) return fail(h, SOFTROD_EINVAL, "rod dynamics: null output buffer");
+    if (const char* why = rod_dynamics_why_not(h)) return fail(h, SOFTROD_EINVAL, why);
+    // The kernel's own test for a joint is SOFTROD_FEAT_OCTO_HEAD and its arm is readout_rod's: rod_layout gives the
+    // weight-pulling arm (one rod per env) arm 0, which is the joint's own index there.
+    return launch_readout(h, softrod_rod_dynamics_kernel, out, stream);
 }
 
 int softrod_state_view_get(softrod_handle* h, softrod_state_view* out) {

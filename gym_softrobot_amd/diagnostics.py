@@ -305,6 +305,29 @@ def joint_loads_views(buf) -> JointLoads:
                       body[..., 0:3], body[..., 3:6], body[..., 6:9], body[..., 9:12])
 
 
+class RodDynamics(NamedTuple):
+    """What softrod_rod_dynamics / rod_dynamics() return (include/softrod.h): the two sides of every rod's equation of
+    motion from ONE evaluation at the resident state — internal_force (.., rods, 3, n_elem + 1) on the nodes (lab
+    frame) and internal_torque (.., rods, 3, n_elem) on the elements (material frame), CosseratRod's
+    _compute_internal_forces / _torques; external_force (.., 3, n_elem + 1) and external_torque (.., 3, n_elem),
+    everything synchronize adds: the joint, gravity, the point force, the tip force, the muscle layers' equivalent
+    loads and the plane contact; acceleration (.., 3, n_elem + 1) = (internal_force + external_force) / mass and
+    angular_acceleration (.., 3, n_elem) = J^-1 (internal_torque + external_torque) e, update_accelerations'."""
+    internal_force: object
+    internal_torque: object
+    external_force: object
+    external_torque: object
+    acceleration: object
+    angular_acceleration: object
+
+
+def rod_dynamics_views(buf) -> RodDynamics:
+    """The six fields as views of softrod_rod_dynamics' buffer (.., rods, 18, n_elem + 1): three rows each, the
+    per-element fields without the last column."""
+    return RodDynamics(buf[..., 0:3, :], buf[..., 3:6, :-1], buf[..., 6:9, :], buf[..., 9:12, :-1],
+                       buf[..., 12:15, :], buf[..., 15:18, :-1])
+
+
 def _z_rotation(vector, theta):
     """joint.py:7-17."""
     theta = theta / 180.0 * np.pi

@@ -172,6 +172,13 @@ class SingleRodEnv(GymEnv):
         r = self._vec.joint_loads()
         return type(r)(*(t[0] for t in r))
 
+    def rod_dynamics(self):
+        """VecRodEnvBase.rod_dynamics of this env, without the env axis, as NumPy arrays: RodDynamics(internal_force
+        (rods, 3, n_elem + 1), internal_torque (rods, 3, n_elem), external_force (rods, 3, n_elem + 1), external_torque
+        (rods, 3, n_elem), acceleration (rods, 3, n_elem + 1), angular_acceleration (rods, 3, n_elem))."""
+        r = self._vec.rod_dynamics()
+        return type(r)(*(t[0] for t in r))
+
     def save_data(self, filename_video, fps):
         """The reference renders `rod_parameters_dict` to a video here (soft_pendulum.py:253-256, flat_env.py:410-420);
         drawing is out of scope: the data is in `rod_parameters_dict`, nothing is written."""
@@ -707,6 +714,34 @@ class VecRodEnvBase:
         if why is not None:
             raise ValueError(why)
         r = be.joint_loads()
+        return type(r)(*(self._out(t) for t in r))
+
+    def rod_dynamics(self):
+        """RodDynamics(internal_force, internal_torque, external_force, external_torque, acceleration,
+        angular_acceleration) of every rod: the two sides of its equation of motion, what PyElastica keeps on every
+        rod (internal_forces / internal_torques, external_forces / external_torques, and acceleration_collection /
+        alpha_collection after update_accelerations) and the reference returns none of — what an accelerometer or a
+        gyro-rate sensor on the arm would read, and what a reward that penalises jerk or effort needs — without leaving
+        the device.  internal_force, external_force and acceleration (N, rods_per_env, 3, n_elem + 1) on the nodes,
+        lab frame; internal_torque, external_torque and angular_acceleration (N, rods_per_env, 3, n_elem) on the
+        elements, material frame.  external_* hold everything synchronize adds, gathered in the substep's own order:
+        FixedJoint2Rigid on node 0 / element 0, then gravity, the point force, the tip force and the COOMM layers'
+        equivalent loads, and the plane contact before or after them as contact_before_forcing says.  acceleration =
+        (internal_force + external_force) / mass, angular_acceleration = J^-1 (internal_torque + external_torque) e;
+        constraints, dampers and suckers act on values and rates and do not enter.  THE INSTANT is
+        ground_reaction()'s: one fresh evaluation at the state as it stands, not the value the last substep applied
+        (include/softrod.h softrod_rod_dynamics); the point force is the resident previous action (none for an env
+        just reset), the muscle activations the resident rows as the last action left them.  Per-env material,
+        per-env contact and a radius profile are honoured.  Every env but SoftArmTracking, rods of up to 63 elements,
+        on the HIP backend; elsewhere NotImplementedError.  Device tensors, views of one buffer overwritten by the
+        next call (NumPy copies with numpy_output=True)."""
+        be = self.backend
+        if not hasattr(be, "rod_dynamics"):
+            raise NotImplementedError(f"rod dynamics need the HIP backend, not {type(be).__name__}")
+        why = _capi.rod_dynamics_refusal(self.cfg)
+        if why is not None:
+            raise NotImplementedError(why)
+        r = be.rod_dynamics()
         return type(r)(*(self._out(t) for t in r))
 
     # -- per-env material (domain randomisation) ----------------------------------------

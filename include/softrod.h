@@ -792,6 +792,48 @@ int softrod_muscle_loads(softrod_handle* h, double* out, void* stream);
  * output buffer", "joint loads: this handle has no rigid body" (no SOFTROD_FEAT_OCTO_HEAD).                      */
 int softrod_joint_loads(softrod_handle* h, double* out, void* stream);
 
+/* Rod dynamics: the two sides of every rod's equation of motion — what PyElastica keeps on every rod as
+ * internal_forces / internal_torques, external_forces / external_torques and, once update_accelerations has run,
+ * acceleration_collection / alpha_collection, and the reference returns none of — for every rod of every env, on the
+ * device: what an accelerometer or a gyro-rate sensor on a soft arm would read, what a reward that penalises jerk or
+ * effort needs.  The other read-outs return one contribution each (softrod_ground_reaction the contact's,
+ * softrod_muscle_loads the muscles', softrod_joint_loads the joint's); this one returns their sum.
+ * out: device [n_envs][rods_per_env][18][n_elem + 1] float64, rods_per_env as for softrod_rod_energies:
+ *   rows 0-2    internal force on the nodes, lab frame: CosseratRod._compute_internal_forces           n_elem + 1 columns
+ *   rows 3-5    internal torque on the elements, material frame: _compute_internal_torques — bend/twist
+ *               difference, kappa x B kappa, shear couple, (J w / e) x w, unsteady dilatation          n_elem
+ *   rows 6-8    external force on the nodes, lab frame: everything synchronize adds                    n_elem + 1
+ *   rows 9-11   external torque on the elements, material frame: everything it adds                    n_elem
+ *   rows 12-14  acceleration = (internal force + external force) / mass, lab frame                     n_elem + 1
+ *   rows 15-17  angular acceleration = J^-1 (internal torque + external torque) e, material frame      n_elem
+ * Column n_elem of the per-element rows is written as +0.0; every column of every row is written by every call.
+ * THE INSTANT is softrod_ground_reaction's: ONE FRESH evaluation at x, v, Q, omega, rest_kappa (and the rigid body's
+ * state) as they stand in device memory, with no half kinematic step and no constrain_values before it.  It is NOT
+ * the value the last substep applied: that one was taken at the mid-substep configuration with the pre-update rates.
+ * Constraints, the analytical damper, the Laplace filter and the suckers act on values and rates, not on loads, and
+ * do not enter: this is update_accelerations, before constrain_rates.
+ * THE ORDER in which the external loads are gathered is the substep's own: FixedJoint2Rigid on node 0 / element 0 of
+ * every arm of a handle with SOFTROD_FEAT_OCTO_HEAD; then the forcing group — gravity times nodal mass, the point
+ * force of SOFTROD_FEAT_POINT_FORCE_NODE0_X (which ASSIGNS component x of node 0), the tip force, the COOMM layers'
+ * equivalent loads — and the plane contact (the literal law of softrod_ground_reaction, reading f_int + f_ext and
+ * t_int + t_ext of its moment), before or after that group as contact_before_forcing says.
+ * THE ACTION-BORNE INPUTS are read from the resident state.  The point force is the env's resident previous action
+ * as the step prologue applies it, (double)prev_action[0], and 0.0 for an env whose time is 0: a fresh simulator has
+ * no point force until the first set_action, while _prev_action survives reset.  The muscle activations are the
+ * rows softrod_state_view.muscle_activation as they stand, read per element, and the muscle law (PARITY UNPINNED, as
+ * for softrod_muscle_loads) is evaluated on the strains of THIS state — softrod_muscle_loads' instant is another
+ * one unless the env's time is 0.
+ * ARITHMETIC: float64 as written (IEEE division and sqrt, libm acos / sin / cos, no contraction), one kernel for
+ * SOFTROD_MATH_LIBM and SOFTROD_MATH_FAST handles.  The per-env tables of softrod_set_env_material /
+ * softrod_set_env_contact and the radius profile of a tapered rod are honoured.  Asynchronous on `stream`, like
+ * softrod_rod_energies; capturable.  It reads the state and writes `out` only.
+ * Scope: every handle whose rods have one slot per lane (n_elem <= 63), either math mode, every env kind except
+ * SOFTROD_ENV_SOFT_ARM.  Errors, each SOFTROD_EINVAL with its text in softrod_last_error: "rod dynamics: null
+ * handle", "rod dynamics: null output buffer", "rod dynamics: not with spline muscle torques (loads that are not in
+ * the resident state)", "rod dynamics: rods of up to 63 elements only (not the two-slot or windowed long rods)",
+ * "rod dynamics: softrod_set_muscle_layers has not been called".                                                */
+int softrod_rod_dynamics(softrod_handle* h, double* out, void* stream);
+
 /* Per-env rod material, for domain randomisation of single-rod envs.  Upstream has no counterpart: there
  * every env builds its rod with CosseratRod.straight_rod(..., density, youngs_modulus, shear_modulus) and
  * AnalyticalLinearDamper(damping_constant, ...), and a batch of them shares one softrod_config.  This call
