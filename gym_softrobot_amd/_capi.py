@@ -869,6 +869,33 @@ class SoftrodError(RuntimeError):
     pass
 
 
+def copy_envs_pairs(src, dst):
+    """The (src, dst) arguments of copy_envs / fork as two contiguous int32 arrays of one length: array-likes of
+    ints (a range, a list, an integer array or tensor), a scalar `src` broadcast over `dst`.  ValueError for anything
+    that is not integers, more than one dimension, or lengths that differ.  Which indices are acceptable is the
+    library's to say (softrod_copy_envs)."""
+    import numpy as np
+
+    out = []
+    for name, v in (("src", src), ("dst", dst)):
+        a = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else list(v) if isinstance(v, range) else v)
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError(f"copy_envs: {name} must hold integers, got dtype {a.dtype}")
+        if a.ndim > 1:
+            raise ValueError(f"copy_envs: {name} must be a scalar or one-dimensional, got shape {a.shape}")
+        if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+            raise ValueError(f"copy_envs: {name} does not fit an int32")
+        out.append(a.astype(np.int32))
+    s, d = out
+    if d.ndim == 0:
+        d = d.reshape(1)
+    if s.ndim == 0:
+        s = np.full(d.shape, s, np.int32)
+    if s.shape != d.shape:
+        raise ValueError(f"copy_envs: src has {s.size} entries, dst has {d.size}")
+    return np.ascontiguousarray(s), np.ascontiguousarray(d)
+
+
 _VP = C.c_void_p
 _EXPORTS = {
     # name: (restype, argtypes)
@@ -919,6 +946,7 @@ _EXPORTS = {
     "softrod_rod_dynamics": (C.c_int, [_VP, _VP, _VP]),
     "softrod_set_env_material": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_set_env_contact": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "softrod_copy_envs": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP]),
     "softrod_substeps": (C.c_int, [_VP, _VP, C.c_int, _VP]),
     "softrod_state_view_get": (C.c_int, [_VP, C.POINTER(SoftrodStateView)]),
     "softrod_set_timing": (C.c_int, [_VP, C.c_int]),

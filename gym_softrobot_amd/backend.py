@@ -164,8 +164,26 @@ class HipRodBackend:
         set_env_contact."""
         return _env_table(self, "contact")
 
+    def copy_envs(self, src, dst) -> None:
+        """softrod_copy_envs: fork on the device — env dst[i] becomes a bitwise copy of env src[i] as it stood before
+        the call: its part of every array of state(), and its row of the per-env material / contact tables where they
+        exist.  `src`, `dst`: array-likes of ints of one length; a scalar `src` broadcasts over `dst`
+        (copy_envs(0, range(1, n))).  One small upload and one kernel on the current stream, no synchronisation —
+        where snapshot() / restore() move the whole batch through the host.  Not graph-capturable.  SoftrodError
+        where the library refuses (include/softrod.h): an index outside the batch, an env twice in dst, an env that
+        is the dst of one pair and the src of another, a handle with device-side auto-reset; a refused call changes
+        nothing.  An empty call and a pair with src == dst are no-ops.  env_material() / env_contact() and a later
+        snapshot() follow the copy."""
+        s, d = _capi.copy_envs_pairs(src, dst)
+        check(self._lib.softrod_copy_envs(self._h, s.ctypes.data if s.size else None, d.ctypes.data if d.size else None,
+                                          int(s.size), self._stream()), self._h)
+        for name in ("_env_material", "_env_contact"):
+            tab = getattr(self, name, None)
+            if tab is not None:
+                tab[d] = tab[s]
+
     def reset(self, theta0: np.ndarray, mask: Optional[np.ndarray] = None) -> None:
-        th = np.ascontiguousarray(theta0, dtype=np.float64).reshape(self.n_envs)
+        th =np.ascontiguousarray(theta0, dtype=np.float64).reshape(self.n_envs)
         m = None
         if mask is not None:
             m = np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.n_envs)

@@ -17,6 +17,7 @@
 
 #include "softrod_kernels.hpp"
 #include "softrod_dynamics_readout.hpp"
+#include "softrod_copy_envs.hpp"
 
 using namespace softrod;
 
@@ -88,6 +89,11 @@ struct softrod_handle {
     hipEvent_t ev_queue = nullptr;  // guards reuse of h_queue / h_produced
     EnvTable<EnvMaterial> env_mat;      // softrod_set_env_material
     EnvTable<EnvContact> env_contact;   // softrod_set_env_contact
+    // softrod_copy_envs: the (src, dst) pairs of a call on their way to the device, sized for n_envs pairs at create
+    int2* d_pairs = nullptr;        // [N]
+    int2* h_pairs = nullptr;        // pinned [N]
+    hipEvent_t ev_pairs = nullptr;  // guards reuse of h_pairs
+    std::vector<uint8_t> is_dst;    // [N] scratch of its validation, all zero between calls
     std::string err;
 };
 
@@ -845,6 +851,70 @@ void shape_handle(softrod_handle* h) {
     }
 }
 
+
+// Why softrod_copy_envs refuses these arguments (empty: it does not).  Host only; leaves h->is_dst all zero.
+std::string copy_envs_why_not(softrod_handle* h, const int32_t* src, const int32_t* dst, int count) {
+    const int N = h->cfg.n_envs;
+    if (h->q_depth > 0)
+        return "copy envs: not on a handle with device-side auto-reset (the pending-reset flags and the staged queue "
+               "belong to each env's RNG future)";
+    if (count < 0 || count > N) return "copy envs: count " + std::to_string(count) + " is outside 0 .. n_envs = " + std::to_string(N);
+    if (count > 0 && (!src || !dst)) return "copy envs: null src or dst";
+    for (int i = 0; i < count; ++i)
+        for (const int e : {src[i], dst[i]})
+            if (e < 0 || e >= N)
+                return "copy envs: env index " + std::to_string(e) + " (pair " + std::to_string(i) + ") is outside 0 .. " + std::to_string(N - 1);
+    std::string why;
+    for (int i = 0; i < count && why.empty(); ++i) {
+        if (h->is_dst[dst[i]]) why = "copy envs: env " + std::to_string(dst[i]) + " appears twice in dst";
+        h->is_dst[dst[i]] = 1;
+    }
+    // the kernel reads and writes in place: a row that one pair writes and another reads would depend on scheduling
+    for (int i = 0; i < count && why.empty(); ++i)
+        if (src[i] != dst[i] && h->is_dst[src[i]])
+            why = "copy envs: env " + std::to_string(src[i]) + " is the dst of one pair and the src of another";
+    for (int i = 0; i < count; ++i) h->is_dst[dst[i]] = 0;
+    return why;
+}
+
+// Every per-env array of the handle, as softrod_copy_envs_kernel takes them: the arrays of softrod_state_view (the
+// audit of softrod_create's allocation list: everything else it allocates is shared by all envs — spline table,
+// action basis, material and muscle tables, clock table, the parameter copies, the scatter ticket — or reset staging)
+// and the per-env tables that exist.
+CopyTable copy_table(const softrod_handle* h) {
+    CopyTable T{};
+    T.n_envs = h->cfg.n_envs;
+    auto add = [&T](const void* p, size_t comps, size_t row_bytes) {
+        if (p) T.a[T.n++] = CopyArray{(unsigned char*)const_cast<void*>(p), (unsigned)comps, (unsigned)row_bytes};
+    };
+    const StatePtrs& S = h->S;
+    const softrod_config& c = h->cfg;
+    const size_t W = (size_t)rod_layout(h).lane_stride * sizeof(double);
+    const size_t adim = (size_t)softrod_config_action_dim(&c);
+    const size_t per = is_mocto(h) ? (size_t)c.n_arm : 1;      // SuckerControllers per env
+    add(S.pos, 3, W); add(S.vel, 3, W); add(S.dir, 9, W); add(S.omg, 3, W); add(S.tan, 3, W);
+    add(S.kap, 3, W); add(S.rkap, 3, W); add(S.envmem, 1, W); add(S.mact, SOFTROD_MAX_MUSCLES, W);
+    add(S.time, 1, sizeof(double)); add(S.ctrl, 4, sizeof(double)); add(S.head, 20, sizeof(double));
+    add(S.bc, 12, sizeof(double)); add(S.aux, 8, sizeof(double));
+    add(S.prev_action, 1, (adim > 7 ? adim : 7) * sizeof(float));
+    add(S.prev_kappa, 1, (size_t)c.n_arm * (size_t)(c.n_elem - 1) * sizeof(float));
+    add(S.sucker, SOFTROD_MAX_SUCKERS, per * sizeof(double));
+    add(S.sucker_idx, SOFTROD_MAX_SUCKERS, per * sizeof(int));
+    add(h->env_mat.dev, 1, sizeof(EnvMaterial));
+    add(h->env_contact.dev, 1, sizeof(EnvContact));
+    static_assert(kCopyMaxArrays >= 20, "copy_table adds up to 20 arrays");
+    return T;
+}
+
+// The pinned copy of a per-env table follows the device rows: the next softrod_set_env_* uploads all of it.
+template <class Row>
+hipError_t copy_table_rows(EnvTable<Row>& T, const int2* pairs, int n) {
+    if (!T.dev) return hipSuccess;
+    const hipError_t e = hipEventSynchronize(T.ev);      // the previous upload has left the staging buffer
+    if (e != hipSuccess) return e;
+    for (int i = 0; i < n; ++i) T.host[pairs[i].y] = T.host[pairs[i].x];
+    return hipSuccess;
+}
 }  // namespace
 
 extern "C" {
@@ -1194,6 +1264,11 @@ int softrod_create(const softrod_config* cfg, int device, softrod_handle** out) 
     if (rc == SOFTROD_OK && hipHostMalloc((void**)&h->h_mask, N) != hipSuccess) rc = SOFTROD_ENOMEM;
     if (rc == SOFTROD_OK && hipEventCreateWithFlags(&h->ev_reset, hipEventDisableTiming) != hipSuccess)
         rc = SOFTROD_EHIP;
+    alloc(h->d_pairs, N * sizeof(int2));
+    if (rc == SOFTROD_OK && hipHostMalloc((void**)&h->h_pairs, N * sizeof(int2)) != hipSuccess) rc = SOFTROD_ENOMEM;
+    if (rc == SOFTROD_OK && hipEventCreateWithFlags(&h->ev_pairs, hipEventDisableTiming) != hipSuccess)
+        rc = SOFTROD_EHIP;
+    h->is_dst.assign(N, 0);
     upload(h->d_state, &h->S, sizeof(StatePtrs));
     if (rc != SOFTROD_OK) {
         softrod_destroy(h);
@@ -1930,6 +2005,26 @@ int softrod_rod_dynamics(softrod_handle* h, double* out, void* stream) {
     return launch_readout(h, softrod_rod_dynamics_kernel, out, stream);
 }
 
+int softrod_copy_envs(softrod_handle* h, const int32_t* src, const int32_t* dst, int count, void* stream) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "copy envs: null handle");
+    const std::string why = copy_envs_why_not(h, src, dst, count);
+    if (!why.empty()) return fail(h, SOFTROD_EINVAL, why);
+    SR_ON_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    SR_HIP(h, hipEventSynchronize(h->ev_pairs));     // the previous call's pairs have left the staging buffer
+    int n = 0;
+    for (int i = 0; i < count; ++i)
+        if (src[i] != dst[i]) h->h_pairs[n++] = make_int2(src[i], dst[i]);
+    if (n == 0) return SOFTROD_OK;
+    SR_HIP(h, copy_table_rows(h->env_mat, h->h_pairs, n));
+    SR_HIP(h, copy_table_rows(h->env_contact, h->h_pairs, n));
+    SR_HIP(h, hipMemcpyAsync(h->d_pairs, h->h_pairs, (size_t)n * sizeof(int2), hipMemcpyHostToDevice, st));
+    SR_HIP(h, hipEventRecord(h->ev_pairs, st));
+    hipLaunchKernelGGL(softrod_copy_envs_kernel, dim3((unsigned)n), dim3(kCopyThreads), 0, st, copy_table(h), h->d_pairs);
+    SR_HIP(h, hipGetLastError());
+    return SOFTROD_OK;
+}
+
 int softrod_state_view_get(softrod_handle* h, softrod_state_view* out) {
     if (!h || !out) return fail(h, SOFTROD_EINVAL, "null argument");
     out->n_envs = h->cfg.n_envs;
@@ -2034,6 +2129,8 @@ int softrod_destroy(softrod_handle* h) {
     for (hipEvent_t e : h->ev_start) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->ev_stop) (void)hipEventDestroy(e);
     if (h->ev_reset) (void)hipEventDestroy(h->ev_reset);
+    if (h->h_pairs) (void)hipHostFree(h->h_pairs);
+    if (h->ev_pairs) (void)hipEventDestroy(h->ev_pairs);
     delete h;
     return SOFTROD_OK;
 }

@@ -930,6 +930,49 @@ class VecRodEnvBase:
         self._steps += 1
         return packed, self._infos(self._times())
 
+    # -- fork: many rollouts from one env's current state (planning) --------------------
+    def fork(self, src, dst, copy_rng: bool = True) -> None:
+        """Make env dst[i] an exact copy of env src[i], now, without leaving the GPU: what CEM, MPPI, population-based
+        training or branching a rollout for a value estimate start from.  `src`, `dst`: array-likes of env indices of
+        one length; a scalar `src` broadcasts, so fork(0, range(1, N)) makes every env a copy of env 0.  The reference
+        has no counterpart (one env is one Python object there).
+
+        Copied: the whole resident state of the env and its per-env material and contact (backend.copy_envs:
+        softrod_copy_envs, include/softrod.h), and the host bookkeeping — steps since reset, a pending host
+        auto-reset, the reset target (`targets`) and the tracked trajectory where the env has them.  With
+        `copy_rng=True` dst also takes the state of src's NumPy stream: the copies then draw the same resets as their
+        source.  With `copy_rng=False` dst keeps its own stream and the copies' next episodes differ.  A copy and its
+        source, stepped with the same actions, return bitwise-equal observations, rewards and flags.
+
+        SoftrodError for indices outside the batch, an env twice in dst, or an env that is the dst of one pair and the
+        src of another (fork in two calls instead); nothing changes then.  NotImplementedError with
+        autoreset="device" (reset records staged on the device belong to each env's RNG future, as for state_dict()).
+        Not offered on the sharded env (distributed.py: src and dst may live on different GPUs) nor on the N = 1
+        single-env classes (SingleRodEnv: there is nothing to fork into)."""
+        if self.device_autoreset:
+            raise NotImplementedError("fork() with autoreset='device': staged reset records are not copied")
+        be = self.backend
+        if not hasattr(be, "copy_envs"):
+            raise NotImplementedError(f"fork needs the HIP backend, not {type(be).__name__}")
+        s, d = _capi.copy_envs_pairs(src, dst)
+        be.copy_envs(s, d)
+        self._steps[d] = self._steps[s]
+        self._needs_reset[d] = self._needs_reset[s]
+        for k in ("targets", "_traj"):
+            rows = getattr(self, k, None)
+            if rows is not None:
+                rows[d] = rows[s]
+        if copy_rng:
+            for i, j in zip(s.tolist(), d.tolist()):
+                if i == j:
+                    continue
+                if self._rngs[i] is None:
+                    self._rngs[j] = None
+                else:
+                    if self._rngs[j] is None:
+                        self._rngs[j], _ = np_random(0)
+                    self._rngs[j].bit_generator.state = self._rngs[i].bit_generator.state
+
     # -- checkpoint / resume ----------------------------------------------------------
     def state_dict(self) -> Dict[str, Any]:
         """Everything needed to continue this batch exactly where it is: the resident state

@@ -877,6 +877,39 @@ int softrod_set_env_material(softrod_handle* h, const double* material, const ui
  * SOFTROD_EINVAL with "per-env contact" in softrod_last_error.  */
 int softrod_set_env_contact(softrod_handle* h, const double* contact, const uint8_t* mask, void* stream);
 
+/* Fork resident envs on the device, for planning: after the call, on `stream`, env dst[i] is an exact (bitwise) copy
+ * of env src[i] as it stood before the call, for i = 0 .. count - 1 — what CEM, MPPI, population-based training and
+ * branching a rollout for a value estimate begin with.  Upstream has no counterpart (an env there is one Python
+ * object; its state is never copied).  Here it replaces the host path of the Python layer, backend.snapshot() +
+ * restore(), which moves the WHOLE batch to the host and back, synchronises the device twice and re-uploads the
+ * per-env tables.  src, dst: host [count] env indices.  Asynchronous on `stream`, like softrod_observe: one small
+ * upload of the pairs (through a pinned buffer the handle owns, sized for n_envs pairs at create: no allocation per
+ * call) and one cold kernel, softrod_copy_envs_kernel (csrc/softrod_copy_envs.hpp), one workgroup per pair.
+ * NOT graph-capturable: the arguments are validated on the host and the pairs are uploaded by the call.
+ * WHAT IS COPIED is every per-env datum the handle keeps:
+ *   - env src's part of every array of softrod_state_view: the rows position, velocity, director, omega, tangents,
+ *     kappa, rest_kappa, env_memory, muscle_activation; the columns time, control, head, bc_targets, env_aux;
+ *     prev_action, prev_kappa; sucker_ratio and sucker_index (the muscle octopus's [4][n_envs * n_arm] form: all
+ *     n_arm entries of the env).  Arrays the handle does not have (NULL in the view) are skipped
+ *   - the env's row of the device tables of softrod_set_env_material and softrod_set_env_contact, where they exist
+ *     (before the first softrod_set_env_* call there is no table and every env runs on the config's values).
+ * softrod_create allocates nothing else per env.  The arrays shared by all envs — `material`, the spline table, the
+ * action basis, the muscle layers — are not touched.  With it softrod_state_view's promise ("a complete snapshot")
+ * holds on the device: a copy and its source, stepped with the same actions, stay bitwise equal.
+ * count == 0 is a successful no-op, and so is a pair with src[i] == dst[i].  One src may feed any number of dst.
+ * Errors, each SOFTROD_EINVAL with its text in softrod_last_error, found on the host before anything is enqueued (a
+ * refused call changes nothing):
+ *   "copy envs: null handle"
+ *   "copy envs: not on a handle with device-side auto-reset ..." (softrod_autoreset_enable: the pending-reset flags
+ *       and the staged queue belong to each env's RNG future)
+ *   "copy envs: count <c> is outside 0 .. n_envs = <N>"
+ *   "copy envs: null src or dst" (with count > 0)
+ *   "copy envs: env index <e> (pair <i>) is outside 0 .. <N - 1>"
+ *   "copy envs: env <e> appears twice in dst"
+ *   "copy envs: env <e> is the dst of one pair and the src of another" (the kernel reads and writes in place: that
+ *       result would depend on scheduling; copy in two calls instead).                                            */
+int softrod_copy_envs(softrod_handle* h, const int32_t* src, const int32_t* dst, int count, void* stream);
+
 /* Run `n` bare PositionVerlet substeps with fixed per-env forcing inputs and no
  * env epilogue (the inner loop of soft_pendulum.py:183-184 alone); `actions`
  * (device [n_envs] float32 or NULL) feeds SOFTROD_FEAT_POINT_FORCE_NODE0_X.
