@@ -11,14 +11,12 @@
 // THE INSTANT is softrod_ground_reaction's: ONE evaluation at x, v, Q of the arms and of the body as they stand in
 // memory — no half kinematic step, no constrain_values.  It is not the value the last substep applied.
 //
-// THE ARITHMETIC is joint_load_literal's (softrod_reaction.hpp), called, not edited: the literal fp64 form of the
-// law, which no step kernel inlines.  It returns the force and the lab-frame torque only, and it may not be edited, so
-// the gap (end_distance_vector, end_distance) is formed here by a SECOND COPY of its angle, connection-point and gap
-// statements.  The two copies agree because they are kept identical by hand — change one and change the other; that
-// the compiler happens to merge them is a matter of cost, not of correctness.  tests/test_gpu_joint_loads.py holds
-// both to the NumPy twin, where force and gap come from one computation.  Everything in
-// this file is compiled without floating-point contraction, so that a product followed by a sum rounds twice, as
-// NumPy does in diagnostics.joint_loads_host and oracle/softrod_oracle_np.py.
+// THE ARITHMETIC is joint_load_literal's (softrod_literal.hpp): the literal fp64 form of the law, which no step
+// kernel inlines, the one rod_literal_joint calls for the ground reaction and the rod dynamics.  Force, torque and
+// the gap they act on (end_distance_vector, end_distance) come from that ONE computation, as they do in the NumPy
+// twin tests/test_gpu_joint_loads.py holds them to.  Everything in this file is compiled without floating-point
+// contraction, so that a product followed by a sum rounds twice, as NumPy does in diagnostics.joint_loads_host and
+// oracle/softrod_oracle_np.py.
 //
 // THE NET ROW is formed in a fixed loop a = 0 .. rods - 1 that reads lane a's values with a wave shuffle and adds
 // them left to right to +0.0: the order of the reference's loop over its connections (head.f_ext += ...), the same
@@ -72,23 +70,8 @@ softrod_joint_loads_kernel(const RodParams P, const StatePtrs S, const int rods,
 
     // Lanes >= rods run the law on zeros: finite values that no shuffle below reads and no store writes; every lane
     // has to reach the shuffle loop.
-    double fj[3], tj[3];
-    joint_load_literal(P, H, arm, x0, v0, x1, fj, tj);
-
-    // end_distance_vector and end_distance: joint_load_literal's own statements, copied (see the head of this file)
-    const double th = (P.joint_angle0 + P.joint_angle_step * (double)arm) / 180.0 * M_PI;
-    const double ct = cos(th), st = sin(th);
-    const double b0 = H.Q[3], b1 = H.Q[4], b2 = H.Q[5];
-    const double dir[3] = {-(ct * b0 - st * b1), -(st * b0 + ct * b1), -b2};
-    double pos[3] = {H.x[0], H.x[1], 0.0};
-    double dv[3], d2 = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        pos[i] = pos[i] + dir[i] * P.head_radius;
-        dv[i] = x0[i] - pos[i];
-        d2 += dv[i] * dv[i];
-    }
-    const double dist = sqrt(d2);
+    const JointLoad J = joint_load_literal(P, H, arm, x0, v0, x1);
+    const double (&fj)[3] = J.f, (&tj)[3] = J.t;
 
     double bt[3], at[3];                               // the torque in the body's frame, negated, and in element 0's
 #pragma unroll
@@ -115,9 +98,9 @@ softrod_joint_loads_kernel(const RodParams P, const StatePtrs S, const int rods,
             o[3 + c] = bt[c];
             o[6 + c] = -fj[c];
             o[9 + c] = at[c];
-            o[12 + c] = dv[c];
+            o[12 + c] = J.gap[c];
         }
-        o[15] = dist;
+        o[15] = J.dist;
     }
     if (arm == 0) {
         double* b = out + ((size_t)env * (size_t)(rods + 1) + (size_t)rods) * kJointCols;

@@ -20,8 +20,10 @@
 // File map: softrod_contact.hpp (rod-plane contact), softrod_fast.hpp (the default step
 // kernel), softrod_planar.hpp (SoftPendulum's planar substep), softrod_octo.hpp (OctoFlat: one
 // env per workgroup), softrod_window.hpp (64..102-element arms on two overlapping windows),
-// and the three cold read-out kernels: softrod_readout.hpp (their shared addressing and load, the rod
-// energies), softrod_reaction.hpp (the ground reaction), softrod_strains.hpp (the strains and internal loads);
+// and the six cold read-out kernels: softrod_literal.hpp (the literal fp64 force evaluation they share),
+// softrod_readout.hpp (their shared addressing and load, the rod energies), softrod_reaction.hpp (the ground
+// reaction), softrod_strains.hpp (the strains and internal loads), softrod_muscle_readout.hpp (the muscle loads),
+// softrod_joint_readout.hpp (the joint loads), softrod_dynamics_readout.hpp (the rod dynamics);
 // this file holds the state layout, the env prologues/epilogues, the reset /
 // observe / auto-reset kernels and the LIBM kernel.
 //
@@ -2160,6 +2162,7 @@ softrod_autoreset_kernel(const RodParams P, const StatePtrs S, float* __restrict
 #include "softrod_fast.hpp"
 #include "softrod_octo.hpp"
 #include "softrod_window.hpp"
+#include "softrod_literal.hpp"
 #include "softrod_readout.hpp"
 #include "softrod_reaction.hpp"
 #include "softrod_strains.hpp"

@@ -1,14 +1,26 @@
 // softrod_readout.hpp — what the per-rod read-out kernels share, and the first of them.
 //
 // The read-outs are cold kernels beside the step kernels: softrod_rod_energies_kernel (here),
-// softrod_rod_strains_kernel (softrod_strains.hpp), softrod_ground_reaction_kernel (softrod_reaction.hpp) and
-// softrod_muscle_loads_kernel (softrod_muscle_readout.hpp).  All four run one wave per rod — env blockIdx.x / rods, arm blockIdx.x % rods, its slots
-// arm * arm_stride .. arm * arm_stride + n_elem of the env's row (`lane_stride` wide: the layouts of
-// softrod_state_view) — so every rod's sums are a plain wave reduction.  Slots past the rod are never read.
+// softrod_rod_strains_kernel (softrod_strains.hpp), softrod_ground_reaction_kernel (softrod_reaction.hpp),
+// softrod_muscle_loads_kernel (softrod_muscle_readout.hpp), softrod_rod_dynamics_kernel (softrod_dynamics_readout.hpp)
+// and softrod_joint_loads_kernel (softrod_joint_readout.hpp).  The first five run one wave per rod — env
+// blockIdx.x / rods, arm blockIdx.x % rods, its slots arm * arm_stride .. arm * arm_stride + n_elem of the env's row
+// (`lane_stride` wide: the layouts of softrod_state_view) — so every rod's sums are a plain wave reduction; the joint
+// loads run one wave per env, one arm per lane.  Slots past the rod are never read.
 //
 // readout_rod is that addressing; readout_load fills the wave's LaneN<EPL> from the resident rows and the
-// boundary-condition targets as the energies, the strains and the muscle loads take them.  The reaction kernel takes only the
-// addressing: its load is masked per element and Voronoi vertex and also clears kappa and the tangents.
+// boundary-condition targets as the energies, the strains and the muscle loads take them.  The ground reaction and
+// the rod dynamics take only the addressing: their load is rod_literal_load's (softrod_literal.hpp), masked per element
+// and Voronoi vertex, which also clears kappa and the tangents.
+//
+// WHO CALLS WHAT of the literal force evaluation (softrod_literal.hpp):
+//   ground reaction   rod_literal_load, rod_literal_internal, rod_literal_joint, rod_literal_contact
+//   rod dynamics      the last three of these and muscle_law_literal<1>; the masked load in its own words
+//                     (softrod_dynamics_readout.hpp says why)
+//   muscle loads      muscle_law_literal<EPL> on rod_strain_config_n's configuration (softrod_strains.hpp)
+//   joint loads       joint_load_literal
+//   energies, strains none: rod_energies_m and its restatement in softrod_strains.hpp (the early-termination step
+//                     kernels inline the original)
 #pragma once
 
 namespace softrod {

@@ -95,7 +95,8 @@ def test_symbol_in_header_library_and_bindings():
         "joint loads: null handle", "joint loads: null output buffer", "joint loads: this handle has no rigid body"}
     kernel = (CSRC / "softrod_joint_readout.hpp").read_text()
     assert "kJointCols = 16" in kernel and "#pragma clang fp contract(off)" in kernel
-    assert "joint_load_literal(P, H, arm, x0, v0, x1, fj, tj);" in kernel
+    assert "const JointLoad J = joint_load_literal(P, H, arm, x0, v0, x1);" in kernel      # force, torque AND gap from one call
+    assert "o[12 + c] = J.gap[c];" in kernel and "o[15] = J.dist;" in kernel and "sqrt(" not in kernel
     assert "__shared__" not in kernel and "atomic" not in kernel.replace("no atomics", "")
     assert "softrod_joint_loads" in _capi.EXPORTED_SYMBOLS
     assert _capi._EXPORTS["softrod_joint_loads"] == _capi._EXPORTS["softrod_rod_energies"]

@@ -77,7 +77,11 @@ def test_symbol_header_and_table():
     assert "int softrod_rod_dynamics(softrod_handle* h, double* out, void* stream) {" in source
     kernel = (CSRC / "softrod_dynamics_readout.hpp").read_text()
     assert "kDynamicsRows = 18" in kernel and "#pragma clang fp contract(off)" in kernel
-    assert "joint_load_literal(P, H, arm, x0, v0, x1, fj, tj);" in kernel and "plane_contact_n<1, false, false>(" in kernel
+    assert "rod_literal_joint(P, S, R.N, R.env, R.arm, lane, X, jf, jt);" in kernel
+    assert "rod_literal_contact(P, S, env, lane, X, F, T, fc, dt);" in kernel
+    literal = (CSRC / "softrod_literal.hpp").read_text()                       # ... which call the two laws themselves
+    assert "const JointLoad J = joint_load_literal(P, H, arm, x0, v0, x1);" in literal
+    assert "plane_contact_n<1, false, false>(CP, Pc, lane, CK, X.L, X.xn, X.vn, X.len, F1, tq, fc1);" in literal
     assert "__shared__" not in kernel and "atomic" not in kernel.replace("no atomics", "")
     assert "softrod_rod_dynamics" in _capi.EXPORTED_SYMBOLS
     assert _capi._EXPORTS["softrod_rod_dynamics"] == _capi._EXPORTS["softrod_rod_energies"]
