@@ -666,37 +666,49 @@ __device__ __forceinline__ void general_substeps(const RodParams& P, const RodPa
         }
     }
 }
-// The SoftPendulum kernel's fallback for a state that is NOT planar (written through the state
-// view, or reset with an out-of-plane frame): the general 3-D substeps as an out-of-line call that
-// shares NOTHING with its caller but scalars — it reads the parameters and the array pointers
-// from their device-memory copies (StatePtrs.params / .self), loads the rod from its HBM rows,
-// establishes the constraint invariants, steps, and stores the rod and its clock back; the
-// caller reloads.  Nothing of the caller's lane state is address-taken that way, so the planar
-// path keeps every value in registers and the kernel writes no scratch (r1k: a by-reference
-// call parked 692 B per lane in scratch on EVERY launch, 164 MB of the 240 MB HBM traffic).
+// The SoftPendulum kernel's path for everything but a planar rod in range: the general 3-D substeps
+// for a state that is NOT planar (written through the state view, or reset with an out-of-plane
+// frame), the NaN fill of a rod that has blown up (`poison`), and the launch that only constrains
+// (n_sub = 0).  An out-of-line call that shares NOTHING with its caller but scalars — it reads the
+// parameters and the array pointers from their device-memory copies (StatePtrs.params / .self),
+// loads the rod from its HBM rows, establishes the constraint invariants, steps, and stores the rod
+// and its clock back; the caller reloads.  Nothing of the caller's lane state is address-taken that
+// way and no row address of it has a use behind the planar loop, so the planar path keeps every
+// value in registers and writes no scratch (r1k: a by-reference call parked 692 B per lane in
+// scratch on EVERY launch, 164 MB of the 240 MB HBM traffic; until the planar launch rework the
+// caller's own store_lane for the NaN and n_sub = 0 paths parked the addresses of the twelve rows
+// it alone writes: 24 MB of spill lines per launch, never read back).
 template <unsigned F, int E, int EPL>
 __device__ __attribute__((noinline)) void general_step_cold(const RodParams* __restrict__ params,
                                                             const StatePtrs* __restrict__ sp, int rod, int lane,
-                                                            const float* __restrict__ actions, int n_sub) {
+                                                            const float* __restrict__ actions, int n_sub, int poison) {
     const RodParams P = *params;
     const StatePtrs S = *sp;
     const size_t N = (size_t)P.n_envs;
     LaneN<EPL> L;
-    load_lane<EPL, F>(S, N, rod, lane, L);
-    BcTargets B;
-    load_bc(S, N, rod, B);
-    EnvAction A;
-    set_action_n<F, E, EPL>(P, S, N, rod, lane, actions, A, B, L);
-    constrain_rates_n<F, EPL>(P, B, lane, L);
-    constrain_values_n<F, EPL>(P, B, lane, L);
-    double time = S.time[rod];
-    ConstN<EPL> C;
-    if constexpr (kEnvMaterial<F>) build_const_m<F, EPL>(P, S.env_mat[rod], lane, A, C);   // the env's row
-    else build_const<F, EPL>(P, lane, A, C);
-    if constexpr (kEnvContact<F>) C.ct = S.env_contact[rod];
-    RodParams Pk = P;
-    if (!has<F>(P, SOFTROD_FEAT_ANALYTICAL_DAMPER)) Pk.damp_t = 1.0;
-    general_substeps<F, EPL>(P, Pk, C, B, lane, L, n_sub);
+    double time;
+    if (poison) {
+        poison_rod<EPL>(L);
+        time = S.time[rod];
+    } else {
+        load_lane<EPL, F>(S, N, rod, lane, L);
+        BcTargets B;
+        load_bc(S, N, rod, B);
+        EnvAction A;
+        set_action_n<F, E, EPL>(P, S, N, rod, lane, actions, A, B, L);
+        constrain_rates_n<F, EPL>(P, B, lane, L);
+        constrain_values_n<F, EPL>(P, B, lane, L);
+        time = S.time[rod];
+        if (n_sub > 0) {
+            ConstN<EPL> C;
+            if constexpr (kEnvMaterial<F>) build_const_m<F, EPL>(P, S.env_mat[rod], lane, A, C);   // the env's row
+            else build_const<F, EPL>(P, lane, A, C);
+            if constexpr (kEnvContact<F>) C.ct = S.env_contact[rod];
+            RodParams Pk = P;
+            if (!has<F>(P, SOFTROD_FEAT_ANALYTICAL_DAMPER)) Pk.damp_t = 1.0;
+            general_substeps<F, EPL>(P, Pk, C, B, lane, L, n_sub);
+        }
+    }
     time = clock_after(P, S, time, n_sub);
     store_lane<EPL, F>(S, N, rod, lane, L);
     if (lane == 0) S.time[rod] = time;
@@ -774,8 +786,11 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
 
     __builtin_amdgcn_s_setprio(3);     // ProgressPriority lowers it as the substeps advance
     SR_PHASE(0);
+    // The SoftPendulum instantiation: the planar path overwrites the tangents before it reads them (its
+    // first force evaluation), and the other paths reload the rod behind general_step_cold
+    constexpr bool kPlanarKernel = (F & ~kFeatEnvMaterial) == SOFTROD_FEATURES_SOFTPENDULUM;
     LaneN<EPL> L;
-    load_lane<EPL, F>(S, N, rod, lane, L);
+    load_lane<EPL, F, !kPlanarKernel>(S, N, rod, lane, L);
     SR_PHASE(1);
     if (has<F>(P, SOFTROD_FEAT_LAPLACE_FILTER)) sanitize_unused_rates<EPL>(P, lane, L);
     if (has<F>(P, SOFTROD_FEAT_PLANE_CONTACT_ANISO)) sanitize_unused_slots<EPL>(P, lane, L);
@@ -803,22 +818,24 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
     RodParams Pk = P;
     if (!has<F>(P, SOFTROD_FEAT_ANALYTICAL_DAMPER)) Pk.damp_t = 1.0;
 
-    bool stepped = false, stored = false;
     // A rod whose state already holds a NaN (an env that blew up and was not reset — the
     // reference reports terminated and -50 for it on every further step, soft_pendulum.py:
     // 196-208) would only smear that NaN over all of its nodes while dragging every
     // range-reduction loop to its iteration cap.  It is not integrated: its state becomes NaN
     // throughout (where the reference's would end up after a few substeps), its clock advances.
+    bool blown_up = false;
     if (n_sub > 0 && epilogue && rod_has_nan<EPL>(P, lane, L)) {
-        poison_rod<EPL>(L);
-        time = clock_after(P, S, time, n_sub);
-        stepped = true;
+        blown_up = true;
+        if constexpr (!kPlanarKernel) {
+            poison_rod<EPL>(L);
+            time = clock_after(P, S, time, n_sub);
+        }
     }
-    if constexpr ((F & ~kFeatEnvMaterial) == SOFTROD_FEATURES_SOFTPENDULUM) {
+    if constexpr (kPlanarKernel) {
         // SoftPendulum-v0 lives in the x-y plane: same substep without the identically
         // zero out-of-plane terms (softrod_planar.hpp); any other state takes the 3-D loop
         PlanarN<EPL> Z;
-        if (n_sub > 0 && !stepped && planar_from_lane<EPL>(P, B, lane, L, Z)) {
+        if (n_sub > 0 && !blown_up && planar_from_lane<EPL>(P, B, lane, L, Z)) {
             PlanarC<EPL> K;
             planar_build_const<EPL, kEnvMaterial<F>>(Pk, C, lane, K);
             // The clock takes the reference's additions in the reference's order: 2 n_sub times
@@ -886,7 +903,7 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
             // velocities and tangents; everything else of the 3-D lane state is dead from here on
             // the planar path — said explicitly, so that none of it stays in registers (at 128:
             // in scratch) across the loop for the sake of the other path's merge.
-            planar_store<EPL>(S, N, rod, lane, Z);
+            planar_store<EPL>(S, N, rod, lane, Z, !SOFTROD_PLANAR_EXEC_MASK || lane * EPL <= P.n_elem);
 #pragma unroll
             for (int s = 0; s < EPL; ++s) {
 #pragma unroll
@@ -895,24 +912,23 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
                 for (int c = 0; c < 9; ++c) L.Q[s][c] = 0.0;
             }
             planar_to_lane<EPL>(Z, L);
-            stepped = true;
-            stored = true;
-        }
-    }
-    if (n_sub > 0 && !stepped) {
-        if constexpr ((F & ~kFeatEnvMaterial) == SOFTROD_FEATURES_SOFTPENDULUM) {
-            general_step_cold<F, E, EPL>(S.params, S.self, rod, lane, actions, n_sub);   // HBM -> HBM
+        } else {
+            // Every other case — not planar, blown up, nothing to integrate — goes HBM -> HBM through the
+            // cold call and is read back for the epilogue.  The lane index passes through an opaque
+            // register first: the reload's row addresses are formed here, not shared with the kernel's
+            // first loads and kept (in scratch) across the planar block.
+            general_step_cold<F, E, EPL>(S.params, S.self, rod, lane, actions, n_sub, blown_up);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            load_lane<EPL, F>(S, N, rod, lane, L);
+            load_lane<EPL, F>(S, N, rod, opaque_lane(lane), L);
             time = S.time[rod];
-            stored = true;
-        } else
-        {
+        }
+    } else {
+        if (n_sub > 0 && !blown_up) {
             general_substeps<F, EPL, TAPER>(P, Pk, C, B, lane, L, n_sub);
             time = clock_after(P, S, time, n_sub);
         }
+        store_lane<EPL, F>(S, N, rod, lane, L);
     }
-    if (!stored) store_lane<EPL, F>(S, N, rod, lane, L);
     if (has<F>(P, SOFTROD_FEAT_SPLINE_MUSCLE_TORQUES)) muscle_store<EPL>(P, S, rod, lane, L);
     if (env_of<E>(P) == SOFTROD_ENV_SOFT_ARM && lane == 0)   // self.tick += 1 per substep, soft_arm_tracking.py:222
         S.ctrl[(size_t)0 * N + rod] += (double)n_sub;

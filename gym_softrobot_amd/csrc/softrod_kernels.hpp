@@ -319,7 +319,12 @@ __device__ __forceinline__ void shift_prev(const double (&a)[EPL], double (&o)[E
     for (int s = 1; s < EPL; ++s) o[s] = a[s - 1];
 }
 
-template <int EPL, unsigned F>
+// A lane index the compiler cannot trace back: row addresses formed from it are formed THERE, not shared with
+// an earlier load's and kept live (at 128 registers: in scratch) in between.
+__device__ __forceinline__ int opaque_lane(int lane) { asm volatile("" : "+v"(lane)); return lane; }
+
+// TAN = false: without the tangent rows (zeros instead), for a caller that overwrites them before it reads them
+template <int EPL, unsigned F, bool TAN = true>
 __device__ __forceinline__ void load_lane(const StatePtrs& S, size_t N, int rod, int lane, LaneN<EPL>& L) {
     constexpr size_t W = (size_t)kLanes * EPL;
     const size_t base = (size_t)rod * W + (size_t)lane * EPL;
@@ -330,7 +335,7 @@ __device__ __forceinline__ void load_lane(const StatePtrs& S, size_t N, int rod,
             L.x[s][c] = S.pos[c * N * W + base + s];
             L.v[s][c] = S.vel[c * N * W + base + s];
             L.w[s][c] = S.omg[c * N * W + base + s];
-            L.t[s][c] = S.tan[c * N * W + base + s];
+            L.t[s][c] = TAN ? S.tan[c * N * W + base + s] : 0.0;
             if (F == kRuntimeFeatures || (F & (SOFTROD_FEAT_REST_KAPPA_ACTION | SOFTROD_FEAT_SPLINE_MUSCLE_TORQUES))) {
                 L.kap[s][c] = S.kap[c * N * W + base + s];
                 L.rk[s][c] = S.rkap[c * N * W + base + s];

@@ -178,7 +178,9 @@ __device__ __forceinline__ bool planar_from_lane(const RodParams& P, const BcTar
         Z.v[s][0] = L.v[s][0]; Z.v[s][1] = L.v[s][1];
         Z.c[s] = c; Z.s[s] = sn;
         Z.wz[s] = (idx < n) ? Z.s2 * L.w[s][1] : 0.0;
-        Z.t[s][0] = L.t[s][0]; Z.t[s][1] = L.t[s][1];
+        // the first force evaluation writes the tangents before anything reads them, so the kernel does not load
+        // those rows; a lane that sits the loop out keeps this zero and planar_store leaves its row entries alone
+        Z.t[s][0] = 0.0; Z.t[s][1] = 0.0;
     }
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
@@ -224,24 +226,42 @@ __device__ __forceinline__ void planar_to_lane(const PlanarN<EPL>& Z, LaneN<EPL>
 // What a planar step changes, written to the resident rows: x, y, v_x, v_y, d1 = (-s2 s, s2 c), d3 = (c, s),
 // omega_2 and the tangents — 12 of the rod's 21 rows.  The other nine (z components, d2, the
 // out-of-plane directors and rates) hold the exact values planar_from_lane has just checked.
+// Plain stores: measured against __builtin_nontemporal_store and a relaxed agent-scope __hip_atomic_store
+// (global_store_dwordx2 ... sc1) with tools/step_ab.py, seven alternating passes each at 4096 envs — all three inside
+// one another's spread (profiles/planar_launch_ab.json), so the plain store stays.
+// `stepped`: this lane took part in the loop.  A lane that sat it out (past the rod's end node, EXEC cleared) holds in
+// x, v and d3 the very values it loaded, so those rows are not written there; its tangents were never loaded (the
+// kernel skips those rows) and stay what memory holds.  (This rests on the kernel's prologue — set_action_n,
+// constrain_rates_n, constrain_values_n — touching only node 0 / element 0 in this feature set: a constraint that
+// wrote a lane past the end node would have to be stored here, as the whole-row store before this one did.)  d1, omega_2 and the tangents' z are written in every lane:
+// they are REBUILT (d1 from d3, one rounding away from a frame a reset wrote; s2 * 0 with s2's sign; 0), so a
+// padding lane's bytes may move the first time — as they always did.
 template <int EPL>
-__device__ __forceinline__ void planar_store(const StatePtrs& S, size_t N, int rod, int lane, const PlanarN<EPL>& Z) {
+__device__ __forceinline__ void planar_store(const StatePtrs& S, size_t N, int rod, int lane, const PlanarN<EPL>& Z,
+                                             bool stepped) {
     constexpr size_t W = (size_t)kLanes * EPL;
-    const size_t base = (size_t)rod * W + (size_t)lane * EPL;
+    // the row addresses are formed here, behind the loop (opaque_lane): shared with the kernel's first loads they
+    // stayed live across it, 26 registers' worth, and the allocator parked what did not fit in scratch
+    const size_t base = (size_t)rod * W + (size_t)opaque_lane(lane) * EPL;
 #pragma unroll
     for (int s = 0; s < EPL; ++s) {
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            S.pos[c * N * W + base + s] = Z.x[s][c];
-            S.vel[c * N * W + base + s] = Z.v[s][c];
-            S.tan[c * N * W + base + s] = Z.t[s][c];
-        }
         S.tan[2 * N * W + base + s] = 0.0;
         S.dir[0 * N * W + base + s] = -Z.s2 * Z.s[s];
         S.dir[1 * N * W + base + s] = Z.s2 * Z.c[s];
-        S.dir[6 * N * W + base + s] = Z.c[s];
-        S.dir[7 * N * W + base + s] = Z.s[s];
         S.omg[1 * N * W + base + s] = Z.s2 * Z.wz[s];
+    }
+    if (stepped) {
+#pragma unroll
+        for (int s = 0; s < EPL; ++s) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                S.pos[c * N * W + base + s] = Z.x[s][c];
+                S.vel[c * N * W + base + s] = Z.v[s][c];
+                S.tan[c * N * W + base + s] = Z.t[s][c];
+            }
+            S.dir[6 * N * W + base + s] = Z.c[s];
+            S.dir[7 * N * W + base + s] = Z.s[s];
+        }
     }
 }
 
