@@ -2,8 +2,10 @@
 reference's only training example (examples/soft_pendulum_3d/train_ppo.py, Stable-Baselines3
 on ONE env).  Here `num_envs` pendulums step in one kernel launch, observations, rewards and
 flags stay on the device (zero-copy views of the stepper's buffers), finished episodes restart
-on the device (`autoreset="device"`, Gymnasium NEXT_STEP semantics), and a small torch policy
-acts on the same GPU: no host round trip inside the rollout.
+on the device within the call that ends them (`autoreset="same_step"`, Gymnasium SAME_STEP
+semantics: every call of every env is a sample, and a truncated episode bootstraps from its
+terminal observation, `info["final_obs"]`), and a small torch policy acts on the same GPU: no
+host round trip inside the rollout.
 
     python examples/soft_pendulum_3d_ppo.py --num-envs 1024 --updates 30
 
@@ -50,7 +52,7 @@ def main():
 
     torch.manual_seed(args.seed)
     dev = torch.device("cuda", 0)
-    env = gsa.make_vec("SoftPendulum3D-v0", args.num_envs, device=0, autoreset="device")
+    env = gsa.make_vec("SoftPendulum3D-v0", args.num_envs, device=0, autoreset="same_step")
     N, T = args.num_envs, args.horizon
     od, ad = env.obs_dim, env.action_dim
     lo, hi = env.action_low, env.action_high
@@ -62,6 +64,7 @@ def main():
     logp_buf = torch.empty((T, N), device=dev)
     rew_buf = torch.empty((T, N), device=dev)
     done_buf = torch.empty((T, N), device=dev)
+    boot_buf = torch.empty((T, N), device=dev)        # what a finished step bootstraps from
     val_buf = torch.empty((T + 1, N), device=dev)
 
     obs, _ = env.reset(seed=args.seed)
@@ -74,16 +77,20 @@ def main():
                 a = d.sample()
                 obs_buf[t], act_buf[t], logp_buf[t] = obs, a, d.log_prob(a).sum(-1)
                 val_buf[t] = net.v(obs).squeeze(-1)
-                nobs, rew, term, trunc, _ = env.step(a.clamp(lo, hi))
+                nobs, rew, term, trunc, info = env.step(a.clamp(lo, hi))
                 rew_buf[t] = rew.float()
                 done_buf[t] = (term | trunc).float()
+                # `nobs` of a finished env is already its next episode's first observation; the finished step's value
+                # target is V(terminal observation) after a truncation and 0 after a termination
+                boot_buf[t] = torch.where(trunc & ~term, net.v(info["final_obs"]).squeeze(-1), torch.zeros_like(rew_buf[t]))
                 obs = nobs.clone()                    # the env's buffers are overwritten by the next step
             val_buf[T] = net.v(obs).squeeze(-1)
             adv = torch.zeros((T, N), device=dev)
             last = torch.zeros(N, device=dev)
-            for t in reversed(range(T)):              # GAE; an env that finished restarts on its next step
+            for t in reversed(range(T)):              # GAE; val_buf[t + 1] of a finished env belongs to its next episode
                 nonterminal = 1.0 - done_buf[t]
-                delta = rew_buf[t] + args.gamma * val_buf[t + 1] * nonterminal - val_buf[t]
+                next_value = val_buf[t + 1] * nonterminal + boot_buf[t] * done_buf[t]
+                delta = rew_buf[t] + args.gamma * next_value - val_buf[t]
                 last = delta + args.gamma * args.lam * nonterminal * last
                 adv[t] = last
             ret = adv + val_buf[:T]

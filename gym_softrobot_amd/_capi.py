@@ -918,6 +918,8 @@ _EXPORTS = {
     "softrod_config_obs_dim": (C.c_int, [C.POINTER(SoftrodConfig)]),
     "softrod_reset_octo": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "softrod_autoreset_enable": (C.c_int, [_VP, C.c_int]),
+    "softrod_autoreset_same_step": (C.c_int, [_VP, C.c_int]),
+    "softrod_final_view": (C.c_int, [_VP, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "softrod_queue_push": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP]),
     "softrod_queue_push_straight": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, _VP]),
     "softrod_queue_push_octo": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, _VP]),

@@ -240,6 +240,22 @@ class HipRodBackend:
         check(self._lib.softrod_autoreset_enable(self._h, int(depth)), self._h)
         self.queue_depth = int(depth)
 
+    def autoreset_same_step(self, on: bool = True) -> None:
+        """softrod_autoreset_same_step: Gymnasium's SAME_STEP semantics on the staged queue (after autoreset_enable).
+        A step that ends an env's episode keeps its reward and flags, leaves the NEW episode's first observation in
+        `obs` and the finished one in `final_obs` / `final_time` / `final_aux`: zero-copy device views, valid for the
+        backend's life, of which a call rewrites the rows of the envs it finished (terminated | truncated) and no
+        others.  `on=False` returns to NEXT_STEP.  A captured graph must be captured again after a switch."""
+        check(self._lib.softrod_autoreset_same_step(self._h, int(bool(on))), self._h)
+        self.same_step = bool(on)
+        if on and getattr(self, "final_obs", None) is None:
+            fo, ft, fa = C.c_void_p(), C.c_void_p(), C.c_void_p()
+            check(self._lib.softrod_final_view(self._h, C.byref(fo), C.byref(ft), C.byref(fa)), self._h)
+            n = self.n_envs
+            self.final_obs = torch.as_tensor(_DevArray(fo.value, (n, self.obs_dim), "<f4", self), device=self.device)
+            self.final_time = torch.as_tensor(_DevArray(ft.value, (n,), "<f8", self), device=self.device)
+            self.final_aux = torch.as_tensor(_DevArray(fa.value, (n,), "<f8", self), device=self.device)
+
     @staticmethod
     def _counts(counts, n):
         return np.ascontiguousarray(counts, dtype=np.int32).reshape(n)

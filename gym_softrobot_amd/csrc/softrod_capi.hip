@@ -87,6 +87,11 @@ struct softrod_handle {
     hipEvent_t ev_status = nullptr;
     bool status_pending = false;
     hipEvent_t ev_queue = nullptr;  // guards reuse of h_queue / h_produced
+    // same-step auto-reset (softrod_autoreset_same_step): owned, allocated by the first call that switches it on
+    bool same_step = false;
+    float* d_final_obs = nullptr;   // [N][obs_dim] the finished step's observation
+    double* d_final_time = nullptr; // [N] the finished episode's clock
+    double* d_final_aux = nullptr;  // [N] the finished step's aux value (SoftPendulum3D's tilt)
     EnvTable<EnvMaterial> env_mat;      // softrod_set_env_material
     EnvTable<EnvContact> env_contact;   // softrod_set_env_contact
     // softrod_copy_envs: the (src, dst) pairs of a call on their way to the device, sized for n_envs pairs at create
@@ -328,6 +333,20 @@ int launch_autoreset(softrod_handle* h, float* obs, double* reward, uint8_t* ter
     else
         hipLaunchKernelGGL(by_epl(h, softrod_autoreset_kernel<1>, softrod_autoreset_kernel<2>), grid, block, 0, st, h->P, h->S,
                            obs, reward, term, trunc, aux, pack);
+    SR_HIP(h, hipGetLastError());
+    return SOFTROD_OK;
+}
+
+// SAME_STEP auto-reset pass behind a step (softrod_autoreset.hpp): envs the step just finished hand out their final
+// observation and restart within the call
+int launch_autoreset_same_step(softrod_handle* h, float* obs, double* aux, int pack, hipStream_t st) {
+    const dim3 grid((unsigned)h->cfg.n_envs), block(kLanes * h->nw);
+    if (is_octo(h))
+        hipLaunchKernelGGL(softrod_octo_autoreset_same_step_kernel, grid, block, 0, st, h->P, h->S, obs, pack, h->d_final_obs,
+                           h->d_final_time);
+    else
+        hipLaunchKernelGGL(by_epl(h, softrod_autoreset_same_step_kernel<1>, softrod_autoreset_same_step_kernel<2>), grid, block,
+                           0, st, h->P, h->S, obs, aux, pack, h->d_final_obs, h->d_final_time, h->d_final_aux);
     SR_HIP(h, hipGetLastError());
     return SOFTROD_OK;
 }
@@ -582,7 +601,7 @@ int set_env_table(softrod_handle* h, EnvTable<Row>& T, const Row*& slot, unsigne
 int launch_step(softrod_handle* h, const float* actions, float* obs, double* reward,
                 uint8_t* term, uint8_t* trunc, double* aux, int n_sub, int epilogue, int pack,
                 hipStream_t st) {
-    if (h->q_depth > 0 && epilogue)
+    if (h->q_depth > 0 && epilogue && !h->same_step)
         if (const int rc = launch_autoreset(h, obs, reward, term, trunc, aux, pack, st)) return rc;
     if ((h->cfg.features & SOFTROD_FEAT_COOMM_MUSCLES) && h->cfg.math_mode == SOFTROD_MATH_FAST) {
         // what the muscle handles need set before they step
@@ -623,6 +642,9 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
         SR_HIP(h, hipEventRecord(h->ev_stop[h->timed], st));
         ++h->timed;
     }
+    // behind the timing record, so that kernel_times_ms keeps meaning the step (as for the NEXT_STEP pass in front)
+    if (h->q_depth > 0 && epilogue && h->same_step)
+        if (const int rc = launch_autoreset_same_step(h, obs, aux, pack, st)) return rc;
     return SOFTROD_OK;
 }
 
@@ -1390,6 +1412,34 @@ int softrod_autoreset_enable(softrod_handle* h, int depth) {
         h->err = why;
     }
     return rc;
+}
+
+int softrod_autoreset_same_step(softrod_handle* h, int on) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "null argument");
+    if (!h->q_depth) return fail(h, SOFTROD_EINVAL, "call softrod_autoreset_enable first");
+    SR_ON_DEVICE(h);
+    if (on && !h->d_final_obs) {
+        // owned buffers, zero-filled: released with the handle, kept through on = 0 so that the pointers
+        // softrod_final_view hands out stay good for the handle's life
+        const size_t N = (size_t)h->cfg.n_envs;
+        float* fo = nullptr;
+        double *ft = nullptr, *fa = nullptr;
+        SR_HIP(h, alloc_owned(h, fo, N * (size_t)softrod_config_obs_dim(&h->cfg) * sizeof(float)));
+        SR_HIP(h, alloc_owned(h, ft, N * sizeof(double)));
+        SR_HIP(h, alloc_owned(h, fa, N * sizeof(double)));
+        h->d_final_obs = fo; h->d_final_time = ft; h->d_final_aux = fa;
+    }
+    h->same_step = on != 0;
+    return SOFTROD_OK;
+}
+
+int softrod_final_view(softrod_handle* h, float** final_obs, double** final_time, double** final_aux) {
+    if (!h || !final_obs || !final_time || !final_aux) return fail(h, SOFTROD_EINVAL, "null argument");
+    if (!h->same_step) return fail(h, SOFTROD_EINVAL, "call softrod_autoreset_same_step first");
+    *final_obs = h->d_final_obs;
+    *final_time = h->d_final_time;
+    *final_aux = h->d_final_aux;
+    return SOFTROD_OK;
 }
 
 namespace {

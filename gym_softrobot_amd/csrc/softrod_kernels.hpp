@@ -2173,3 +2173,4 @@ softrod_autoreset_kernel(const RodParams P, const StatePtrs S, float* __restrict
 #include "softrod_strains.hpp"
 #include "softrod_muscle_readout.hpp"
 #include "softrod_joint_readout.hpp"
+#include "softrod_autoreset.hpp"

@@ -158,6 +158,10 @@ class ShardedVecEnv:
     def __init__(self, local_env, total_envs: int, group: Optional[dist.ProcessGroup] = None,
                  gather: bool = True, overlap: bool = False, force_collective: bool = False,
                  overlap_depth: Optional[int] = None, transport: str = "rccl"):
+        if getattr(local_env, "same_step", False):
+            raise NotImplementedError("ShardedVecEnv over autoreset='same_step': the packed row the ranks exchange has "
+                                      "no room for a second observation and final_obs is not gathered; "
+                                      "use autoreset='device'")
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0

@@ -15,6 +15,14 @@ SURVEY.md §8(f) N2:
                        (softrod_queue_push*); the step applies them itself.  The host tops
                        the queue up within every `queue_depth` steps (one small non-blocking read).  `infos`
                        then carry device tensors.
+  * `autoreset="same_step"`  Gymnasium-1.x AutoresetMode.SAME_STEP on the same staged queue: the call
+                       that ends an env's episode returns that step's reward and flags, the NEW episode's
+                       first observation in `obs`, and the terminal observation in infos["final_obs"]
+                       (rows where infos["_final_obs"] = terminated | truncated), its clock in
+                       infos["final_info"]["time"].  No env ever spends a call resetting, and value
+                       targets of truncated episodes can bootstrap from the terminal observation.  One
+                       cold kernel behind the step (csrc/softrod_autoreset.hpp); an env can use a
+                       record per step, so the queue is topped up twice as often (`top_up_every`).
 """
 from __future__ import annotations
 
@@ -307,9 +315,10 @@ class VecRodEnvBase:
         self.num_envs = int(num_envs)
         self.cfg = cfg
         self.numpy_output = numpy_output
-        if autoreset not in (False, True, "host", "device"):
-            raise ValueError("autoreset must be False, True/'host' or 'device'")
-        self.device_autoreset = autoreset == "device"
+        if autoreset not in (False, True, "host", "device", "same_step"):
+            raise ValueError("autoreset must be False, True/'host', 'device' or 'same_step'")
+        self.same_step = autoreset == "same_step"        # the device mode with SAME_STEP semantics
+        self.device_autoreset = autoreset == "device" or self.same_step
         self.autoreset = bool(autoreset) and not self.device_autoreset
         self._queue_depth = self._ring_depth = 32      # (queue_depth / top_up_every properties)
         self.action_dim = _capi.config_action_dim(cfg)
@@ -335,8 +344,12 @@ class VecRodEnvBase:
         self._since_top_up = 0
         self._status_in_flight = False
         self.top_up_paused = False     # True: the caller reads the queue counters and stages records itself (tests)
+        if self.same_step and not hasattr(self.backend, "autoreset_same_step"):
+            raise NotImplementedError(f"same-step auto-reset needs the HIP backend, not {type(self.backend).__name__}")
         if self.device_autoreset:
             self.backend.autoreset_enable(self.queue_depth)
+        if self.same_step:
+            self.backend.autoreset_same_step(True)
         # soft_pendulum.py:117-126: RodCallBack -> rod_parameters_dict, one sample per env.step.
         # Video/plot generation from it stays out of scope; the data tap is here (env 0, or
         # `record_envs` set before reset).
@@ -378,7 +391,14 @@ class VecRodEnvBase:
         queue_depth so that the two cannot drift apart: an env uses at most one record per two
         steps, so between a reading of the counters and the end of the NEXT top-up (fewer than
         2 * top_up_every steps) it uses at most top_up_every records — fewer than the
-        queue_depth - 1 that are certainly staged at the reading."""
+        queue_depth - 1 that are certainly staged at the reading.
+
+        autoreset="same_step": the step that ends an episode also restarts it, so an env can use one record
+        PER step (episodes of one step).  Between a reading and the end of the next top-up lie fewer than
+        2 * top_up_every steps, hence fewer than 2 * top_up_every records: the deadline is halved,
+        (queue_depth - 2) // 2, which keeps that number within queue_depth - 2."""
+        if self.same_step:
+            return max(1, (self._queue_depth - 2) // 2)
         every = max(1, self._queue_depth - 2)
         assert every <= self._queue_depth - 1
         return every
@@ -573,8 +593,29 @@ class VecRodEnvBase:
         # cut-off as well, and the epilogue writes the time-limit flag on its own (backend.time_limit)
         tl = self.backend.time_limit() if getattr(self.cfg, "early_termination", 0) else trunc.view(torch.bool)
         infos = {"time": self._out(self._dev_time), "TimeLimit.truncated": self._out(tl)}
+        if self.same_step:
+            infos.update(self._final_infos(term, trunc))
         return (self._out(obs), self._out(reward), self._out(term.view(torch.bool)),
                 self._out(trunc.view(torch.bool)), infos)
+
+    aux_info_key: Optional[str] = None     # what the backend's aux column is called in `infos` (SoftPendulum3D: "tilt")
+
+    def _final_infos(self, term, trunc) -> Dict[str, Any]:
+        """autoreset="same_step": Gymnasium's SAME_STEP keys.  `final_obs` (N, obs_dim) and `final_info` hold the
+        finished step's observation, clock and aux value in the rows where `_final_obs` = terminated | truncated is
+        set; the other rows are unspecified (an earlier episode end of that env).  `obs`, infos["time"] (0 for a
+        restarted env) and the aux key describe the new episode.  The flags, the reward and
+        infos["TimeLimit.truncated"] are the finished step's: the reset leaves the time-limit row of env_aux alone."""
+        import torch
+
+        be = self.backend
+        final_info = {"time": self._out(be.final_time)}
+        out = {"final_obs": self._out(be.final_obs), "_final_obs": self._out((term | trunc).view(torch.bool)),
+               "final_info": final_info}
+        if self.aux_info_key is not None:
+            out[self.aux_info_key] = self._out(be.aux[:, 0])
+            final_info[self.aux_info_key] = self._out(be.final_aux)
+        return out
 
     def step(self, actions):
         import torch
@@ -872,9 +913,11 @@ class VecRodEnvBase:
         policy: obs (N, obs_dim) float32 device tensor -> actions (N, action_dim) float32, pure device work.
         Returns replay() -> (obs, reward, terminated, truncated): the backend's resident output tensors, overwritten
         by every replay (as `step` does).  The observation the policy reads is the one the previous step wrote —
-        call `reset` BEFORE capturing.  Needs autoreset off or "device" (the host-driven NEXT_STEP mode reads flags
-        back every step and cannot live in a graph); the queue top-ups of the device mode stay outside the graph
-        and run between replays.  Results are bit-identical to the eager loop (tests/test_gpu_policy_loop.py).
+        call `reset` BEFORE capturing.  Needs autoreset off, "device" or "same_step" (the host-driven NEXT_STEP mode
+        reads flags back every step and cannot live in a graph); the queue top-ups of the device modes stay outside
+        the graph and run between replays.  In same-step mode the pass behind the step is one more kernel of the
+        same straight line, and the finished observations are in backend.final_obs / final_time.  Results are
+        bit-identical to the eager loop (tests/test_gpu_policy_loop.py, tests/test_gpu_same_step.py).
         The kernel arguments (RodParams, array pointers) are baked into the graph BY VALUE at capture: after
         anything that changes them (a radius profile, an action basis, enabling auto-reset, enabling per-env material or contact)
         capture again.  Once per-env material is on, later set_material calls update its table in place: replays
@@ -883,7 +926,7 @@ class VecRodEnvBase:
         import torch
 
         if self.autoreset:
-            raise NotImplementedError("capture_policy_step needs autoreset=False or autoreset='device'")
+            raise NotImplementedError("capture_policy_step needs autoreset=False, 'device' or 'same_step'")
         if self.recorder is not None:
             raise NotImplementedError("capture_policy_step with a diagnostics recorder: the per-step host tap "
                                       "cannot live in a graph (config_generate_video=False)")
@@ -926,7 +969,9 @@ class VecRodEnvBase:
         packed = self.backend.step_packed(a) if out is None else self.backend.step_packed(a, out)
         if self.device_autoreset:
             self._top_up_tick()
-            return packed, {}
+            # same-step mode: the packed row has no room for a second observation; the finished one is the dense
+            # resident buffer, valid in the rows whose packed flags are set
+            return packed, ({"final_obs": self._out(self.backend.final_obs)} if self.same_step else {})
         self._steps += 1
         return packed, self._infos(self._times())
 
@@ -950,7 +995,8 @@ class VecRodEnvBase:
         Not offered on the sharded env (distributed.py: src and dst may live on different GPUs) nor on the N = 1
         single-env classes (SingleRodEnv: there is nothing to fork into)."""
         if self.device_autoreset:
-            raise NotImplementedError("fork() with autoreset='device': staged reset records are not copied")
+            raise NotImplementedError(f"fork() with autoreset='{'same_step' if self.same_step else 'device'}': "
+                                      "staged reset records are not copied")
         be = self.backend
         if not hasattr(be, "copy_envs"):
             raise NotImplementedError(f"fork needs the HIP backend, not {type(be).__name__}")
@@ -981,7 +1027,8 @@ class VecRodEnvBase:
         an addition.  Not available with autoreset="device" (reset records staged on the device
         belong to the RNG streams' future)."""
         if self.device_autoreset:
-            raise NotImplementedError("state_dict() with autoreset='device': staged reset records are not captured")
+            raise NotImplementedError(f"state_dict() with autoreset='{'same_step' if self.same_step else 'device'}': "
+                                      "staged reset records are not captured")
         extra = {k: np.array(getattr(self, k)) for k in ("targets", "_traj") if getattr(self, k, None) is not None}
         return {
             "backend": self.backend.snapshot(),

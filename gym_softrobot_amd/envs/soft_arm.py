@@ -59,7 +59,7 @@ class VecSoftArmTrackingEnv(VecRodEnvBase):
                  numpy_output: bool = False, autoreset: bool = False, backend=None):
         if game_mode not in (1, 2):
             raise ValueError("game_mode is 1 (fixed target) or 2 (moving target), soft_arm_tracking.py:386-412")
-        if game_mode == 2 and autoreset == "device":
+        if game_mode == 2 and autoreset in ("device", "same_step"):
             raise NotImplementedError("game_mode 2 draws a trajectory per episode on the host: use autoreset=True")
         cfg = _capi.soft_arm_config(num_envs, n_elems=n_elems, math_mode=math_mode)
         super().__init__(num_envs, cfg, render_mode=render_mode, config_generate_video=False, device=device,

@@ -90,6 +90,8 @@ class VecSoftPendulum3DEnv(VecRodEnvBase):
                 # soft_pendulum_3d.py:116-117 (device tensors are the caller's responsibility)
                 raise ValueError(f"Action {actions!r} is outside {self.single_action_space}")
 
+    aux_info_key = "tilt"
+
     def _infos(self, times):
         return {"time": times, "tilt": self._out(self.backend.aux[:, 0])}
 

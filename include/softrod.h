@@ -581,8 +581,33 @@ int softrod_step_packed(softrod_handle* h, const float* actions, float* packed,
  *   softrod_queue_advance      mark by[e] staged records of env e as used (a manual reset
  *                              took the env's next draw), or all of them if by[e] < 0
  *                              (the env's stream was re-seeded); synchronises
- * softrod_reset* of an env clears its pending auto-reset.                            */
+ * softrod_reset* of an env clears its pending auto-reset.
+ *
+ * SAME_STEP semantics (Gymnasium 1.x AutoresetMode.SAME_STEP), on the same queue:
+ *   softrod_autoreset_same_step(h, on)   after softrod_autoreset_enable (else SOFTROD_EINVAL, "call
+ *                              softrod_autoreset_enable first").  on != 0: the pass in front of the step is no
+ *                              longer launched; one cold pass runs BEHIND everything softrod_step /
+ *                              softrod_step_packed enqueue (csrc/softrod_autoreset.hpp; behind the timing
+ *                              record too, so softrod_kernel_times_ms keeps meaning the step).  An env whose step
+ *                              ended its episode keeps that step's reward and flags, hands out its terminal
+ *                              observation, clock and aux value through the final buffers, consumes its next staged
+ *                              record and has the NEW episode's first observation in its obs row (and, for
+ *                              SOFTROD_ENV_SOFTPENDULUM3D, that observation's value in `aux`) when the call
+ *                              returns; the next call steps the new episode with its own action, so no env ever
+ *                              spends a call resetting.  An env may now use one record per step.  An env that
+ *                              finds no staged record stays finished exactly as above (its obs row keeps the
+ *                              final observation).  Envs that did not finish are not touched.  on = 0 returns to
+ *                              NEXT_STEP.  Switch while no env is finished (right after enabling, or after a reset).
+ *                              The first on != 0 allocates the final buffers (released by softrod_destroy);
+ *                              a captured graph must be captured again after a switch.
+ *   softrod_final_view         device pointers, valid for the handle's life: final_obs float [n_envs][obs_dim]
+ *                              (dense also under softrod_step_packed), final_time double [n_envs], final_aux
+ *                              double [n_envs].  Row e holds the last episode end of env e; which rows the last
+ *                              call wrote is that call's terminated | truncated.  SOFTROD_EINVAL while same-step
+ *                              is off.                                                  */
 int softrod_autoreset_enable(softrod_handle* h, int depth);
+int softrod_autoreset_same_step(softrod_handle* h, int on);
+int softrod_final_view(softrod_handle* h, float** final_obs, double** final_time, double** final_aux);
 int softrod_queue_push(softrod_handle* h, const double* theta0, const int32_t* counts,
                        int max_count, void* stream);
 int softrod_queue_push_straight(softrod_handle* h, const double* start,
