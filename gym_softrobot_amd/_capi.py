@@ -199,6 +199,66 @@ class SoftrodStateView(C.Structure):
     ]
 
 
+class SoftrodCamera(C.Structure):
+    """Mirror of `struct softrod_camera` (include/softrod.h, softrod_render): the orthographic camera all envs of a
+    handle share."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("follow", C.c_int32),
+        ("center", C.c_double * 3),
+        ("right", C.c_double * 3),
+        ("up", C.c_double * 3),
+        ("half_width", C.c_double),
+        ("target_radius", C.c_double),
+        ("light", C.c_double * 3),
+        ("ambient", C.c_double),
+    ]
+
+    def copy(self) -> "SoftrodCamera":
+        out = SoftrodCamera()
+        C.memmove(C.byref(out), C.byref(self), C.sizeof(SoftrodCamera))
+        return out
+
+
+# softrod_render's colours (SOFTROD_RENDER_PALETTE / SOFTROD_RENDER_BACKGROUND of include/softrod.h) as (r, g, b) of
+# 0 .. 255: the arm index modulo 8 (entries 0-7), the rigid body, the target
+RENDER_PALETTE = ((0x1F, 0x77, 0xB4), (0xFF, 0x7F, 0x0E), (0x2C, 0xA0, 0x2C), (0xD6, 0x27, 0x28), (0x94, 0x67, 0xBD),
+                  (0x8C, 0x56, 0x4B), (0xE3, 0x77, 0xC2), (0x17, 0xBE, 0xCF), (0x7F, 0x7F, 0x7F), (0xBC, 0xBD, 0x22))
+RENDER_BACKGROUND = (0xF5, 0xF5, 0xF5)
+RENDER_BODY_HEAD, RENDER_BODY_TARGET = 8, 9
+
+
+def camera_default(cfg: "SoftrodConfig") -> SoftrodCamera:
+    """Host-side equivalent of `softrod_camera_default`: a view that frames a freshly reset env of `cfg`, 84 x 84."""
+    cam = SoftrodCamera()
+    cam.struct_size = C.sizeof(SoftrodCamera)
+    cam.width = cam.height = 84
+    L = float(cfg.base_length)
+    kind = int(cfg.env_kind)
+    if kind in (ENV_SOFTPENDULUM3D, ENV_SOFT_ARM):
+        # a fixed oblique view from (+x, -y, +z); the reset rod stands on the origin along z (SoftPendulum3D) or y
+        cam.right[0], cam.right[1], cam.right[2] = 0.8, 0.6, 0.0
+        cam.up[0], cam.up[1], cam.up[2] = -0.36, 0.48, 0.8
+        cam.center[1 if kind == ENV_SOFT_ARM else 2] = 0.5 * L
+        cam.half_width = 0.75 * L
+    else:
+        # the pendulum's plane seen along -z, the ground plane seen from above: x right, y up
+        cam.right[0] = 1.0
+        cam.up[1] = 1.0
+        if int(cfg.features) & FEAT_OCTO_HEAD:
+            cam.follow = 1
+            cam.half_width = 1.1 * (float(cfg.head_radius) + L)
+        else:
+            cam.half_width = 1.1 * L
+    cam.target_radius = 0.05 * L
+    cam.light[0], cam.light[1], cam.light[2] = -0.48, 0.6, 0.64
+    cam.ambient = 0.35
+    return cam
+
+
 def _common(cfg: SoftrodConfig, n_envs, final_time, time_step, recording_fps, n_elems, math_mode):
     cfg.struct_size = C.sizeof(SoftrodConfig)
     cfg.n_envs = int(n_envs)
@@ -949,6 +1009,9 @@ _EXPORTS = {
     "softrod_set_env_material": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_set_env_contact": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_copy_envs": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP]),
+    "softrod_camera_default": (C.c_int, [C.POINTER(SoftrodConfig), C.POINTER(SoftrodCamera)]),
+    "softrod_camera_check": (C.c_int, [C.POINTER(SoftrodCamera)]),
+    "softrod_render": (C.c_int, [_VP, C.POINTER(SoftrodCamera), _VP, _VP, _VP]),
     "softrod_substeps": (C.c_int, [_VP, _VP, C.c_int, _VP]),
     "softrod_state_view_get": (C.c_int, [_VP, C.POINTER(SoftrodStateView)]),
     "softrod_set_timing": (C.c_int, [_VP, C.c_int]),

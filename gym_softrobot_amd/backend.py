@@ -77,6 +77,7 @@ class HipRodBackend:
         # radius profile): their bytes go into config_fingerprint()
         self._tables: Dict[str, bytes] = {}
         self._readouts: Dict[str, torch.Tensor] = {}     # rod_energies / ground_reaction / rod_strains / muscle_loads / joint_loads / rod_dynamics buffers (_readout)
+        self._frames: Dict[tuple, torch.Tensor] = {}      # render(): the RGB and depth frames per (H, W)
         check(self._lib.softrod_create(C.byref(self.cfg), self.device_index, C.byref(self._h)))
         if self.cfg.features & _capi.FEAT_REST_KAPPA_ACTION:
             if self.is_octo:
@@ -401,6 +402,28 @@ class HipRodBackend:
         (n_envs, rods_per_env, 18, n_elem + 1) buffer allocated on first use and overwritten by the next call."""
         rods = _capi.config_rods_per_env(self.cfg)
         return rod_dynamics_views(self._readout("rod_dynamics", rods, 18, int(self.cfg.n_elem) + 1))
+
+    def render(self, camera: "_capi.SoftrodCamera", depth: bool = False):
+        """softrod_render: one (n_envs, H, W, 3) uint8 device tensor of RGB frames of every env through `camera`
+        (an orthographic _capi.SoftrodCamera shared by the batch; _capi.camera_default(cfg) frames a fresh env), or
+        (rgb, depth) with depth (n_envs, H, W) float32 — the surface's camera-frame depth, -inf where nothing is
+        drawn — when `depth` is true.  The image model is include/softrod.h's.  One kernel on the current stream, no
+        upload, capturable once the buffers exist: they are allocated on first use per (H, W) and overwritten by
+        the next call, like the read-outs'."""
+        h, w = int(camera.height), int(camera.width)
+        key = (h, w)
+        rgb = self._frames.get(key)
+        if rgb is None:
+            check(self._lib.softrod_camera_check(C.byref(camera)))      # before sizes from it are trusted
+            rgb = self._frames[key] = torch.empty((self.n_envs, h, w, 3), dtype=torch.uint8, device=self.device)
+        z = None
+        if depth:
+            z = self._frames.get(key + ("depth",))
+            if z is None:
+                z = self._frames[key + ("depth",)] = torch.empty((self.n_envs, h, w), dtype=torch.float32, device=self.device)
+        check(self._lib.softrod_render(self._h, C.byref(camera), rgb.data_ptr(), z.data_ptr() if depth else None,
+                                       self._stream()), self._h)
+        return (rgb, z) if depth else rgb
 
     def time_limit(self) -> torch.Tensor:
         """early_termination handles: the last step's time-limit flag per env (row 0 of softrod_state_view.env_aux)

@@ -56,6 +56,8 @@ struct softrod_handle {
     StatePtrs* d_state = nullptr;   // device copy of S (re-uploaded whenever S changes)
     double* d_time_tab = nullptr;   // clock after k env.steps from a reset (clock_after, softrod_fast.hpp)
     double* d_mat = nullptr;        // [kMatRows][64 * epl] material table of a tapered rod
+    double* d_render_radius = nullptr;  // [n_elem] rest radius of every element, for softrod_render: base_radius, or the
+                                        // profile of softrod_set_radius_profile
     double* d_mtab = nullptr;       // [SOFTROD_MAX_MUSCLES][4][64 * epl] ratio_position x, y, z, strength
     bool muscles_set = false;
     unsigned* d_ticket = nullptr;   // softrod_scatter_rows: blocks that have finished storing (tagged form)
@@ -1278,6 +1280,11 @@ int softrod_create(const softrod_config* cfg, int device, softrod_handle** out) 
             for (size_t e = 0; e < NS; ++e) init[(size_t)j * NS + e] = cfg->sucker_reduction_ratio;
         upload(h->S.sucker, init.data(), init.size() * sizeof(double));
     }
+    {   // softrod_render draws every element with its rest radius
+        const std::vector<double> radius((size_t)cfg->n_elem, cfg->base_radius);
+        alloc(h->d_render_radius, radius.size() * sizeof(double));
+        upload(h->d_render_radius, radius.data(), radius.size() * sizeof(double));
+    }
     alloc(h->d_basis, (size_t)2 * kLanes * 7 * sizeof(double));
     h->S.basis = h->d_basis;
     alloc(h->d_init, N * h->init_stride * sizeof(double));
@@ -1726,6 +1733,7 @@ int softrod_set_radius_profile(softrod_handle* h, const double* radius) {
         for (int k = period; k < W; ++k) T[(size_t)row * W + k] = T[(size_t)row * W + (k % period)];
     if (!h->d_mat) SR_HIP(h, alloc_owned(h, h->d_mat, T.size() * sizeof(double)));
     SR_HIP(h, hipMemcpy(h->d_mat, T.data(), T.size() * sizeof(double), hipMemcpyHostToDevice));
+    SR_HIP(h, hipMemcpy(h->d_render_radius, radius, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
     h->S.mat = h->d_mat;
     h->P.mass_total = ms;
     h->tapered = true;
@@ -2071,6 +2079,108 @@ int softrod_copy_envs(softrod_handle* h, const int32_t* src, const int32_t* dst,
     SR_HIP(h, hipMemcpyAsync(h->d_pairs, h->h_pairs, (size_t)n * sizeof(int2), hipMemcpyHostToDevice, st));
     SR_HIP(h, hipEventRecord(h->ev_pairs, st));
     hipLaunchKernelGGL(softrod_copy_envs_kernel, dim3((unsigned)n), dim3(kCopyThreads), 0, st, copy_table(h), h->d_pairs);
+    SR_HIP(h, hipGetLastError());
+    return SOFTROD_OK;
+}
+
+// ---- softrod_render (softrod_render.hpp) ----
+int softrod_camera_default(const softrod_config* cfg, softrod_camera* cam) {
+    if (!cfg || !cam) return fail(nullptr, SOFTROD_EINVAL, "render: null argument");
+    std::memset(cam, 0, sizeof(*cam));
+    cam->struct_size = (uint32_t)sizeof(softrod_camera);
+    cam->width = 84;
+    cam->height = 84;
+    const double L = cfg->base_length;
+    if (cfg->env_kind == SOFTROD_ENV_SOFTPENDULUM3D || cfg->env_kind == SOFTROD_ENV_SOFT_ARM) {
+        // a fixed oblique view from (+x, -y, +z); the reset rod stands on the origin along z (SoftPendulum3D) or y
+        cam->right[0] = 0.8; cam->right[1] = 0.6; cam->right[2] = 0.0;
+        cam->up[0] = -0.36; cam->up[1] = 0.48; cam->up[2] = 0.8;
+        cam->center[cfg->env_kind == SOFTROD_ENV_SOFT_ARM ? 1 : 2] = 0.5 * L;
+        cam->half_width = 0.75 * L;
+    } else {
+        // the pendulum's plane seen along -z, the ground plane seen from above: x right, y up
+        cam->right[0] = 1.0;
+        cam->up[1] = 1.0;
+        if (cfg->features & SOFTROD_FEAT_OCTO_HEAD) {
+            cam->follow = 1;
+            cam->half_width = 1.1 * (cfg->head_radius + L);
+        } else {
+            cam->half_width = 1.1 * L;
+        }
+    }
+    cam->target_radius = 0.05 * L;
+    cam->light[0] = -0.48; cam->light[1] = 0.6; cam->light[2] = 0.64;
+    cam->ambient = 0.35;
+    return SOFTROD_OK;
+}
+
+int softrod_camera_check(const softrod_camera* cam) {
+    if (!cam) return fail(nullptr, SOFTROD_EINVAL, "render: null camera");
+    if (cam->struct_size != sizeof(softrod_camera)) return fail(nullptr, SOFTROD_EINVAL, "render: softrod_camera.struct_size mismatch");
+    if (cam->width < 1 || cam->width > 1024 || cam->height < 1 || cam->height > 1024)
+        return fail(nullptr, SOFTROD_EINVAL, "render: width and height must be 1 .. 1024");
+    const double* fields[] = {cam->center, cam->right, cam->up, cam->light};
+    bool finite = std::isfinite(cam->half_width) && std::isfinite(cam->target_radius) && std::isfinite(cam->ambient);
+    for (const double* f : fields)
+        for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(f[i]);
+    if (!finite) return fail(nullptr, SOFTROD_EINVAL, "render: a camera field is not finite");
+    if (!(cam->half_width > 0.0)) return fail(nullptr, SOFTROD_EINVAL, "render: half_width must be positive");
+    auto dot = [](const double* x, const double* y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; };
+    const double tol = 1e-6;
+    if (std::fabs(std::sqrt(dot(cam->right, cam->right)) - 1.0) > tol || std::fabs(std::sqrt(dot(cam->up, cam->up)) - 1.0) > tol)
+        return fail(nullptr, SOFTROD_EINVAL, "render: right and up must be unit vectors (to 1e-6)");
+    if (std::fabs(dot(cam->right, cam->up)) > tol) return fail(nullptr, SOFTROD_EINVAL, "render: right and up must be orthogonal (to 1e-6)");
+    if (std::fabs(std::sqrt(dot(cam->light, cam->light)) - 1.0) > tol)
+        return fail(nullptr, SOFTROD_EINVAL, "render: light must be a unit vector (to 1e-6)");
+    if (cam->ambient < 0.0 || cam->ambient > 1.0) return fail(nullptr, SOFTROD_EINVAL, "render: ambient must be in [0, 1]");
+    if (cam->target_radius < 0.0) return fail(nullptr, SOFTROD_EINVAL, "render: target_radius must not be negative");
+    if (cam->follow != 0 && cam->follow != 1) return fail(nullptr, SOFTROD_EINVAL, "render: follow must be 0 or 1");
+    return SOFTROD_OK;
+}
+
+int softrod_render(softrod_handle* h, const softrod_camera* cam, uint8_t* rgb, float* depth, void* stream) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "render: null handle");
+    if (!cam) return fail(h, SOFTROD_EINVAL, "render: null camera");
+    if (!rgb) return fail(h, SOFTROD_EINVAL, "render: null rgb buffer");
+    if (softrod_camera_check(cam) != SOFTROD_OK) return fail(h, SOFTROD_EINVAL, g_err);
+    const softrod_config& c = h->cfg;
+    const RodLayout y = rod_layout(h);
+    RenderScene sc{};
+    sc.pos = h->S.pos;
+    sc.head = is_octo(h) ? h->S.head : nullptr;
+    sc.radius = h->d_render_radius;
+    sc.head_radius = (float)c.head_radius;
+    sc.n_envs = c.n_envs; sc.n_elem = c.n_elem; sc.rods = y.rods; sc.lane_stride = y.lane_stride; sc.arm_stride = y.arm_stride;
+    const size_t N = (size_t)c.n_envs;
+    switch (c.env_kind) {      // the env's target, where it has one (render.py draws the same)
+        case SOFTROD_ENV_ARM_SINGLE: sc.target_kind = 1; sc.target_const[0] = c.target[0]; sc.target_const[1] = c.target[1]; break;
+        case SOFTROD_ENV_OCTO_FLAT: sc.target_kind = 2; sc.target = h->S.head + 18 * N; sc.target_dims = 2; break;
+        case SOFTROD_ENV_CRAWL: case SOFTROD_ENV_ARM_TWO: sc.target_kind = 2; sc.target = h->S.aux; sc.target_dims = 2; break;
+        case SOFTROD_ENV_REACH: sc.target_kind = 2; sc.target = h->S.aux; sc.target_dims = 3; break;
+        case SOFTROD_ENV_SOFT_ARM: sc.target_kind = 2; sc.target = h->S.ctrl + N; sc.target_dims = 3; break;
+        default: break;
+    }
+    sc.n_prims = y.rods * c.n_elem + (sc.head ? 1 : 0) + (sc.target_kind ? 1 : 0);
+    if (sc.n_prims > kRenderMaxPrims)
+        return fail(h, SOFTROD_EINVAL, "render: more than " + std::to_string(kRenderMaxPrims) + " primitives per env");
+    RenderCamera rc{};
+    for (int i = 0; i < 3; ++i) {
+        rc.c[i] = cam->center[i]; rc.a[i] = cam->right[i]; rc.b[i] = cam->up[i];
+        rc.light[i] = (float)cam->light[i];
+    }
+    rc.n[0] = rc.a[1] * rc.b[2] - rc.a[2] * rc.b[1];
+    rc.n[1] = rc.a[2] * rc.b[0] - rc.a[0] * rc.b[2];
+    rc.n[2] = rc.a[0] * rc.b[1] - rc.a[1] * rc.b[0];
+    rc.half_width = (float)cam->half_width; rc.target_radius = (float)cam->target_radius; rc.ambient = (float)cam->ambient;
+    rc.width = cam->width; rc.height = cam->height; rc.follow = cam->follow;
+    const int tiles_x = (cam->width + kRenderTileW - 1) / kRenderTileW, tiles_y = (cam->height + kRenderTileH - 1) / kRenderTileH;
+    // a lane's 12 RGB bytes as three 32-bit stores, its four depths as one float4: whole groups of four pixels, aligned buffers
+    if ((size_t)c.n_envs * (size_t)tiles_x * (size_t)tiles_y > (size_t)INT32_MAX)
+        return fail(h, SOFTROD_EINVAL, "render: n_envs x tiles exceeds the grid (render a smaller frame)");
+    const int wide = cam->width % kRenderPx == 0 && ((uintptr_t)rgb & 3u) == 0 && ((uintptr_t)depth & 15u) == 0;
+    SR_ON_DEVICE(h);
+    hipLaunchKernelGGL(softrod_render_kernel, dim3((unsigned)(c.n_envs * tiles_x * tiles_y)), dim3(kRenderThreads),
+                       render_lds_bytes(sc.n_prims), (hipStream_t)stream, sc, rc, rgb, depth, tiles_x, tiles_y, wide);
     SR_HIP(h, hipGetLastError());
     return SOFTROD_OK;
 }

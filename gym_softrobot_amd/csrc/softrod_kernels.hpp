@@ -2173,4 +2173,5 @@ softrod_autoreset_kernel(const RodParams P, const StatePtrs S, float* __restrict
 #include "softrod_strains.hpp"
 #include "softrod_muscle_readout.hpp"
 #include "softrod_joint_readout.hpp"
+#include "softrod_render.hpp"
 #include "softrod_autoreset.hpp"

@@ -904,6 +904,38 @@ class VecRodEnvBase:
         return {"contact_k": c[:, 0].copy(), "contact_nu": c[:, 1].copy(), "kinetic_mu": c[:, 2:5].copy(),
                 "static_mu": c[:, 5:8].copy()}
 
+    def default_camera(self) -> "_capi.SoftrodCamera":
+        """The camera render_frames() uses when given none: _capi.camera_default(cfg), an orthographic 84 x 84 view that
+        frames a freshly reset env (softrod_camera_default, include/softrod.h).  A fresh object: edit its fields (centre,
+        axes, half_width, size, follow, target_radius, light, ambient) and pass it back."""
+        return _capi.camera_default(self.cfg)
+
+    def render_frames(self, width=None, height=None, camera=None, depth=False):
+        """RGB frames of EVERY env without leaving the device: an (N, H, W, 3) uint8 tensor, or (rgb, depth) with depth
+        (N, H, W) float32 (camera-frame depth of the surface, -inf where nothing is drawn) when `depth` is true — pixel
+        observations, RGB-D policies and per-env video logging of a resident batch.  The single-env `render()` (one
+        matplotlib frame from a host snapshot) is what it was; the reference has no batched counterpart.
+
+        `camera`: a _capi.SoftrodCamera shared by all envs (default: default_camera()); `width` / `height` override
+        its size.  Rods are drawn as shaded capsules of their rest radius, one colour per arm, the rigid body and the
+        env's target as spheres; an env whose state is not finite renders as background.  The image model is
+        include/softrod.h's softrod_render.  One HIP kernel (csrc/softrod_render.hpp) on the current stream; the
+        tensors are allocated on first use per (H, W) and overwritten by the next call; usable inside
+        capture_policy_step once a first call has allocated them.  Device tensors (NumPy copies with
+        numpy_output=True).  HIP backend only."""
+        be = self.backend
+        if not hasattr(be, "render"):
+            raise NotImplementedError(f"render_frames needs the HIP backend, not {type(be).__name__}")
+        cam = self.default_camera() if camera is None else camera
+        if width is not None or height is not None:
+            cam = cam.copy()
+            if width is not None:
+                cam.width = int(width)
+            if height is not None:
+                cam.height = int(height)
+        out = be.render(cam, depth=bool(depth))
+        return (self._out(out[0]), self._out(out[1])) if depth else self._out(out)
+
     def capture_policy_step(self, policy):
         """One HIP graph for `actions = policy(obs); step(actions)` — the launch-bound tail of an on-device
         rollout (a small policy is half a dozen tiny kernels per step) becomes ONE graph launch per env.step.

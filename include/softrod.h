@@ -935,6 +935,82 @@ int softrod_set_env_contact(softrod_handle* h, const double* contact, const uint
  *       result would depend on scheduling; copy in two calls instead).                                            */
 int softrod_copy_envs(softrod_handle* h, const int32_t* src, const int32_t* dst, int count, void* stream);
 
+/* Render: batched RGB and depth frames of the resident envs, on the device.  Replaces: render() of
+ * render_mode="rgb_array", which upstream ships on every env (metadata["render_modes"]) and draws one env at a time on
+ * the host; here it is what pixel observations, RGB-D policies and per-env video logging of a resident batch need.  A
+ * small software rasteriser (csrc/softrod_render.hpp) reads the resident state and writes
+ *   rgb    device [n_envs][H][W][3] uint8
+ *   depth  device [n_envs][H][W] float32, or NULL: not wanted (RGB is bitwise the same either way)
+ * on `stream`.  Nothing of upstream's renderers is reproduced (no POV-Ray parity, no perspective, no ground plane, no
+ * anti-aliasing): THE IMAGE MODEL below is this library's own and is the whole contract.
+ * CAMERA (softrod_camera; orthographic, shared by all envs of the handle): `center`; unit, mutually orthogonal axes
+ *   `right` = a and `up` = b; the direction towards the viewer is n = a x b; `half_width` > 0 in world units; `width` W
+ *   and `height` H in pixels; `follow` 0: center is absolute, 1: center is added to the env's anchor — the rigid body's
+ *   position (`head` rows 0-2) for a handle with SOFTROD_FEAT_OCTO_HEAD, else node 0 of rod 0; `target_radius`;
+ *   `light`, a unit vector in camera coordinates; `ambient` in [0, 1].  A world point X maps to
+ *   (u, v, w) = ((X - c) . a, (X - c) . b, (X - c) . n), computed in float64 from the float64 state (a crawling octopus
+ *   may be far from the origin) and only then rounded to float32; everything per pixel is float32.
+ * PIXELS: row i, column j has its centre at u = ((j + 0.5) / W * 2 - 1) * half_width,
+ *   v = (1 - (i + 0.5) / H * 2) * half_width * H / W.
+ * PRIMITIVES, in this order (the order decides ties):
+ *   1. for rod 0 .. rods - 1, for element k = 0 .. n_elem - 1: the capsule between nodes k and k + 1, its radius the
+ *      element's REST radius (base_radius, or element k of softrod_set_radius_profile's array; the dilatation is ignored)
+ *   2. the rigid body of a handle with SOFTROD_FEAT_OCTO_HEAD: a sphere of head_radius
+ *   3. the env's target, a sphere of target_radius: SOFTROD_ENV_ARM_SINGLE softrod_config.target with z = 0;
+ *      SOFTROD_ENV_OCTO_FLAT `head` rows 18-19 with z = 0; the muscle octopus envs `env_aux` rows 0-2, with z = 0 for
+ *      the two-component targets of SOFTROD_ENV_CRAWL / _ARM_TWO; SOFTROD_ENV_SOFT_ARM `control` rows 1-3; the other
+ *      envs have none.
+ * COVERAGE AND DEPTH of a primitive with projected end points A, B and depths wA, wB (a sphere: A = B), at pixel p:
+ *   t = clamp((p - A) . (B - A) / |B - A|^2, 0, 1), t = 0 when |B - A|^2 == 0;  q = A + t (B - A);  d = |p - q|;
+ *   covered iff d < r;  h = sqrt(r^2 - d^2);  surface depth z = wA + t (wB - wA) + h;
+ *   camera-frame normal m = (p_u - q_u, p_v - q_v, h) / r.
+ *   This is a sphere-swept impostor: exact for the silhouette, and exact for the depth where the element is
+ *   perpendicular to the view.  The covering primitive with the greatest z wins; on equal z the lowest index wins.
+ * COLOUR: palette[body] * (ambient + (1 - ambient) * max(0, m . light)) per channel, stored as floor(255 x + 0.5)
+ *   clamped to 0 .. 255; body = the arm index modulo 8 for a rod (entries 0-7), 8 the rigid body, 9 the target.  An
+ *   uncovered pixel gets SOFTROD_RENDER_BACKGROUND and depth -inf.
+ * NON-FINITE STATE: a primitive with a non-finite coordinate or radius (after rounding to float32) covers no pixel: a
+ *   blown-up env renders as background and disturbs no other env.
+ * The call validates with softrod_camera_check before it enqueues anything, then launches ONE kernel: asynchronous on
+ * `stream`, capturable — the camera travels in the kernel arguments, the radii live in a device table made by
+ * softrod_create and rewritten by softrod_set_radius_profile, nothing is uploaded per call.  It reads the state and
+ * writes the two outputs only.  Scope: every handle softrod_create accepts — one- and two-slot rows, windowed long arms,
+ * tapered rods, every OctoFlat wave shape, handles with device-side auto-reset — of at most 8 * 126 + 2 primitives per
+ * env.  Errors, each SOFTROD_EINVAL with its text in softrod_last_error: "render: null handle", "render: null camera",
+ * "render: null rgb buffer", every refusal of softrod_camera_check, "render: more than 1010 primitives per env".
+ *
+ * softrod_camera_default   host only (no device): a view that frames a freshly reset env of `cfg`, 84 x 84 pixels.
+ *                          Planar SoftPendulum: looking along -z, x right, y up, half_width 1.1 base_length.  The
+ *                          ground-plane envs (ArmSingle, ArmPush, OctoFlat, the muscle envs): from above, x right, y up;
+ *                          those with a rigid body follow it and span 1.1 (head_radius + base_length).  SoftPendulum3D
+ *                          and SoftArmTracking: a fixed oblique view from (+x, -y, +z), right (0.8, 0.6, 0), up
+ *                          (-0.36, 0.48, 0.8), centred on the middle of the reset rod, half_width 0.75 base_length.
+ *                          target_radius 0.05 base_length, light (-0.48, 0.6, 0.64), ambient 0.35.
+ * softrod_camera_check     host only: SOFTROD_EINVAL with "render: <reason>" in softrod_last_error(NULL) for a null
+ *                          camera, a wrong struct_size, width or height outside 1 .. 1024, a non-finite field,
+ *                          half_width <= 0, axes whose norms differ from 1 or whose dot product differs from 0 by more
+ *                          than 1e-6, a light that is not unit to 1e-6, ambient outside [0, 1], target_radius < 0, a
+ *                          follow that is neither 0 nor 1.                                                              */
+typedef struct softrod_camera {
+    uint32_t struct_size; /* = sizeof(softrod_camera); ABI guard */
+    int32_t width, height;
+    int32_t follow;
+    double center[3];
+    double right[3];
+    double up[3];
+    double half_width;
+    double target_radius;
+    double light[3];
+    double ambient;
+} softrod_camera;
+/* 0xRRGGBB: arm index modulo 8 (entries 0-7), the rigid body, the target; mirrored in _capi.RENDER_PALETTE */
+#define SOFTROD_RENDER_PALETTE                                                                             \
+    { 0x1F77B4u, 0xFF7F0Eu, 0x2CA02Cu, 0xD62728u, 0x9467BDu, 0x8C564Bu, 0xE377C2u, 0x17BECFu, 0x7F7F7Fu, 0xBCBD22u }
+#define SOFTROD_RENDER_BACKGROUND 0xF5F5F5u
+int softrod_camera_default(const softrod_config* cfg, softrod_camera* cam);
+int softrod_camera_check(const softrod_camera* cam);
+int softrod_render(softrod_handle* h, const softrod_camera* cam, uint8_t* rgb, float* depth, void* stream);
+
 /* Run `n` bare PositionVerlet substeps with fixed per-env forcing inputs and no
  * env epilogue (the inner loop of soft_pendulum.py:183-184 alone); `actions`
  * (device [n_envs] float32 or NULL) feeds SOFTROD_FEAT_POINT_FORCE_NODE0_X.
