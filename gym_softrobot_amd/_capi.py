@@ -900,6 +900,26 @@ def rod_dynamics_refusal(cfg: "SoftrodConfig", muscles_set: bool = True):
     return None
 
 
+# what softrod_rod_clearance answers before it looks at the handle
+ROD_CLEARANCE_ARGUMENT_ERRORS = ("rod clearance: null handle", "rod clearance: null output buffer",
+                                 "rod clearance: self_gap must be 2 .. 126")
+# the env kinds whose envs have a target point (what softrod_render draws and softrod_rod_clearance measures to)
+TARGET_ENVS = (ENV_ARM_SINGLE, ENV_OCTO_FLAT, ENV_CRAWL, ENV_ARM_TWO, ENV_REACH, ENV_SOFT_ARM)
+
+
+def rod_clearance_self_gap(rest_length, radii) -> int:
+    """The self_gap rod_clearance() passes to softrod_rod_clearance by default: max(2, 1 + ceil(2 max(radii) /
+    rest_length)) for a rod of rest element length `rest_length` and element radii `radii` (a scalar or an array) —
+    the first separation j - i at which two elements of a STRAIGHT rod no longer overlap by construction: the gap
+    between them is (j - i - 1) rest_length - r_i - r_j.  (The library takes 2 .. 126 and refuses anything else.)"""
+    import math
+
+    import numpy as np
+
+    r = float(np.max(np.asarray(radii, np.float64)))
+    return max(2, 1 + math.ceil(2.0 * r / float(rest_length)))
+
+
 def env_contact_defaults(cfg: "SoftrodConfig") -> "np.ndarray":
     """(8,) float64: the config's own contact_k, contact_nu, kinetic_mu[3], static_mu[3] (forward, backward,
     sideways)."""
@@ -1012,6 +1032,7 @@ _EXPORTS = {
     "softrod_camera_default": (C.c_int, [C.POINTER(SoftrodConfig), C.POINTER(SoftrodCamera)]),
     "softrod_camera_check": (C.c_int, [C.POINTER(SoftrodCamera)]),
     "softrod_render": (C.c_int, [_VP, C.POINTER(SoftrodCamera), _VP, _VP, _VP]),
+    "softrod_rod_clearance": (C.c_int, [_VP, C.c_int, _VP, _VP]),
     "softrod_substeps": (C.c_int, [_VP, _VP, C.c_int, _VP]),
     "softrod_state_view_get": (C.c_int, [_VP, C.POINTER(SoftrodStateView)]),
     "softrod_set_timing": (C.c_int, [_VP, C.c_int]),

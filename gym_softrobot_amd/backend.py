@@ -11,8 +11,8 @@ import torch
 
 from . import _capi
 from ._capi import LANE_STRIDE, SoftrodConfig, SoftrodStateView, check, load_library
-from .diagnostics import (JointLoads, MuscleLoads, RodDynamics, RodStrains, joint_loads_views, muscle_loads_views,
-                          rod_dynamics_views, rod_strains_views)
+from .diagnostics import (JointLoads, MuscleLoads, RodClearance, RodDynamics, RodStrains, joint_loads_views,
+                          muscle_loads_views, rod_clearance_views, rod_dynamics_views, rod_strains_views)
 
 
 class _DevArray:
@@ -76,7 +76,7 @@ class HipRodBackend:
         # per-handle physics tables that live outside softrod_config (action basis, spline table,
         # radius profile): their bytes go into config_fingerprint()
         self._tables: Dict[str, bytes] = {}
-        self._readouts: Dict[str, torch.Tensor] = {}     # rod_energies / ground_reaction / rod_strains / muscle_loads / joint_loads / rod_dynamics buffers (_readout)
+        self._readouts: Dict[str, torch.Tensor] = {}     # rod_energies / ground_reaction / rod_strains / muscle_loads / joint_loads / rod_dynamics / rod_clearance buffers (_readout)
         self._frames: Dict[tuple, torch.Tensor] = {}      # render(): the RGB and depth frames per (H, W)
         check(self._lib.softrod_create(C.byref(self.cfg), self.device_index, C.byref(self._h)))
         if self.cfg.features & _capi.FEAT_REST_KAPPA_ACTION:
@@ -339,13 +339,13 @@ class HipRodBackend:
 
     supports_early_termination = True     # softrod_config.early_termination runs in the step kernels' epilogue
 
-    def _readout(self, entry: str, rods: int, *tail: int) -> torch.Tensor:
+    def _readout(self, entry: str, rods: int, *tail: int, args: tuple = ()) -> torch.Tensor:
         """One per-rod read-out softrod_<entry>: its (n_envs, rods, *tail) float64 device buffer, allocated on first
-        use and filled by the call."""
+        use and filled by the call.  `args`: what the entry point takes between the handle and the buffer."""
         buf = self._readouts.get(entry)
         if buf is None:
             buf = self._readouts[entry] = torch.empty((self.n_envs, rods, *tail), dtype=torch.float64, device=self.device)
-        check(getattr(self._lib, "softrod_" + entry)(self._h, buf.data_ptr(), self._stream()), self._h)
+        check(getattr(self._lib, "softrod_" + entry)(self._h, *args, buf.data_ptr(), self._stream()), self._h)
         return buf
 
     def rod_energies(self) -> torch.Tensor:
@@ -402,6 +402,23 @@ class HipRodBackend:
         (n_envs, rods_per_env, 18, n_elem + 1) buffer allocated on first use and overwritten by the next call."""
         rods = _capi.config_rods_per_env(self.cfg)
         return rod_dynamics_views(self._readout("rod_dynamics", rods, 18, int(self.cfg.n_elem) + 1))
+
+    def rod_clearance(self, self_gap: Optional[int] = None) -> RodClearance:
+        """softrod_rod_clearance: RodClearance(gap, distance, element, point, target_gap, target_distance,
+        target_element, target_point) of float64 device tensors — (n_envs, rods_per_env, rods_per_env) twice,
+        (n_envs, rods_per_env, rods_per_env, 2) twice, (n_envs, rods_per_env) four times (None for an env kind without
+        a target) — the least capsule gap between every two rods, within every rod (element pairs at least `self_gap`
+        apart) and from every rod to the env's target (include/softrod.h).  self_gap None:
+        _capi.rod_clearance_self_gap of the rest element length and the radii this handle was built with (the radius
+        profile if one was set, else base_radius).  Views of one (n_envs, rods_per_env, rods_per_env + 1, 6) buffer
+        allocated on first use and overwritten by the next call."""
+        rods, n = _capi.config_rods_per_env(self.cfg), int(self.cfg.n_elem)
+        if self_gap is None:
+            prof = self._tables.get("radius_profile")
+            radii = float(self.cfg.base_radius) if prof is None else np.frombuffer(prof, np.float64)
+            self_gap = _capi.rod_clearance_self_gap(float(self.cfg.base_length) / n, radii)
+        buf = self._readout("rod_clearance", rods, rods + 1, 6, args=(int(self_gap),))
+        return rod_clearance_views(buf, int(self.cfg.env_kind) in _capi.TARGET_ENVS)
 
     def render(self, camera: "_capi.SoftrodCamera", depth: bool = False):
         """softrod_render: one (n_envs, H, W, 3) uint8 device tensor of RGB frames of every env through `camera`

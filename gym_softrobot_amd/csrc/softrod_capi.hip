@@ -56,8 +56,8 @@ struct softrod_handle {
     StatePtrs* d_state = nullptr;   // device copy of S (re-uploaded whenever S changes)
     double* d_time_tab = nullptr;   // clock after k env.steps from a reset (clock_after, softrod_fast.hpp)
     double* d_mat = nullptr;        // [kMatRows][64 * epl] material table of a tapered rod
-    double* d_render_radius = nullptr;  // [n_elem] rest radius of every element, for softrod_render: base_radius, or the
-                                        // profile of softrod_set_radius_profile
+    double* d_render_radius = nullptr;  // [n_elem] rest radius of every element, for softrod_render and
+                                        // softrod_rod_clearance: base_radius, or the profile of softrod_set_radius_profile
     double* d_mtab = nullptr;       // [SOFTROD_MAX_MUSCLES][4][64 * epl] ratio_position x, y, z, strength
     bool muscles_set = false;
     unsigned* d_ticket = nullptr;   // softrod_scatter_rows: blocks that have finished storing (tagged form)
@@ -2083,6 +2083,25 @@ int softrod_copy_envs(softrod_handle* h, const int32_t* src, const int32_t* dst,
     return SOFTROD_OK;
 }
 
+namespace {
+// The env's target, where its kind has one: the point softrod_render draws (render.py draws the same) and
+// softrod_rod_clearance measures to.
+EnvTarget env_target(const softrod_handle* h) {
+    const softrod_config& c = h->cfg;
+    const size_t N = (size_t)c.n_envs;
+    EnvTarget T{};
+    switch (c.env_kind) {
+        case SOFTROD_ENV_ARM_SINGLE: T.kind = 1; T.constant[0] = c.target[0]; T.constant[1] = c.target[1]; break;
+        case SOFTROD_ENV_OCTO_FLAT: T.kind = 2; T.rows = h->S.head + 18 * N; T.dims = 2; break;
+        case SOFTROD_ENV_CRAWL: case SOFTROD_ENV_ARM_TWO: T.kind = 2; T.rows = h->S.aux; T.dims = 2; break;
+        case SOFTROD_ENV_REACH: T.kind = 2; T.rows = h->S.aux; T.dims = 3; break;
+        case SOFTROD_ENV_SOFT_ARM: T.kind = 2; T.rows = h->S.ctrl + N; T.dims = 3; break;
+        default: break;
+    }
+    return T;
+}
+}  // namespace
+
 // ---- softrod_render (softrod_render.hpp) ----
 int softrod_camera_default(const softrod_config* cfg, softrod_camera* cam) {
     if (!cfg || !cam) return fail(nullptr, SOFTROD_EINVAL, "render: null argument");
@@ -2151,16 +2170,8 @@ int softrod_render(softrod_handle* h, const softrod_camera* cam, uint8_t* rgb, f
     sc.radius = h->d_render_radius;
     sc.head_radius = (float)c.head_radius;
     sc.n_envs = c.n_envs; sc.n_elem = c.n_elem; sc.rods = y.rods; sc.lane_stride = y.lane_stride; sc.arm_stride = y.arm_stride;
-    const size_t N = (size_t)c.n_envs;
-    switch (c.env_kind) {      // the env's target, where it has one (render.py draws the same)
-        case SOFTROD_ENV_ARM_SINGLE: sc.target_kind = 1; sc.target_const[0] = c.target[0]; sc.target_const[1] = c.target[1]; break;
-        case SOFTROD_ENV_OCTO_FLAT: sc.target_kind = 2; sc.target = h->S.head + 18 * N; sc.target_dims = 2; break;
-        case SOFTROD_ENV_CRAWL: case SOFTROD_ENV_ARM_TWO: sc.target_kind = 2; sc.target = h->S.aux; sc.target_dims = 2; break;
-        case SOFTROD_ENV_REACH: sc.target_kind = 2; sc.target = h->S.aux; sc.target_dims = 3; break;
-        case SOFTROD_ENV_SOFT_ARM: sc.target_kind = 2; sc.target = h->S.ctrl + N; sc.target_dims = 3; break;
-        default: break;
-    }
-    sc.n_prims = y.rods * c.n_elem + (sc.head ? 1 : 0) + (sc.target_kind ? 1 : 0);
+    sc.target = env_target(h);
+    sc.n_prims = y.rods * c.n_elem + (sc.head ? 1 : 0) + (sc.target.kind ? 1 : 0);
     if (sc.n_prims > kRenderMaxPrims)
         return fail(h, SOFTROD_EINVAL, "render: more than " + std::to_string(kRenderMaxPrims) + " primitives per env");
     RenderCamera rc{};
@@ -2181,6 +2192,24 @@ int softrod_render(softrod_handle* h, const softrod_camera* cam, uint8_t* rgb, f
     SR_ON_DEVICE(h);
     hipLaunchKernelGGL(softrod_render_kernel, dim3((unsigned)(c.n_envs * tiles_x * tiles_y)), dim3(kRenderThreads),
                        render_lds_bytes(sc.n_prims), (hipStream_t)stream, sc, rc, rgb, depth, tiles_x, tiles_y, wide);
+    SR_HIP(h, hipGetLastError());
+    return SOFTROD_OK;
+}
+
+// ---- softrod_rod_clearance (softrod_clearance.hpp) ----
+int softrod_rod_clearance(softrod_handle* h, int self_gap, double* out, void* stream) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "rod clearance: null handle");
+    if (!out) return fail(h, SOFTROD_EINVAL, "rod clearance: null output buffer");
+    if (self_gap < 2 || self_gap > 126) return fail(h, SOFTROD_EINVAL, "rod clearance: self_gap must be 2 .. 126");
+    // every handle's resident rows have rod_layout's form, so there is no refusal list
+    const softrod_config& c = h->cfg;
+    const RodLayout y = rod_layout(h);
+    const size_t waves = (size_t)c.n_envs * (size_t)(y.rods * (y.rods + 1) / 2 + y.rods);    // pairs a <= b, then the targets
+    if (waves > (size_t)INT32_MAX) return fail(h, SOFTROD_EINVAL, "rod clearance: n_envs x record pairs exceeds the grid");
+    SR_ON_DEVICE(h);
+    hipLaunchKernelGGL(by_epl(h, softrod_rod_clearance_kernel<1>, softrod_rod_clearance_kernel<2>), dim3((unsigned)waves),
+                       dim3(kLanes), 0, (hipStream_t)stream, h->S.pos, h->d_render_radius, env_target(h), c.n_envs, c.n_elem,
+                       y.rods, y.lane_stride, y.arm_stride, self_gap, out);
     SR_HIP(h, hipGetLastError());
     return SOFTROD_OK;
 }

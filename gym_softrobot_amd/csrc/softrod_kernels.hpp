@@ -2174,4 +2174,5 @@ softrod_autoreset_kernel(const RodParams P, const StatePtrs S, float* __restrict
 #include "softrod_muscle_readout.hpp"
 #include "softrod_joint_readout.hpp"
 #include "softrod_render.hpp"
+#include "softrod_clearance.hpp"
 #include "softrod_autoreset.hpp"

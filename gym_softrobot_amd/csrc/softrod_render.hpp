@@ -69,17 +69,32 @@ struct RenderCamera {
     int width, height, follow;
 };
 
-// What of the handle the kernel reads.  target_kind: 0 none, 1 target_const (z = 0), 2 rows of `target` ([dims][n_envs],
+// An env's target point, where its kind has one: what softrod_render draws and softrod_rod_clearance measures to (the
+// host fills it in env_target, softrod_capi.hip).  kind: 0 none, 1 `constant` (z = 0), 2 rows of `rows` ([dims][n_envs],
 // z = 0 with dims == 2).
+struct EnvTarget {
+    const double* rows;
+    double constant[2];
+    int kind, dims;
+};
+__device__ __forceinline__ void env_target_point(const EnvTarget& T, size_t N, int env, double X[3]) {
+    if (T.kind == 1) {
+        X[0] = T.constant[0]; X[1] = T.constant[1]; X[2] = 0.0;
+    } else {
+        X[0] = T.rows[env]; X[1] = T.rows[N + env];
+        X[2] = T.dims == 3 ? T.rows[2 * N + env] : 0.0;
+    }
+}
+
+// What of the handle the kernel reads.
 struct RenderScene {
     const double* pos;        // [3][n_envs][lane_stride]
     const double* head;       // [20][n_envs], rows 0-2 the rigid body's position; nullptr: no head
-    const double* target;
     const double* radius;     // [n_elem] rest radius of every element
-    double target_const[2];
+    EnvTarget target;
     float head_radius;
     int n_envs, n_elem, rods, lane_stride, arm_stride;
-    int n_prims, target_kind, target_dims;
+    int n_prims;
 };
 
 __device__ __forceinline__ bool render_finite(float x) { return fabsf(x) <= FLT_MAX; }    // false for NaN and +-inf
@@ -144,12 +159,7 @@ softrod_render_kernel(const RenderScene sc, const RenderCamera cam, uint8_t* __r
                 r = sc.head_radius;
                 body = 8;
             } else {
-                if (sc.target_kind == 1) {
-                    A[0] = sc.target_const[0]; A[1] = sc.target_const[1]; A[2] = 0.0;
-                } else {
-                    A[0] = sc.target[env]; A[1] = sc.target[N + env];
-                    A[2] = sc.target_dims == 3 ? sc.target[2 * N + env] : 0.0;
-                }
+                env_target_point(sc.target, N, env, A);
 #pragma unroll
                 for (int q = 0; q < 3; ++q) B[q] = A[q];
                 r = cam.target_radius;

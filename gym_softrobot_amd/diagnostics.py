@@ -328,6 +328,33 @@ def rod_dynamics_views(buf) -> RodDynamics:
                        buf[..., 12:15, :], buf[..., 15:18, :-1])
 
 
+class RodClearance(NamedTuple):
+    """What softrod_rod_clearance / rod_clearance() return (include/softrod.h): for every row rod a and column rod b of
+    an env, gap (.., rods, rods) = the least (centre-line distance - r_i - r_j) over the element pairs (negative when
+    the capsules interpenetrate; a == b: over the pairs with j - i >= self_gap), distance (.., rods, rods) = that
+    pair's centre-line distance, element (.., rods, rods, 2) = (i, j) as exact float64 and point (.., rods, rods, 2) =
+    (s, t), the closest points' parameters along the two elements; [b][a] is [a][b] with i <-> j, s <-> t.  For the
+    env's target: target_distance (.., rods) from the target to the nearest point of rod a's centre line, target_gap
+    = target_distance - r_i, target_element i and target_point s; all four None for an env kind without a target.
+    No pair: +inf, +inf, -1, -1, 0, 0.  A non-finite rod: NaN, NaN, -1, -1, NaN, NaN in its rows and columns."""
+    gap: object
+    distance: object
+    element: object
+    point: object
+    target_gap: object
+    target_distance: object
+    target_element: object
+    target_point: object
+
+
+def rod_clearance_views(buf, has_target: bool = True) -> RodClearance:
+    """The eight fields as views of softrod_rod_clearance's buffer (.., rods, rods + 1, 6): the last column holds the
+    target's records (None fields with has_target false)."""
+    rods, tgt = buf[..., :-1, :], buf[..., -1, :]
+    target = (tgt[..., 0], tgt[..., 1], tgt[..., 2], tgt[..., 4]) if has_target else (None,) * 4
+    return RodClearance(rods[..., 0], rods[..., 1], rods[..., 2:4], rods[..., 4:6], *target)
+
+
 def _z_rotation(vector, theta):
     """joint.py:7-17."""
     theta = theta / 180.0 * np.pi

@@ -187,6 +187,13 @@ class SingleRodEnv(GymEnv):
         r = self._vec.rod_dynamics()
         return type(r)(*(t[0] for t in r))
 
+    def rod_clearance(self, self_gap=None):
+        """VecRodEnvBase.rod_clearance of this env, without the env axis, as NumPy arrays: RodClearance(gap (rods, rods),
+        distance (rods, rods), element (rods, rods, 2), point (rods, rods, 2), target_gap (rods,), target_distance
+        (rods,), target_element (rods,), target_point (rods,)); the target fields None for an env without a target."""
+        r = self._vec.rod_clearance(self_gap)
+        return type(r)(*(None if t is None else t[0] for t in r))
+
     def save_data(self, filename_video, fps):
         """The reference renders `rod_parameters_dict` to a video here (soft_pendulum.py:253-256, flat_env.py:410-420);
         drawing is out of scope: the data is in `rod_parameters_dict`, nothing is written."""
@@ -784,6 +791,33 @@ class VecRodEnvBase:
             raise NotImplementedError(why)
         r = be.rod_dynamics()
         return type(r)(*(self._out(t) for t in r))
+
+    def rod_clearance(self, self_gap=None):
+        """RodClearance(gap, distance, element, point, target_gap, target_distance, target_element, target_point):
+        where the rods of every env are relative to each other, to themselves and to the env's target — upstream has
+        no rod-rod contact in any env (arms pass through each other, a long arm through itself), and this is what a
+        collision penalty, a planner on fork() that rejects interpenetrating gaits, or a grasping reward needs —
+        without leaving the device.  Element k of a rod is the capsule around the segment node k -> node k + 1 with
+        the element's REST radius (a radius profile is honoured, the dilatation ignored); the rigid head / weight is
+        deliberately not a body: the arms are joined to it.  gap (N, rods_per_env, rods_per_env) is the least
+        (centre-line distance - r_i - r_j) over the element pairs of row rod a and column rod b, negative when the
+        capsules interpenetrate; distance that pair's centre-line distance; element (.., 2) its (i, j) as exact
+        float64; point (.., 2) the closest points' parameters (s, t) in [0, 1] along the two elements; [b][a] is
+        [a][b] with i <-> j, s <-> t.  The diagonal is the rod against itself, over the pairs with j - i >= self_gap
+        (None: the first separation at which two elements of the straight rest rod no longer overlap,
+        _capi.rod_clearance_self_gap; 2 .. 126); +inf, +inf, -1, -1, 0, 0 where no such pair exists.  target_distance
+        (N, rods_per_env) is the distance from the env's target (the one render_frames() draws) to the nearest point
+        of the rod's centre line, target_gap = target_distance - r_i, target_element i, target_point s; the four are
+        None for an env without a target.  Among equal gaps the lowest i, then the lowest j wins.  A rod with a
+        non-finite node has NaN, NaN, -1, -1, NaN, NaN in its rows and columns and disturbs no other (include/softrod.h
+        softrod_rod_clearance).  THE INSTANT is the state as it stands.  Every env kind, rods of up to 126 elements, on
+        the HIP backend; elsewhere NotImplementedError.  Device tensors, views of one buffer overwritten by the next
+        call (NumPy copies with numpy_output=True).  Inside a capture_policy_step graph when the policy calls it."""
+        be = self.backend
+        if not hasattr(be, "rod_clearance"):
+            raise NotImplementedError(f"rod clearance needs the HIP backend, not {type(be).__name__}")
+        r = be.rod_clearance(self_gap)
+        return type(r)(*(None if t is None else self._out(t) for t in r))
 
     # -- per-env material (domain randomisation) ----------------------------------------
     _MATERIAL_KEYS = ("youngs_modulus", "shear_modulus", "density", "damping_constant")

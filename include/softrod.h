@@ -1011,6 +1011,65 @@ int softrod_camera_default(const softrod_config* cfg, softrod_camera* cam);
 int softrod_camera_check(const softrod_camera* cam);
 int softrod_render(softrod_handle* h, const softrod_camera* cam, uint8_t* rgb, float* depth, void* stream);
 
+/* Rod clearance: where the rods of an env are relative to each other, to themselves and to the env's target, on the
+ * device — arm-arm, self and target proximity.  Upstream has no rod-rod contact in any env (arms pass through each
+ * other, a long arm through itself) and rewards reaching by tip or head distance only; this is what a collision
+ * penalty, a planner that rejects interpenetrating gaits on forked envs, a sucker-based grasping reward or a
+ * tactile-proximity observation needs.  One cold kernel (csrc/softrod_clearance.hpp) reads the resident positions and
+ * writes `out`.
+ * BODIES: element k of a rod is the capsule around the segment node k -> node k + 1; its radius is the element's REST
+ * radius, the table softrod_render draws with (base_radius, or element k of softrod_set_radius_profile's array), so a
+ * radius profile is honoured and the dilatation is ignored.  The rigid head / weight of a handle with
+ * SOFTROD_FEAT_OCTO_HEAD is deliberately NOT a body here: the arms are joined to it, so their first element always
+ * "touches".
+ * out: device [n_envs][rods_per_env][rods_per_env + 1][6] float64, rods_per_env as for softrod_rod_energies.  For env
+ * e, row rod a and column b, out[e][a][b][0..5] is one record
+ *     gap, distance, i, j, s, t
+ *   b < rods_per_env, b != a (arm-arm), over all element pairs (i of rod a, j of rod b): gap = the minimum of
+ *     (centre-line distance - r_i) - r_j, negative when the capsules interpenetrate; distance = that pair's
+ *     centre-line distance; i, j the element indices; s, t in [0, 1] the closest points' parameters along element i
+ *     and element j.  Record [b][a] is the SAME pair with i <-> j and s <-> t: it is evaluated once, as rod a < b
+ *     against rod b, and written twice.
+ *   b == a (self): the same over the pairs with j - i >= self_gap; 2 <= self_gap <= 126.  If no such pair exists
+ *     (n_elem <= self_gap) the record is +inf, +inf, -1, -1, 0, 0.  There is no default: the first separation at
+ *     which two elements of a STRAIGHT rod no longer overlap by construction is max(2, 1 + ceil(2 max(r) / rest
+ *     element length)), which the Python layer passes (_capi.rod_clearance_self_gap).
+ *   b == rods_per_env (target): distance = the distance from the env's target point to the nearest point of rod a's
+ *     centre line, gap = distance - r_i, i the element, s the parameter along it, j = -1, t = 0.  The target is the
+ *     one softrod_render draws (PRIMITIVES, 3): SOFTROD_ENV_ARM_SINGLE softrod_config.target with z = 0;
+ *     SOFTROD_ENV_OCTO_FLAT `head` rows 18-19 with z = 0; the muscle octopus envs `env_aux` rows 0-2, with z = 0 for
+ *     SOFTROD_ENV_CRAWL / _ARM_TWO; SOFTROD_ENV_SOFT_ARM `control` rows 1-3.  The other envs have none: their target
+ *     records are +inf, +inf, -1, -1, 0, 0 whatever the state.
+ *   The indices are stored as exact doubles.  Every record is written by every call.
+ * ARITHMETIC: float64 as written — IEEE division and sqrt, no contraction, u . v = (u0 v0 + u1 v1) + u2 v2.  Every
+ *   coordinate (rod a's nodes, rod b's nodes, the target) is taken relative to node 0 of rod a BEFORE any product: a
+ *   crawling octopus may be metres from the origin, and the products cancel.  clamp(x) = 0 if x < 0, 1 if x > 1, else x.
+ * THE SEGMENT-SEGMENT RULE is the clamped closest-point construction (Ericson, Real-Time Collision Detection,
+ *   5.1.9) for P1 + s d1 (element i: P1 node i, d1 = node i + 1 - node i) and P2 + t d2 (element j):
+ *     r = P1 - P2;  a = d1 . d1;  e = d2 . d2;  f = d2 . r;  c = d1 . r;  b = d1 . d2
+ *     a zero-length element is a point:   not a > 0 and not e > 0:  s = t = 0
+ *                                         not a > 0:                s = 0, t = clamp(f / e)
+ *                                         not e > 0:                t = 0, s = clamp(-c / a)
+ *     otherwise  denom = a e - b b;  s = clamp((b f - c e) / denom) if denom > 0, else s = 0 (parallel elements take
+ *                s = 0 first);  t = (b s + f) / e;
+ *                if t < 0: t = 0, s = clamp(-c / a);   else if t > 1: t = 1, s = clamp((b - c) / a)
+ *     distance = |(P1 + d1 s) - (P2 + d2 t)|;   gap = (distance - r_i) - r_j.
+ *   THE POINT-SEGMENT RULE of the target X: s = clamp(((X - P1) . d1) / a), s = 0 when not a > 0;
+ *     distance = |X - (P1 + d1 s)|;  gap = distance - r_i.
+ * TIES: among exactly equal gaps the lowest i wins, then the lowest j ((gap, i, j) compared lexicographically in the
+ *   lanes and across the wave, no atomics): the answer does not depend on scheduling, and two calls on one state are
+ *   bitwise equal.
+ * NON-FINITE STATE: if any of nodes 0 .. n_elem of rod a is NaN or +-inf, every record of row a and of column a is
+ *   NaN, NaN, -1, -1, NaN, NaN (the target record too, in an env that has a target); a non-finite target does the same
+ *   to the target column only.  Other rods and other envs are not disturbed.  Every test is a comparison that is false
+ *   for a NaN; no state is converted from float to int.
+ * Asynchronous on `stream`, like softrod_rod_energies; it allocates and uploads nothing and is capturable.  It reads
+ * the state (slots past a rod are never read) and writes `out` only.  Scope: every handle softrod_create accepts —
+ * every env kind, 2 .. 126 elements, one- and two-slot rows, windowed long arms, tapered rods, every OctoFlat wave
+ * shape.  Errors, each SOFTROD_EINVAL with its text in softrod_last_error, found before a device is looked for:
+ * "rod clearance: null handle", "rod clearance: null output buffer", "rod clearance: self_gap must be 2 .. 126".    */
+int softrod_rod_clearance(softrod_handle* h, int self_gap, double* out, void* stream);
+
 /* Run `n` bare PositionVerlet substeps with fixed per-env forcing inputs and no
  * env epilogue (the inner loop of soft_pendulum.py:183-184 alone); `actions`
  * (device [n_envs] float32 or NULL) feeds SOFTROD_FEAT_POINT_FORCE_NODE0_X.
