@@ -513,7 +513,7 @@ class HipRodBackend:
         )
 
     def set_timing(self, n_launches: int) -> None:
-        """Record HIP events around the next `n_launches` kernels (0 = off)."""
+        """Time the next `n_launches` steps with HIP events attached to their own kernel dispatches (0 = off)."""
         check(self._lib.softrod_set_timing(self._h, int(n_launches)), self._h)
 
     def kernel_times_ms(self) -> np.ndarray:

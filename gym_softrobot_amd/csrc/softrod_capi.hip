@@ -6,6 +6,7 @@
 // initial frame of each rod, build.py:46-61), which the reference also performs once
 // per reset on the host.
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 
 #include <cmath>
 #include <cstdio>
@@ -600,6 +601,18 @@ int set_env_table(softrod_handle* h, EnvTable<Row>& T, const Row*& slot, unsigne
     return SOFTROD_OK;
 }
 
+// One kernel of an env.step.  Untimed (no event): the plain launch.  Timed: the kernel's own dispatch carries the time
+// stamps — `t0` takes the dispatch's begin, `t1` its end — instead of an event record in front of it and one behind,
+// each a packet of its own with a system-scope release that the stream waits out.  So a timed step costs what an
+// untimed one costs, and hipEventElapsedTime(t0, t1) is the kernels' own duration, first begin to last end.
+// (Measured against the event records and against records of hipEventReleaseToDevice events, alternating fresh
+// processes at 4096 envs: profiles/planar_step_ab.json.)
+template <class K, class... A>
+void launch_stamped(K kernel, const dim3& grid, const dim3& block, hipStream_t st, hipEvent_t t0, hipEvent_t t1, A... args) {
+    if (t0 || t1) hipExtLaunchKernelGGL(kernel, grid, block, 0, st, t0, t1, 0, args...);
+    else hipLaunchKernelGGL(kernel, grid, block, 0, st, args...);
+}
+
 int launch_step(softrod_handle* h, const float* actions, float* obs, double* reward,
                 uint8_t* term, uint8_t* trunc, double* aux, int n_sub, int epilogue, int pack,
                 hipStream_t st) {
@@ -622,28 +635,28 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
     // a windowed env.step: its substeps, then reward / observation by the row of the same handle's plain substeps
     const StepChoice after = c.row->windowed ? select_step(h, 0) : StepChoice{nullptr, nullptr};
     if (c.row->windowed && !after.row) return fail(h, SOFTROD_EINVAL, after.why);
-    auto launch = [&](const StepRow& r, int n, int epi) {
+    auto launch = [&](const StepRow& r, int n, int epi, hipEvent_t t0, hipEvent_t t1) {
         const dim3 grid((unsigned)((h->cfg.n_envs + r.epb - 1) / r.epb)), block(kLanes * (r.waves ? r.waves : h->nw));
-        if (r.window) hipLaunchKernelGGL(r.window, grid, block, 0, st, h->P, h->S, actions, n, h->window_refresh);
-        else if (r.octo) hipLaunchKernelGGL(r.octo, grid, block, 0, st, h->P, h->S, actions, obs, reward, term, trunc, n, epi, pack);
-        else hipLaunchKernelGGL(r.step, grid, block, 0, st, h->P, h->S, actions, obs, reward, term, trunc, aux, n, epi, pack);
+        if (r.window) launch_stamped(r.window, grid, block, st, t0, t1, h->P, h->S, actions, n, h->window_refresh);
+        else if (r.octo) launch_stamped(r.octo, grid, block, st, t0, t1, h->P, h->S, actions, obs, reward, term, trunc, n, epi, pack);
+        else launch_stamped(r.step, grid, block, st, t0, t1, h->P, h->S, actions, obs, reward, term, trunc, aux, n, epi, pack);
     };
+    // A timed step: its pair of events rides on the step's own dispatches (launch_stamped) — the start on the first
+    // kernel of the step, the stop on the last, one pair per step whatever the number of kernels.
     const bool timing = h->timed < (int)h->ev_start.size();
-    if (timing) SR_HIP(h, hipEventRecord(h->ev_start[h->timed], st));
+    const hipEvent_t t0 = timing ? h->ev_start[h->timed] : nullptr, t1 = timing ? h->ev_stop[h->timed] : nullptr;
     // the muscle octopus: set_action | the body's substeps | get_state + reward; the timing events bracket all three
     const bool mocto = c.row->env == kMoctoEnvs;
+    const bool action_first = mocto && epilogue && actions, epilogue_last = mocto && epilogue;
     const dim3 grid((unsigned)h->cfg.n_envs), block(kLanes * h->nw);
-    if (mocto && epilogue && actions)
-        hipLaunchKernelGGL(softrod_mocto_action_kernel, grid, block, 0, st, h->P, h->S, actions, n_sub);
-    launch(*c.row, n_sub, epilogue);
-    if (after.row) launch(*after.row, 0, 1);
-    if (mocto && epilogue)
-        hipLaunchKernelGGL(softrod_mocto_epilogue_kernel, grid, block, 0, st, h->P, h->S, obs, reward, term, trunc, 1, pack);
+    if (action_first)
+        launch_stamped(softrod_mocto_action_kernel, grid, block, st, t0, nullptr, h->P, h->S, actions, n_sub);
+    launch(*c.row, n_sub, epilogue, action_first ? nullptr : t0, (after.row || epilogue_last) ? nullptr : t1);
+    if (after.row) launch(*after.row, 0, 1, nullptr, epilogue_last ? nullptr : t1);
+    if (epilogue_last)
+        launch_stamped(softrod_mocto_epilogue_kernel, grid, block, st, nullptr, t1, h->P, h->S, obs, reward, term, trunc, 1, pack);
     SR_HIP(h, hipGetLastError());
-    if (timing) {
-        SR_HIP(h, hipEventRecord(h->ev_stop[h->timed], st));
-        ++h->timed;
-    }
+    if (timing) ++h->timed;
     // behind the timing record, so that kernel_times_ms keeps meaning the step (as for the NEXT_STEP pass in front)
     if (h->q_depth > 0 && epilogue && h->same_step)
         if (const int rc = launch_autoreset_same_step(h, obs, aux, pack, st)) return rc;

@@ -1078,9 +1078,12 @@ int softrod_substeps(softrod_handle* h, const float* actions, int n, void* strea
 
 int softrod_state_view_get(softrod_handle* h, softrod_state_view* out);
 
-/* Kernel timing with HIP events recorded on the launch stream around each
- * softrod_step / softrod_substeps kernel (no host synchronisation at record
- * time, so it can stay on inside a timed region).
+/* Kernel timing with one pair of HIP events per softrod_step / softrod_substeps
+ * call, attached to the call's own kernel dispatches (start: begin of its first
+ * kernel; stop: end of its last): no packet in front of or behind the kernels and
+ * no host synchronisation, so a timed launch costs what an untimed one costs and
+ * a duration is the kernels' own, first begin to last end.  Switch it off before
+ * capturing a graph (the events are not part of one).
  *   softrod_set_timing(h, n)      n > 0: keep event pairs for the next n launches
  *                                 (ring restarts at 0); n = 0: off (default).
  *   softrod_kernel_times_ms(...)  synchronises on the recorded events and writes
