@@ -949,6 +949,34 @@ class SoftrodError(RuntimeError):
     pass
 
 
+ROD_SHAPE_FIELDS = ("kappa", "sigma", "velocity", "omega")
+
+
+def rod_shape_field_shape(cfg: "SoftrodConfig", n_envs: int, name: str):
+    """The (n_envs, rods_per_env, 3, width) shape of one field of set_rod_shape (softrod_set_rod_shape): kappa on
+    the n_elem - 1 Voronoi vertices, sigma and omega on the n_elem elements, velocity on the n_elem + 1 nodes."""
+    ne = int(cfg.n_elem)
+    width = {"kappa": ne - 1, "sigma": ne, "velocity": ne + 1, "omega": ne}[name]
+    return (int(n_envs), config_rods_per_env(cfg), 3, width)
+
+
+def rod_shape_check_field(cfg: "SoftrodConfig", n_envs: int, name: str, value) -> None:
+    """Refuse a field of set_rod_shape that softrod_set_rod_shape could not take: ValueError for an array or tensor
+    whose dtype is not float64 or whose shape is not rod_shape_field_shape's (for a one-rod env the rods axis may be
+    left out).  None (all zero) passes; so does a nested sequence of the right shape, which is coerced to float64."""
+    import numpy as np
+
+    if value is None:
+        return
+    want = rod_shape_field_shape(cfg, n_envs, name)
+    dtype = getattr(value, "dtype", None)
+    if dtype is not None and str(dtype).replace("torch.", "") != "float64":
+        raise ValueError(f"set_rod_shape: {name} must be float64, got {dtype}")
+    shape = tuple(value.shape) if hasattr(value, "shape") else np.asarray(value, np.float64).shape
+    if shape != want and not (want[1] == 1 and shape == want[:1] + want[2:]):
+        raise ValueError(f"set_rod_shape: {name} must have shape {want}, got {shape}")
+
+
 def copy_envs_pairs(src, dst):
     """The (src, dst) arguments of copy_envs / fork as two contiguous int32 arrays of one length: array-likes of
     ints (a range, a list, an integer array or tensor), a scalar `src` broadcast over `dst`.  ValueError for anything
@@ -1033,6 +1061,7 @@ _EXPORTS = {
     "softrod_camera_check": (C.c_int, [C.POINTER(SoftrodCamera)]),
     "softrod_render": (C.c_int, [_VP, C.POINTER(SoftrodCamera), _VP, _VP, _VP]),
     "softrod_rod_clearance": (C.c_int, [_VP, C.c_int, _VP, _VP]),
+    "softrod_set_rod_shape": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "softrod_substeps": (C.c_int, [_VP, _VP, C.c_int, _VP]),
     "softrod_state_view_get": (C.c_int, [_VP, C.POINTER(SoftrodStateView)]),
     "softrod_set_timing": (C.c_int, [_VP, C.c_int]),

@@ -183,6 +183,33 @@ class HipRodBackend:
             if tab is not None:
                 tab[d] = tab[s]
 
+    def set_rod_shape(self, mask=None, *, kappa=None, sigma=None, velocity=None, omega=None) -> torch.Tensor:
+        """softrod_set_rod_shape: rebuild every rod of the envs with mask != 0 (None: all) from its base pose and the
+        strain fields, in rod_strains()' conventions (include/softrod.h) — kappa (n_envs, rods_per_env, 3, n_elem - 1),
+        sigma (.., 3, n_elem), velocity (.., 3, n_elem + 1), omega (.., 3, n_elem), float64; None: all zero.  A float64
+        torch tensor on this device is used in place; anything else is coerced once, as step()'s actions are.  One
+        kernel on the current stream and one observe(None): -> the new observations (`obs`).  Between a reset and the
+        first step only; the env layer checks that, this method does not."""
+        ptrs, keep = [], []
+        for name, v in zip(_capi.ROD_SHAPE_FIELDS, (kappa, sigma, velocity, omega)):
+            if v is None:
+                ptrs.append(None)
+                continue
+            shape = _capi.rod_shape_field_shape(self.cfg, self.n_envs, name)
+            t = torch.as_tensor(v, dtype=torch.float64, device=self.device)
+            if t.numel() != int(np.prod(shape)):
+                raise ValueError(f"set_rod_shape: {name} must have shape {shape}, got {tuple(t.shape)}")
+            t = t.reshape(shape).contiguous()
+            keep.append(t)
+            ptrs.append(t.data_ptr())
+        m = None
+        if mask is not None:
+            host = mask.detach().cpu().numpy() if hasattr(mask, "detach") else np.asarray(mask)
+            m = torch.as_tensor(np.ascontiguousarray(host != 0, dtype=np.uint8).reshape(self.n_envs), device=self.device)
+        check(self._lib.softrod_set_rod_shape(self._h, *ptrs, m.data_ptr() if m is not None else None, self._stream()),
+              self._h)
+        return self.observe(None)
+
     def reset(self, theta0: np.ndarray, mask: Optional[np.ndarray] = None) -> None:
         th =np.ascontiguousarray(theta0, dtype=np.float64).reshape(self.n_envs)
         m = None

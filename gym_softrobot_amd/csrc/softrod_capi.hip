@@ -19,6 +19,7 @@
 #include "softrod_kernels.hpp"
 #include "softrod_dynamics_readout.hpp"
 #include "softrod_copy_envs.hpp"
+#include "softrod_shape.hpp"
 
 using namespace softrod;
 
@@ -2223,6 +2224,20 @@ int softrod_rod_clearance(softrod_handle* h, int self_gap, double* out, void* st
     hipLaunchKernelGGL(by_epl(h, softrod_rod_clearance_kernel<1>, softrod_rod_clearance_kernel<2>), dim3((unsigned)waves),
                        dim3(kLanes), 0, (hipStream_t)stream, h->S.pos, h->d_render_radius, env_target(h), c.n_envs, c.n_elem,
                        y.rods, y.lane_stride, y.arm_stride, self_gap, out);
+    SR_HIP(h, hipGetLastError());
+    return SOFTROD_OK;
+}
+
+// ---- softrod_set_rod_shape (softrod_shape.hpp) ----
+int softrod_set_rod_shape(softrod_handle* h, const double* kappa, const double* sigma, const double* velocity,
+                          const double* omega, const uint8_t* mask, void* stream) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "set rod shape: null handle");
+    // every handle's resident rows have rod_layout's form, so there is no refusal list
+    SR_ON_DEVICE(h);
+    const RodLayout y = rod_layout(h);
+    const RodShapeArgs args{kappa, sigma, velocity, omega, mask};
+    hipLaunchKernelGGL(by_epl(h, softrod_rod_shape_kernel<1>, softrod_rod_shape_kernel<2>), dim3((unsigned)(h->cfg.n_envs * y.rods)),
+                       dim3(kLanes), 0, (hipStream_t)stream, h->P, h->S, y.rods, y.lane_stride, y.arm_stride, args);
     SR_HIP(h, hipGetLastError());
     return SOFTROD_OK;
 }

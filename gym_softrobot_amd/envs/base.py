@@ -194,6 +194,14 @@ class SingleRodEnv(GymEnv):
         r = self._vec.rod_clearance(self_gap)
         return type(r)(*(None if t is None else t[0] for t in r))
 
+    def set_rod_shape(self, *, kappa=None, sigma=None, velocity=None, omega=None):
+        """VecRodEnvBase.set_rod_shape of this env, without the env axis: kappa (rods, 3, n_elem - 1), sigma (rods, 3,
+        n_elem), velocity (rods, 3, n_elem + 1), omega (rods, 3, n_elem), float64, the rods axis optional for a one-rod
+        env.  After reset(), before the first step.  -> the new observation."""
+        fields = {k: None if v is None else v[None] if hasattr(v, "shape") else np.asarray(v, np.float64)[None]
+                  for k, v in dict(kappa=kappa, sigma=sigma, velocity=velocity, omega=omega).items()}
+        return self._obs(self._vec.set_rod_shape(None, **fields))
+
     def save_data(self, filename_video, fps):
         """The reference renders `rod_parameters_dict` to a video here (soft_pendulum.py:253-256, flat_env.py:410-420);
         drawing is out of scope: the data is in `rod_parameters_dict`, nothing is written."""
@@ -818,6 +826,55 @@ class VecRodEnvBase:
             raise NotImplementedError(f"rod clearance needs the HIP backend, not {type(be).__name__}")
         r = be.rod_clearance(self_gap)
         return type(r)(*(None if t is None else self._out(t) for t in r))
+
+    # -- initial shapes (exploring starts, curricula, restarts from a recorded pose) ------------
+    def set_rod_shape(self, mask=None, *, kappa=None, sigma=None, velocity=None, omega=None):
+        """Start envs from any strain field instead of upstream's straight rod (its builds call straight_rod only):
+        randomised initial shapes — curled, twisted, pre-stretched arms —, exploring starts, curricula that begin near
+        a goal pose, restarts from a pose recorded with rod_strains().  Called after reset(), before the first step
+        of the envs it writes; `mask`: None (every env) or (N,) booleans.
+
+        Every rod of a masked env keeps its base pose as reset left it (node 0's position, element 0's directors: the
+        boundary-condition targets, head joints and pendulum / moving-base constraints stay consistent) and is rebuilt
+        on the device from the fields, in rod_strains()' own conventions and shapes, float64:
+          kappa     (N, rods_per_env, 3, n_elem - 1)  material frame, not reduced by rest curvature:
+                    Q_{k+1} = exp(-[kappa_k D^]x) Q_k with D^ the rest Voronoi length
+          sigma     (N, rods_per_env, 3, n_elem)      x_{k+1} - x_k = l^ Q_k^T (sigma_k + e3), l^ the rest length
+          velocity  (N, rods_per_env, 3, n_elem + 1)  lab frame, written as given
+          omega     (N, rods_per_env, 3, n_elem)      material frame, written as given
+        A field left None is zero: set_rod_shape() alone rebuilds the straight, unstretched rod at rest along the base
+        director.  For a one-rod env the rods axis may be left out.  A float64 torch tensor on the env's device is
+        used in place; NumPy arrays and sequences are coerced once.  rod_strains() afterwards returns sigma as given
+        and kappa scaled by 1 + acos_shift / 3 (the read-out's own guard: 3.3e-11 relative).
+
+        What reset derives from the shape is derived again: the tangent and kappa rows, OctoArmSingle's
+        prev_kappa_state and prev_com_state.  OctoArmTwo's _prev_kappa moves in the observation, as upstream's
+        get_state moves it: the one observe this call makes is the right number.  Not touched: rest_kappa, muscle
+        activations, suckers, the rigid head, prev_action, the clock, per-env material and contact, the RNG streams,
+        `_steps` and pending resets; unmasked envs stay bitwise as they were.  Values are not validated: a NaN spoils
+        its own rod only.  SoftPendulum-v0 takes any shape, but only a planar one keeps the fast planar path:
+        kappa[:, :, 0] = kappa[:, :, 2] = 0 and sigma[:, :, 1] = 0, kappa[:, :, 1] (about d2) being the in-plane bend;
+        otherwise the 3-D loop steps the rod.
+
+        -> the new observations in reset()'s form (one backend.observe(None)).  Refusals, each before anything is
+        written: ValueError for a masked env that has stepped since its reset (a teleported state has no mid-substep
+        configuration for the read-outs' instant), for a field that is not float64 or has the wrong shape;
+        NotImplementedError with autoreset="device" / "same_step" (staged reset records are straight rods, as for
+        fork()) and on a backend other than the HIP one.  Not offered on the sharded env."""
+        if self.device_autoreset:
+            raise NotImplementedError(f"set_rod_shape() with autoreset='{'same_step' if self.same_step else 'device'}': "
+                                      "staged reset records are straight rods")
+        be = self.backend
+        if not hasattr(be, "set_rod_shape"):
+            raise NotImplementedError(f"set_rod_shape needs the HIP backend, not {type(be).__name__}")
+        sel = _env_mask(mask, self.num_envs)
+        if (self._steps[sel] != 0).any():
+            raise ValueError(f"set_rod_shape: envs {np.nonzero(sel & (self._steps != 0))[0].tolist()} have stepped since "
+                             "their reset; it is a reset-time call")
+        fields = dict(kappa=kappa, sigma=sigma, velocity=velocity, omega=omega)
+        for name, v in fields.items():
+            _capi.rod_shape_check_field(self.cfg, self.num_envs, name, v)
+        return self._out(be.set_rod_shape(None if mask is None else sel, **fields))
 
     # -- per-env material (domain randomisation) ----------------------------------------
     _MATERIAL_KEYS = ("youngs_modulus", "shear_modulus", "density", "damping_constant")

@@ -1070,6 +1070,43 @@ int softrod_render(softrod_handle* h, const softrod_camera* cam, uint8_t* rgb, f
  * "rod clearance: null handle", "rod clearance: null output buffer", "rod clearance: self_gap must be 2 .. 126".    */
 int softrod_rod_clearance(softrod_handle* h, int self_gap, double* out, void* stream);
 
+/* Set rod shape: start resident envs from any strain field, on the device — the write side of softrod_rod_strains.
+ * Upstream has no counterpart: its builds call CosseratRod.straight_rod only (soft_pendulum/build.py:54-61 and the
+ * other build files), so every episode starts from a straight rod.  This is what randomised initial shapes (curled,
+ * twisted, pre-stretched arms), exploring starts, curricula that begin near a goal pose and restarts from a pose
+ * recorded with softrod_rod_strains need.  It is a RESET-TIME call: between a reset and the first step of the envs it
+ * writes (the read-outs' instant reconstructs a mid-substep configuration for time != 0, which a teleported state
+ * does not have; the library does not check this, the Python layer does).
+ * For every env with mask != 0 (mask: device [n_envs] uint8, or NULL: every env) and every rod of it (rods_per_env as
+ * for softrod_rod_energies) ONE cold kernel (csrc/softrod_shape.hpp, one wave per rod) KEEPS THE BASE POSE — node 0's
+ * position and element 0's directors as they stand, so bc_targets, the head joints and the pendulum / moving-base
+ * constraints stay consistent — and rebuilds the rest of the rod from device arrays in softrod_rod_strains' own
+ * conventions, each float64, C-contiguous, or NULL: all zero
+ *   kappa     [n_envs][rods_per_env][3][n_elem - 1]  material frame, NOT reduced by rest curvature:
+ *             Q_{k+1} = exp(-[kappa_k D^]x) Q_k  with Q's rows the directors, [a]x b = a x b and D^ the rest Voronoi
+ *             length — the inverse of what softrod_rod_strains reports, kappa = -log(Q_{k+1} Q_k^T) / D^
+ *   sigma     [n_envs][rods_per_env][3][n_elem]      x_{k+1} - x_k = l^ Q_k^T (sigma_k + e3), l^ the rest length
+ *   velocity  [n_envs][rods_per_env][3][n_elem + 1]  lab frame, written as given
+ *   omega     [n_envs][rods_per_env][3][n_elem]      material frame, written as given
+ * With all four NULL the rod becomes the straight, unstretched rod at rest along the base director d3.
+ * The rotation of every Voronoi vertex is exact (Rodrigues, libm sin / cos; a series below |kappa D^|^2 = 1e-6); the
+ * products along the rod are a wave scan in a fixed order: two calls with the same arguments are bitwise equal.
+ * WHAT FOLLOWS FROM THE SHAPE is derived again with reset's statements: `tangents` (unit, reset's division with
+ * eps_length), `kappa` (what a force evaluation at this state caches), SOFTROD_ENV_ARM_SINGLE's prev_kappa_state
+ * (`env_memory` = row 0 of that kappa) and prev_com_state (`control` rows 0-1).  SOFTROD_ENV_ARM_TWO's prev_kappa
+ * moves in softrod_observe, as upstream's get_state moves it.
+ * WHAT IS NOT TOUCHED: slot 0 of `position` and `director`, the slots past a rod's own (the ghost slots between packed
+ * arms), rest_kappa, the muscle activations, the suckers, the rigid head, prev_action, time, bc_targets,
+ * the per-env material and contact tables, and every array of an env with mask == 0 (bitwise).
+ * Values are not validated: a NaN spoils its own rod only.  A planar SoftPendulum start needs kappa rows 0 and 2 and
+ * sigma row 1 zero (row 1 of kappa, about d2, is the in-plane bend); otherwise the 3-D loop steps the rod.
+ * Asynchronous on `stream`, like softrod_observe: no host synchronisation, no allocation, no upload; capturable.
+ * Scope: every handle softrod_create accepts — every env kind, 2 .. 126 elements, one- and two-slot rows, packed arms.
+ * The staged records of device-side auto-reset are straight rods: a later automatic reset does not repeat the shape.
+ * Error, found before a device is looked for: SOFTROD_EINVAL "set rod shape: null handle".                           */
+int softrod_set_rod_shape(softrod_handle* h, const double* kappa, const double* sigma, const double* velocity,
+                          const double* omega, const uint8_t* mask, void* stream);
+
 /* Run `n` bare PositionVerlet substeps with fixed per-env forcing inputs and no
  * env epilogue (the inner loop of soft_pendulum.py:183-184 alone); `actions`
  * (device [n_envs] float32 or NULL) feeds SOFTROD_FEAT_POINT_FORCE_NODE0_X.
