@@ -8,6 +8,7 @@ terminal observation, `info["final_obs"]`), and a small torch policy acts on the
 host round trip inside the rollout.
 
     python examples/soft_pendulum_3d_ppo.py --num-envs 1024 --updates 30
+    python examples/soft_pendulum_3d_ppo.py --num-envs 1024 --updates 30 --start-shapes 16     # bent starts, every episode
 
 Plain PPO (clipped surrogate, GAE); nothing here is tuned — it is a usage example.
 """
@@ -48,11 +49,25 @@ def main():
     ap.add_argument("--lam", type=float, default=0.95)
     ap.add_argument("--clip", type=float, default=0.2)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--start-shapes", type=int, default=0, metavar="K",
+                    help="train from a pool of K bent start shapes (exploring starts): every episode, the ones the device "
+                         "restarts included, begins from one of them (env.set_reset_shapes)")
     args = ap.parse_args()
 
     torch.manual_seed(args.seed)
     dev = torch.device("cuda", 0)
     env = gsa.make_vec("SoftPendulum3D-v0", args.num_envs, device=0, autoreset="same_step")
+    if args.start_shapes > 0:
+        # K pendulums bent by up to half a radian about a random transverse axis; a field left out (sigma, velocity,
+        # omega) is zero.  The pool lives on the device; which entry a reset draws follows from (seed, env, episode).
+        K, ne, length = args.start_shapes, int(env.cfg.n_elem), float(env.cfg.base_length)
+        g = torch.Generator().manual_seed(args.seed)
+        bend = torch.rand(K, generator=g, dtype=torch.float64) * 0.5 / length
+        axis = torch.rand(K, generator=g, dtype=torch.float64) * 2.0 * torch.pi
+        kappa = torch.zeros((K, 1, 3, ne - 1), dtype=torch.float64)
+        kappa[:, 0, 0] = (bend * axis.cos())[:, None]
+        kappa[:, 0, 1] = (bend * axis.sin())[:, None]
+        env.set_reset_shapes(kappa=kappa, seed=args.seed)
     N, T = args.num_envs, args.horizon
     od, ad = env.obs_dim, env.action_dim
     lo, hi = env.action_low, env.action_high

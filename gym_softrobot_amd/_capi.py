@@ -977,6 +977,61 @@ def rod_shape_check_field(cfg: "SoftrodConfig", n_envs: int, name: str, value) -
         raise ValueError(f"set_rod_shape: {name} must have shape {want}, got {shape}")
 
 
+def reset_shape_index(seed, env, episode, count):
+    """The pool entry env `env`'s reset number `episode` starts from under set_reset_shapes(..., seed=seed) with `count`
+    entries: softrod_reset_shape_index (include/softrod.h) restated in NumPy, uint64 arithmetic mod 2^64 —
+        mix(x): x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31
+        index = mix(mix(seed + 0x9E3779B97F4A7C15 * (env + 1)) + episode) % count
+    The arguments broadcast against each other; -> an int64 array of that shape (an int for scalars)."""
+    import numpy as np
+
+    def mix(x):
+        x = x ^ (x >> np.uint64(30))
+        x = x * np.uint64(0xBF58476D1CE4E5B9)
+        x = x ^ (x >> np.uint64(27))
+        x = x * np.uint64(0x94D049BB133111EB)
+        return x ^ (x >> np.uint64(31))
+
+    def u64(v):
+        a = np.asarray(v)
+        if a.dtype.kind in "iu":
+            return np.atleast_1d(a).astype(np.uint64)        # (negative ints wrap, as a C cast does)
+        return np.array([int(i) % 2**64 for i in a.reshape(-1)], np.uint64).reshape(np.atleast_1d(a).shape)
+
+    scalar = all(np.ndim(v) == 0 for v in (seed, env, episode, count))
+    s, e, j, k = (u64(v) for v in (seed, env, episode, count))
+    with np.errstate(over="ignore"):
+        a = mix(s + np.uint64(0x9E3779B97F4A7C15) * (e + np.uint64(1)))
+        out = (mix(a + j) % k).astype(np.int64)
+    return int(out[0]) if scalar else out
+
+
+def reset_shapes_pool(cfg: "SoftrodConfig", fields: dict):
+    """Check the fields of set_reset_shapes and find the pool size K.  Each given field must be float64 where it has a
+    dtype and have shape (K, rods_per_env, 3, width) with rod_shape_field_shape's width (for a one-rod env the rods axis
+    may be left out), K >= 1 the same for all: ValueError otherwise, worded like set_rod_shape's.  -> K, or 0 when no
+    field is given (the call that clears the pool)."""
+    import numpy as np
+
+    count = 0
+    for name in ROD_SHAPE_FIELDS:
+        value = fields.get(name)
+        if value is None:
+            continue
+        tail = rod_shape_field_shape(cfg, 0, name)[1:]
+        dtype = getattr(value, "dtype", None)
+        if dtype is not None and str(dtype).replace("torch.", "") != "float64":
+            raise ValueError(f"set_reset_shapes: {name} must be float64, got {dtype}")
+        shape = tuple(value.shape) if hasattr(value, "shape") else np.asarray(value, np.float64).shape
+        ok = len(shape) >= 1 and shape[0] >= 1 and (shape[1:] == tail or (tail[0] == 1 and shape[1:] == tail[1:]))
+        if not ok:
+            raise ValueError(f"set_reset_shapes: {name} must have shape {('K',) + tail}, got {shape}")
+        if count and shape[0] != count:
+            raise ValueError(f"set_reset_shapes: {name} has {shape[0]} pool entries, the fields before it {count}")
+        count = int(shape[0])
+    return count
+
+
 def copy_envs_pairs(src, dst):
     """The (src, dst) arguments of copy_envs / fork as two contiguous int32 arrays of one length: array-likes of
     ints (a range, a list, an integer array or tensor), a scalar `src` broadcast over `dst`.  ValueError for anything
@@ -1062,6 +1117,10 @@ _EXPORTS = {
     "softrod_render": (C.c_int, [_VP, C.POINTER(SoftrodCamera), _VP, _VP, _VP]),
     "softrod_rod_clearance": (C.c_int, [_VP, C.c_int, _VP, _VP]),
     "softrod_set_rod_shape": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "softrod_set_reset_shapes": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP, C.c_uint64, _VP]),
+    "softrod_apply_reset_shapes": (C.c_int, [_VP, _VP, _VP]),
+    "softrod_reset_shapes_view": (C.c_int, [_VP, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "softrod_reset_shape_index": (C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]),
     "softrod_substeps": (C.c_int, [_VP, _VP, C.c_int, _VP]),
     "softrod_state_view_get": (C.c_int, [_VP, C.POINTER(SoftrodStateView)]),
     "softrod_set_timing": (C.c_int, [_VP, C.c_int]),

@@ -210,6 +210,63 @@ class HipRodBackend:
               self._h)
         return self.observe(None)
 
+    # -- shaped starts under every reset (softrod_set_reset_shapes) -------------------------------
+    reset_shapes_count = 0      # entries of the pool; 0: none set
+
+    def set_reset_shapes(self, *, kappa=None, sigma=None, velocity=None, omega=None, seed: int = 0) -> int:
+        """softrod_set_reset_shapes: a resident pool of K start shapes, the fields of set_rod_shape with the pool axis
+        in place of the env axis — kappa (K, rods_per_env, 3, n_elem - 1), sigma (.., 3, n_elem), velocity
+        (.., 3, n_elem + 1), omega (.., 3, n_elem), float64; None: all zero; every given field the same K.  The library
+        copies them into buffers of its own in this call.  No field at all clears the pool.  While a pool is set every
+        reset of an env — apply_reset_shapes after a reset by hand, the device auto-reset passes on their own — starts
+        it from entry _capi.reset_shape_index(seed, env, reset_shape_episode[env], K).  A call sets reset_shape_index
+        to -1 and reset_shape_episode to 0 for every env and shapes nothing itself.  -> K.  A captured graph must be
+        captured again after the call."""
+        fields = dict(zip(_capi.ROD_SHAPE_FIELDS, (kappa, sigma, velocity, omega)))
+        count = _capi.reset_shapes_pool(self.cfg, fields)
+        ptrs, keep = [], []
+        for name in _capi.ROD_SHAPE_FIELDS:
+            v = fields[name]
+            if v is None:
+                ptrs.append(None)
+                continue
+            shape = (count,) + _capi.rod_shape_field_shape(self.cfg, 0, name)[1:]
+            t = torch.as_tensor(v, dtype=torch.float64, device=self.device).reshape(shape).contiguous()
+            keep.append(t)
+            ptrs.append(t.data_ptr())
+        check(self._lib.softrod_set_reset_shapes(self._h, count, *ptrs, int(seed) % 2**64, self._stream()), self._h)
+        self.reset_shapes_count = count
+        if count and getattr(self, "_reset_shape_rows", None) is None:
+            ix, ep = C.c_void_p(), C.c_void_p()
+            check(self._lib.softrod_reset_shapes_view(self._h, C.byref(ix), C.byref(ep)), self._h)
+            self._reset_shape_rows = tuple(torch.as_tensor(_DevArray(p.value, (self.n_envs,), "<i4", self), device=self.device)
+                                           for p in (ix, ep))
+        return count
+
+    def apply_reset_shapes(self, mask=None) -> None:
+        """softrod_apply_reset_shapes: after a reset by hand, shape the envs with mask != 0 (None: all) from their pool
+        entries, record the indices and count the resets.  Two kernels on the current stream; observe afterwards."""
+        m = None
+        if mask is not None:
+            host = mask.detach().cpu().numpy() if hasattr(mask, "detach") else np.asarray(mask)
+            m = torch.as_tensor(np.ascontiguousarray(host != 0, dtype=np.uint8).reshape(self.n_envs), device=self.device)
+        check(self._lib.softrod_apply_reset_shapes(self._h, m.data_ptr() if m is not None else None, self._stream()), self._h)
+
+    def _reset_shape_row(self, i: int) -> torch.Tensor:
+        if not self.reset_shapes_count:
+            raise _capi.SoftrodError("no pool of reset shapes is set (set_reset_shapes)")
+        return self._reset_shape_rows[i]
+
+    @property
+    def reset_shape_index(self) -> torch.Tensor:
+        """(n_envs,) int32 zero-copy view: the pool entry each env's current episode started from, -1: none yet."""
+        return self._reset_shape_row(0)
+
+    @property
+    def reset_shape_episode(self) -> torch.Tensor:
+        """(n_envs,) int32 zero-copy view: resets counted per env = the next reset's ordinal; writable."""
+        return self._reset_shape_row(1)
+
     def reset(self, theta0: np.ndarray, mask: Optional[np.ndarray] = None) -> None:
         th =np.ascontiguousarray(theta0, dtype=np.float64).reshape(self.n_envs)
         m = None
@@ -632,7 +689,9 @@ class HipRodBackend:
     def snapshot(self) -> Dict[str, torch.Tensor]:
         """Host copy of the whole resident batch (every array of softrod_state_view): what
         `restore` needs to put the batch back exactly — checkpoint / resume, or branching a
-        rollout.  The reference has no counterpart (its env state is never serialised)."""
+        rollout.  The reference has no counterpart (its env state is never serialised).  While a pool of reset shapes
+        is set (set_reset_shapes) the snapshot also carries reset_shape_index and reset_shape_episode; the pool itself
+        is NOT part of a snapshot: set it again before restoring into another backend."""
         if getattr(self, "queue_depth", 0):
             raise _capi.SoftrodError("snapshot/restore of a handle with device-side auto-reset is not supported: "
                                      "the pending-reset flags and the staged queue are not part of the state view")
@@ -643,6 +702,9 @@ class HipRodBackend:
             snap["env_material"] = torch.from_numpy(self._env_material.copy())
         if getattr(self, "_env_contact", None) is not None:         # per-env contact (set_env_contact)
             snap["env_contact"] = torch.from_numpy(self._env_contact.copy())
+        if self.reset_shapes_count:        # shaped starts: the two per-env rows; the pool itself is not part of a snapshot
+            snap["reset_shape_index"] = self.reset_shape_index.cpu().clone()
+            snap["reset_shape_episode"] = self.reset_shape_episode.cpu().clone()
         snap["config_fingerprint"] = torch.frombuffer(bytearray(self.config_fingerprint()), dtype=torch.uint8).clone()
         return snap
 
@@ -665,6 +727,10 @@ class HipRodBackend:
             self.set_env_material(snap["env_material"].numpy())
         elif getattr(self, "_env_material", None) is not None:
             self.set_env_material(np.tile(_capi.env_material_defaults(self.cfg), (self.n_envs, 1)))
+        # shaped starts: the rows travel when both sides have a pool (set the pool again before restoring into a fresh backend)
+        if self.reset_shapes_count and "reset_shape_index" in snap:
+            self.reset_shape_index.copy_(snap["reset_shape_index"].to(self.device))
+            self.reset_shape_episode.copy_(snap["reset_shape_episode"].to(self.device))
         # the same for per-env contact
         if "env_contact" in snap:
             self.set_env_contact(snap["env_contact"].numpy())

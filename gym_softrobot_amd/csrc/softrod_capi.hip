@@ -20,6 +20,7 @@
 #include "softrod_dynamics_readout.hpp"
 #include "softrod_copy_envs.hpp"
 #include "softrod_shape.hpp"
+#include "softrod_reset_shapes.hpp"
 
 using namespace softrod;
 
@@ -96,6 +97,14 @@ struct softrod_handle {
     float* d_final_obs = nullptr;   // [N][obs_dim] the finished step's observation
     double* d_final_time = nullptr; // [N] the finished episode's clock
     double* d_final_aux = nullptr;  // [N] the finished step's aux value (SoftPendulum3D's tilt)
+    // shaped starts (softrod_set_reset_shapes): the pool is owned, reallocated by every call that sets one; the three
+    // rows are allocated by the first and kept for the handle's life, so that softrod_reset_shapes_view's pointers stay good
+    int rs_count = 0;               // entries of the pool; 0: none set
+    unsigned long long rs_seed = 0;
+    double* d_rs_field[4] = {nullptr, nullptr, nullptr, nullptr};   // kappa, sigma, velocity, omega [count][rods][3][..] or nullptr
+    int* d_rs_index = nullptr;      // [N] the entry each env's current episode started from, -1: none
+    int* d_rs_episode = nullptr;    // [N] resets counted = the next reset's ordinal
+    uint8_t* d_rs_picked = nullptr; // [N] scratch of the pass: the envs it shapes
     EnvTable<EnvMaterial> env_mat;      // softrod_set_env_material
     EnvTable<EnvContact> env_contact;   // softrod_set_env_contact
     // softrod_copy_envs: the (src, dst) pairs of a call on their way to the device, sized for n_envs pairs at create
@@ -351,6 +360,37 @@ int launch_autoreset_same_step(softrod_handle* h, float* obs, double* aux, int p
     else
         hipLaunchKernelGGL(by_epl(h, softrod_autoreset_same_step_kernel<1>, softrod_autoreset_same_step_kernel<2>), grid, block,
                            0, st, h->P, h->S, obs, aux, pack, h->d_final_obs, h->d_final_time, h->d_final_aux);
+    SR_HIP(h, hipGetLastError());
+    return SOFTROD_OK;
+}
+
+// Shaped starts (softrod_reset_shapes.hpp), only while a pool is set: pick the envs this call restarted (`mode`: by
+// the caller's mask, by the NEXT_STEP pass's skip flag, or by the SAME_STEP pass's flags), shape them from their pool
+// entries with softrod_set_rod_shape's own kernel, and — with `obs` — rewrite their observation rows from the shaped
+// state.  Kernels on `st` only: no synchronisation, no allocation, no upload.
+int launch_reset_shapes(softrod_handle* h, int mode, const uint8_t* mask, float* obs, const uint8_t* term, const uint8_t* trunc,
+                        double* aux, int pack, hipStream_t st) {
+    const int N = h->cfg.n_envs;
+    ResetShapesPick pick{};
+    pick.index = h->d_rs_index; pick.episode = h->d_rs_episode; pick.picked = h->d_rs_picked;
+    pick.seed = h->rs_seed; pick.count = h->rs_count; pick.mode = mode; pick.mask = mask;
+    pick.terminated = pack ? nullptr : term; pick.truncated = pack ? nullptr : trunc;
+    pick.packed = (mode == kPickFinished && pack) ? obs : nullptr;
+    pick.od = softrod_config_obs_dim(&h->cfg);
+    hipLaunchKernelGGL(softrod_reset_shapes_pick_kernel, dim3((unsigned)((N + kPickThreads - 1) / kPickThreads)), dim3(kPickThreads),
+                       0, st, h->P, h->S, pick);
+    const RodLayout y = rod_layout(h);
+    const RodShapeArgs args{h->d_rs_field[0], h->d_rs_field[1], h->d_rs_field[2], h->d_rs_field[3], h->d_rs_picked, h->d_rs_index};
+    hipLaunchKernelGGL(by_epl(h, softrod_rod_shape_kernel<1>, softrod_rod_shape_kernel<2>), dim3((unsigned)(N * y.rods)),
+                       dim3(kLanes), 0, st, h->P, h->S, y.rods, y.lane_stride, y.arm_stride, args);
+    if (obs) {      // the kernel softrod_observe would launch for this handle, for the picked envs
+        if (is_mocto(h) || (is_octo(h) && !is_pull(h)))
+            hipLaunchKernelGGL(softrod_reset_shapes_octo_observe_kernel, dim3((unsigned)N), dim3(kLanes * h->nw), 0, st, h->P, h->S,
+                               h->d_rs_picked, obs, pack);
+        else
+            hipLaunchKernelGGL(by_epl(h, softrod_reset_shapes_observe_kernel<1>, softrod_reset_shapes_observe_kernel<2>),
+                               dim3((unsigned)N), dim3(kLanes), 0, st, h->P, h->S, h->d_rs_picked, obs, aux, pack);
+    }
     SR_HIP(h, hipGetLastError());
     return SOFTROD_OK;
 }
@@ -617,8 +657,12 @@ void launch_stamped(K kernel, const dim3& grid, const dim3& block, hipStream_t s
 int launch_step(softrod_handle* h, const float* actions, float* obs, double* reward,
                 uint8_t* term, uint8_t* trunc, double* aux, int n_sub, int epilogue, int pack,
                 hipStream_t st) {
-    if (h->q_depth > 0 && epilogue && !h->same_step)
+    if (h->q_depth > 0 && epilogue && !h->same_step) {
         if (const int rc = launch_autoreset(h, obs, reward, term, trunc, aux, pack, st)) return rc;
+        // shaped starts for the envs the pass just restarted, in front of the step's first dispatch and its time stamp
+        if (h->rs_count > 0)
+            if (const int rc = launch_reset_shapes(h, kPickSkipped, nullptr, obs, term, trunc, aux, pack, st)) return rc;
+    }
     if ((h->cfg.features & SOFTROD_FEAT_COOMM_MUSCLES) && h->cfg.math_mode == SOFTROD_MATH_FAST) {
         // what the muscle handles need set before they step
         const bool push = h->cfg.env_kind == SOFTROD_ENV_ARM_PUSH || is_pull(h) || is_mocto(h);
@@ -659,8 +703,11 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
     SR_HIP(h, hipGetLastError());
     if (timing) ++h->timed;
     // behind the timing record, so that kernel_times_ms keeps meaning the step (as for the NEXT_STEP pass in front)
-    if (h->q_depth > 0 && epilogue && h->same_step)
+    if (h->q_depth > 0 && epilogue && h->same_step) {
         if (const int rc = launch_autoreset_same_step(h, obs, aux, pack, st)) return rc;
+        if (h->rs_count > 0)      // shaped starts for the envs that pass just restarted
+            if (const int rc = launch_reset_shapes(h, kPickFinished, nullptr, obs, term, trunc, aux, pack, st)) return rc;
+    }
     return SOFTROD_OK;
 }
 
@@ -940,7 +987,9 @@ CopyTable copy_table(const softrod_handle* h) {
     add(S.sucker_idx, SOFTROD_MAX_SUCKERS, per * sizeof(int));
     add(h->env_mat.dev, 1, sizeof(EnvMaterial));
     add(h->env_contact.dev, 1, sizeof(EnvContact));
-    static_assert(kCopyMaxArrays >= 20, "copy_table adds up to 20 arrays");
+    // shaped starts: where the copy's episode started, and its resets' count (fork(copy_rng=False) puts dst's back)
+    add(h->d_rs_index, 1, sizeof(int)); add(h->d_rs_episode, 1, sizeof(int));
+    static_assert(kCopyMaxArrays >= 22, "copy_table adds up to 22 arrays");
     return T;
 }
 
@@ -2235,10 +2284,81 @@ int softrod_set_rod_shape(softrod_handle* h, const double* kappa, const double* 
     // every handle's resident rows have rod_layout's form, so there is no refusal list
     SR_ON_DEVICE(h);
     const RodLayout y = rod_layout(h);
-    const RodShapeArgs args{kappa, sigma, velocity, omega, mask};
+    const RodShapeArgs args{kappa, sigma, velocity, omega, mask, nullptr};
     hipLaunchKernelGGL(by_epl(h, softrod_rod_shape_kernel<1>, softrod_rod_shape_kernel<2>), dim3((unsigned)(h->cfg.n_envs * y.rods)),
                        dim3(kLanes), 0, (hipStream_t)stream, h->P, h->S, y.rods, y.lane_stride, y.arm_stride, args);
     SR_HIP(h, hipGetLastError());
+    return SOFTROD_OK;
+}
+
+// ---- softrod_set_reset_shapes (softrod_reset_shapes.hpp) ----
+uint32_t softrod_reset_shape_index(uint64_t seed, uint32_t env, uint32_t episode, uint32_t count) {
+    return count ? reset_shape_index(seed, env, episode, count) : 0u;
+}
+
+int softrod_set_reset_shapes(softrod_handle* h, int count, const double* kappa, const double* sigma, const double* velocity,
+                             const double* omega, uint64_t seed, void* stream) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "set reset shapes: null handle");
+    if (count < 0) return fail(h, SOFTROD_EINVAL, "set reset shapes: negative count");
+    SR_ON_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t N = (size_t)h->cfg.n_envs;
+    const int n = h->cfg.n_elem;
+    const size_t rows = (size_t)count * (size_t)rod_layout(h).rods * 3;
+    const size_t width[4] = {(size_t)(n - 1), (size_t)n, (size_t)(n + 1), (size_t)n};
+    const double* given[4] = {kappa, sigma, velocity, omega};
+    double* fresh[4] = {nullptr, nullptr, nullptr, nullptr};
+    // the new pool first: a failed call leaves the handle with the pool it had
+    for (int f = 0; f < 4; ++f) {
+        if (!count || !given[f]) continue;
+        const size_t bytes = rows * width[f] * sizeof(double);
+        hipError_t e = hipMalloc((void**)&fresh[f], bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(fresh[f], given[f], bytes, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) {
+            for (double* p : fresh) if (p) (void)hipFree(p);
+            return fail(h, SOFTROD_EHIP, std::string("set reset shapes: ") + hipGetErrorString(e));
+        }
+    }
+    if (count && !h->d_rs_index) {
+        int *ix = nullptr, *ep = nullptr;
+        uint8_t* pk = nullptr;
+        hipError_t e = alloc_owned(h, ix, N * sizeof(int));
+        if (e == hipSuccess) e = alloc_owned(h, ep, N * sizeof(int));
+        if (e == hipSuccess) e = alloc_owned(h, pk, N);
+        if (e != hipSuccess) {      // (what alloc_owned did allocate is released with the handle)
+            for (double* p : fresh) if (p) (void)hipFree(p);
+            return fail(h, SOFTROD_EHIP, std::string("set reset shapes: ") + hipGetErrorString(e));
+        }
+        h->d_rs_index = ix; h->d_rs_episode = ep; h->d_rs_picked = pk;
+    }
+    // a new pool starts a new sequence of starts: no env has a shaped start yet, every ordinal is zero
+    if (h->d_rs_index) {
+        SR_HIP(h, hipMemsetAsync(h->d_rs_index, 0xFF, N * sizeof(int), st));     // -1
+        SR_HIP(h, hipMemsetAsync(h->d_rs_episode, 0, N * sizeof(int), st));
+    }
+    // hipFree waits for the device: kernels still reading the old pool have finished
+    for (int f = 0; f < 4; ++f) {
+        if (h->d_rs_field[f]) (void)hipFree(h->d_rs_field[f]);
+        h->d_rs_field[f] = fresh[f];
+    }
+    h->rs_count = count;
+    h->rs_seed = seed;
+    return SOFTROD_OK;
+}
+
+int softrod_apply_reset_shapes(softrod_handle* h, const uint8_t* mask, void* stream) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "apply reset shapes: null handle");
+    if (!h->rs_count) return fail(h, SOFTROD_EINVAL, "apply reset shapes: no pool is set (softrod_set_reset_shapes)");
+    SR_ON_DEVICE(h);
+    return launch_reset_shapes(h, kPickMask, mask, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
+}
+
+int softrod_reset_shapes_view(softrod_handle* h, int32_t** index, int32_t** episode) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "reset shapes view: null handle");
+    if (!index || !episode) return fail(h, SOFTROD_EINVAL, "reset shapes view: null argument");
+    if (!h->rs_count) return fail(h, SOFTROD_EINVAL, "reset shapes view: no pool is set (softrod_set_reset_shapes)");
+    *index = h->d_rs_index;
+    *episode = h->d_rs_episode;
     return SOFTROD_OK;
 }
 
@@ -2339,6 +2459,7 @@ int softrod_destroy(softrod_handle* h) {
     (void)hipDeviceSynchronize();
     autoreset_release(h);
     for (void* p : h->owned) (void)hipFree(p);
+    for (double* p : h->d_rs_field) if (p) (void)hipFree(p);
     if (h->h_init) (void)hipHostFree(h->h_init);
     h->env_mat.release();
     h->env_contact.release();

@@ -24,6 +24,10 @@
 // (directors), 0..n_elem - 1 (omega, tangents) and Voronoi slots 0..n_elem - 2 (kappa): slot 0 of position and
 // directors, the ghost slots between packed arms and every other array stay as they are.  A NULL field is zero.
 // No LDS, no atomics, no array indexed at run time.  Values are not validated: a NaN spoils its own rod only.
+//
+// The same kernel shapes the starts of softrod_set_reset_shapes (softrod_reset_shapes.hpp): there the fields are a pool
+// with a leading entry axis and RodShapeArgs::pool_index names each env's entry.  Only the row a rod reads differs, so a
+// pool start and softrod_set_rod_shape with that entry's fields run the same statements and give the same bits.
 #pragma once
 
 namespace softrod {
@@ -34,6 +38,8 @@ struct RodShapeArgs {
     const double* velocity;   // [n_envs][rods][3][n_elem + 1] lab frame, or nullptr
     const double* omega;      // [n_envs][rods][3][n_elem] material frame, or nullptr
     const uint8_t* mask;      // [n_envs], or nullptr: every env
+    const int* pool_index;    // [n_envs], or nullptr.  Set (softrod_set_reset_shapes): the four fields are a pool
+                              // [count][rods][3][..] and env e reads entry pool_index[e] of it instead of row e
 };
 
 // C = A B (row-major 3x3; rows of a director matrix are d1, d2, d3)
@@ -77,7 +83,8 @@ softrod_rod_shape_kernel(const RodParams P, const StatePtrs S, const int rods, c
     const int lane = threadIdx.x;
     const int n = P.n_elem;
     const size_t NW = R.N * R.W;
-    const size_t rod = (size_t)R.rod;
+    // the row of the fields this rod reads: its own, or its arm's row of the env's pool entry
+    const size_t rod = A.pool_index ? (size_t)A.pool_index[R.env] * (size_t)rods + (size_t)R.arm : (size_t)R.rod;
 
     // ---- the per-slot factors: the base directors in slot 0, exp([-kappa D^]x) of vertex j - 1 in slot j, identity past the rod
     double M[EPL][9];

@@ -135,6 +135,8 @@ class SingleRodEnv(GymEnv):
         super().reset(seed=seed)
         if self.shares_rng:
             self._vec._rngs[0] = self.np_random
+        if seed is not None and getattr(self._vec, "_reset_shapes", 0):
+            self._vec.backend.reset_shape_episode[0] = 0      # a re-seeded env begins its sequence of starts again
         obs, _ = self._vec.reset(seed=None)
         self._book_reset()
         return self._obs(obs), {}
@@ -201,6 +203,23 @@ class SingleRodEnv(GymEnv):
         fields = {k: None if v is None else v[None] if hasattr(v, "shape") else np.asarray(v, np.float64)[None]
                   for k, v in dict(kappa=kappa, sigma=sigma, velocity=velocity, omega=omega).items()}
         return self._obs(self._vec.set_rod_shape(None, **fields))
+
+    def set_reset_shapes(self, kappa=None, sigma=None, velocity=None, omega=None, *, seed: int = 0) -> None:
+        """VecRodEnvBase.set_reset_shapes of this env: a pool of K start shapes, one of which every later reset() starts
+        from — kappa (K, rods, 3, n_elem - 1), sigma (K, rods, 3, n_elem), velocity (K, rods, 3, n_elem + 1), omega
+        (K, rods, 3, n_elem), float64; the pool axis stays, the rods axis is optional for a one-rod env.  No field: the
+        pool is cleared.  `reset_shape_index` is the entry the current episode started from."""
+        self._vec.set_reset_shapes(kappa, sigma, velocity, omega, seed=seed)
+
+    @property
+    def reset_shape_index(self) -> int:
+        """The pool entry this env's current episode started from; -1: no shaped start yet."""
+        return int(self._vec.reset_shape_index[0])
+
+    @property
+    def reset_shape_episode(self) -> int:
+        """The ordinal of this env's next reset in the sequence of shaped starts."""
+        return int(self._vec.reset_shape_episode[0])
 
     def save_data(self, filename_video, fps):
         """The reference renders `rod_parameters_dict` to a video here (soft_pendulum.py:253-256, flat_env.py:410-420);
@@ -359,6 +378,7 @@ class VecRodEnvBase:
         self._since_top_up = 0
         self._status_in_flight = False
         self.top_up_paused = False     # True: the caller reads the queue counters and stages records itself (tests)
+        self._reset_shapes = 0         # entries of the pool of start shapes (set_reset_shapes); 0: straight starts
         if self.same_step and not hasattr(self.backend, "autoreset_same_step"):
             raise NotImplementedError(f"same-step auto-reset needs the HIP backend, not {type(self.backend).__name__}")
         if self.device_autoreset:
@@ -559,6 +579,8 @@ class VecRodEnvBase:
                     self._popped[i] += 1
             self.backend.queue_advance(by)
         self._reset_backend(m, mask is not None, draws)
+        if self._reset_shapes:
+            self._apply_reset_shapes(m if mask is not None else None, reseeded)
         self._steps[m] = 0
         self._needs_reset[m] = False
         # _prev_action lives with the resident state (softrod_state_view.prev_action): it
@@ -655,6 +677,8 @@ class VecRodEnvBase:
             self.backend.prev_action_rows()[torch.from_numpy(pending)] = saved_prev
             self._seed_rngs(None, pending)
             self._reset_backend(pending, True)
+            if self._reset_shapes:
+                self._apply_reset_shapes(pending)
             self._steps[pending] = 0
             robs = self.backend.observe(None)
             pm = torch.from_numpy(pending).to(robs.device)
@@ -876,6 +900,69 @@ class VecRodEnvBase:
             _capi.rod_shape_check_field(self.cfg, self.num_envs, name, v)
         return self._out(be.set_rod_shape(None if mask is None else sel, **fields))
 
+    def set_reset_shapes(self, kappa=None, sigma=None, velocity=None, omega=None, *, seed: int = 0) -> None:
+        """Shaped episode starts under EVERY reset: a resident pool of K start shapes, one of which each reset of an env
+        starts from — reset() and reset(mask=...), the host-driven autoreset=True, autoreset="device" and "same_step"
+        alike.  Where set_rod_shape() shapes the envs once and is gone at the first episode end, this is what exploring
+        starts, shape randomisation and near-goal curricula need while training in the device modes.  Upstream has no
+        counterpart (its builds call straight_rod only).
+
+        The fields follow set_rod_shape()'s conventions and dtypes with a leading pool axis K >= 1 instead of the env
+        axis: kappa (K, rods_per_env, 3, n_elem - 1), sigma (K, rods, 3, n_elem), velocity (K, rods, 3, n_elem + 1),
+        omega (K, rods, 3, n_elem), float64; the rods axis may be left out for a one-rod env; a field left out is zero;
+        every given field has the same K.  The library copies the pool into device buffers of its own in this call, so
+        the arguments may be released.  A call with no field clears the pool: starts are straight again and the steps
+        launch nothing extra.  For a weighted draw repeat entries.  SoftPendulum-v0 takes any pool, but only planar
+        entries keep the fast planar path (set_rod_shape()'s rule: kappa rows 0 and 2, sigma row 1, velocity row 2 and
+        omega rows 0 and 2 zero); an out-of-plane start is stepped by the 3-D loop until the env's next planar start.
+
+        While a pool is set every reset of an env leaves it exactly as reset followed by set_rod_shape(pool[idx])
+        leaves it, bit for bit, and the observation the resetting call returns for the env is the shaped start's; with
+        autoreset="same_step" final_obs / final_info stay the finished step's.  Which entry does not depend on the
+        mode: idx = gym_softrobot_amd.reset_shape_index(seed, e, j, K) with e the env's index in the batch and j the
+        number of resets env e has had since its RNG stream was last seeded — reset(seed=...) zeroes j for the envs it
+        re-seeds, so a seed reproduces the sequence of starts together with the base poses.  `reset_shape_index` holds
+        each env's current entry (to credit returns to start shapes), `reset_shape_episode` the next j.
+
+        The call shapes nothing itself: envs in mid-episode stay bitwise as they are and the pool takes effect at each
+        env's next reset; it sets reset_shape_index to -1 and reset_shape_episode to 0 for every env.  In the device
+        modes an env that finds no staged reset record did not restart and is neither shaped nor counted.  A graph
+        captured with capture_policy_step must be captured again after set_reset_shapes.  fork() copies
+        reset_shape_index, and reset_shape_episode with copy_rng=True; state_dict() carries both rows but not the pool.
+        set_rod_shape() itself is unchanged, its refusals included.
+
+        ValueError for a field that is not float64, has the wrong shape or another K than the fields before it;
+        NotImplementedError on a backend other than the HIP one.  Not offered on the sharded env."""
+        be = self.backend
+        if not hasattr(be, "set_reset_shapes"):
+            raise NotImplementedError(f"set_reset_shapes needs the HIP backend, not {type(be).__name__}")
+        fields = dict(kappa=kappa, sigma=sigma, velocity=velocity, omega=omega)
+        _capi.reset_shapes_pool(self.cfg, fields)
+        self._reset_shapes = int(be.set_reset_shapes(**fields, seed=int(seed)))
+
+    def _apply_reset_shapes(self, mask: Optional[np.ndarray], reseeded: Optional[np.ndarray] = None) -> None:
+        """Between _reset_backend and the observe of a host-driven reset: the masked envs (None: all) start from their
+        pool entries; the envs the reset re-seeded begin their sequence of starts again."""
+        be = self.backend
+        if reseeded is not None and reseeded.any():
+            be.reset_shape_episode[np.nonzero(reseeded)[0].tolist()] = 0
+        if int(self.cfg.env_kind) == _capi.ENV_ARM_TWO:
+            be.observe(None)     # ArmTwoEnv's get_state moves _prev_kappa: the reset's own observation comes first,
+                                 # as in reset() followed by set_rod_shape() and in the device passes
+        be.apply_reset_shapes(mask)
+
+    @property
+    def reset_shape_index(self):
+        """(N,) int32, zero-copy device row (NumPy copy with numpy_output=True): the pool entry each env's current
+        episode started from; -1 for no shaped start yet.  Needs a pool (set_reset_shapes)."""
+        return self._out(self.backend.reset_shape_index)
+
+    @property
+    def reset_shape_episode(self):
+        """(N,) int32, zero-copy device row (NumPy copy with numpy_output=True): the ordinal j of each env's next reset
+        in its sequence of shaped starts.  Needs a pool (set_reset_shapes)."""
+        return self._out(self.backend.reset_shape_episode)
+
     # -- per-env material (domain randomisation) ----------------------------------------
     _MATERIAL_KEYS = ("youngs_modulus", "shear_modulus", "density", "damping_constant")
 
@@ -1042,8 +1129,8 @@ class VecRodEnvBase:
         same straight line, and the finished observations are in backend.final_obs / final_time.  Results are
         bit-identical to the eager loop (tests/test_gpu_policy_loop.py, tests/test_gpu_same_step.py).
         The kernel arguments (RodParams, array pointers) are baked into the graph BY VALUE at capture: after
-        anything that changes them (a radius profile, an action basis, enabling auto-reset, enabling per-env material or contact)
-        capture again.  Once per-env material is on, later set_material calls update its table in place: replays
+        anything that changes them (a radius profile, an action basis, enabling auto-reset, enabling per-env material or contact,
+        setting or clearing a pool of start shapes with set_reset_shapes) capture again.  Once per-env material is on, later set_material calls update its table in place: replays
         issued on the env's stream see them.  The same holds for per-env contact (set_contact).
         Kernel timing (set_timing) is switched off by the capture and stays off."""
         import torch
@@ -1124,7 +1211,12 @@ class VecRodEnvBase:
         if not hasattr(be, "copy_envs"):
             raise NotImplementedError(f"fork needs the HIP backend, not {type(be).__name__}")
         s, d = _capi.copy_envs_pairs(src, dst)
+        # shaped starts: reset_shape_index is copied; reset_shape_episode belongs to the RNG future, so without
+        # copy_rng dst keeps its own
+        own = be.reset_shape_episode[d.tolist()].clone() if self._reset_shapes and not copy_rng and d.size else None
         be.copy_envs(s, d)
+        if own is not None:
+            be.reset_shape_episode[d.tolist()] = own
         self._steps[d] = self._steps[s]
         self._needs_reset[d] = self._needs_reset[s]
         for k in ("targets", "_traj"):

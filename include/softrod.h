@@ -1102,10 +1102,66 @@ int softrod_rod_clearance(softrod_handle* h, int self_gap, double* out, void* st
  * sigma row 1 zero (row 1 of kappa, about d2, is the in-plane bend); otherwise the 3-D loop steps the rod.
  * Asynchronous on `stream`, like softrod_observe: no host synchronisation, no allocation, no upload; capturable.
  * Scope: every handle softrod_create accepts — every env kind, 2 .. 126 elements, one- and two-slot rows, packed arms.
- * The staged records of device-side auto-reset are straight rods: a later automatic reset does not repeat the shape.
+ * The staged records of device-side auto-reset are straight rods: a later automatic reset does not repeat the shape
+ * of THIS call.  Starts that every reset repeats, automatic ones included, are softrod_set_reset_shapes' (below).
  * Error, found before a device is looked for: SOFTROD_EINVAL "set rod shape: null handle".                           */
 int softrod_set_rod_shape(softrod_handle* h, const double* kappa, const double* sigma, const double* velocity,
                           const double* omega, const uint8_t* mask, void* stream);
+
+/* Reset shapes: shaped episode starts under EVERY reset — by hand, host-driven, NEXT_STEP and SAME_STEP on the device.
+ * Upstream has no counterpart: its builds call CosseratRod.straight_rod only (soft_pendulum/build.py:54-61 and the
+ * other build files), and softrod_set_rod_shape alone stops at the first episode end.  The handle keeps a resident POOL
+ * of `count` start shapes; while one is set, every reset of an env leaves the env exactly as that reset followed by
+ * softrod_set_rod_shape with one entry's fields leaves it, bit for bit (the same kernel shapes both, csrc/softrod_shape.hpp),
+ * and the observation row the resetting call reports is the shaped start's.
+ *
+ * WHICH ENTRY does not depend on the mode: env e's reset number j (j counts from 0) starts from entry
+ *   mix(x):  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31
+ *   index = mix(mix(seed + 0x9E3779B97F4A7C15 * (e + 1)) + j) % count                      all uint64, mod 2^64
+ * softrod_reset_shape_index is this function on the host: no handle, no device (count 0 gives 0).  Known answers:
+ * seed 1, count 3, rows e = 0..5, columns j = 0..2: [[2,1,1],[2,2,1],[2,1,1],[0,2,2],[2,1,2],[1,2,0]].
+ *
+ *   softrod_set_reset_shapes(h, count, kappa, sigma, velocity, omega, seed, stream)
+ *       device pointers in softrod_set_rod_shape's conventions with the entry axis in place of the env axis —
+ *       kappa [count][rods_per_env][3][n_elem - 1], sigma [count][rods_per_env][3][n_elem], velocity
+ *       [count][rods_per_env][3][n_elem + 1], omega [count][rods_per_env][3][n_elem], float64, C-contiguous — or NULL:
+ *       all zero (count > 0 with all four NULL is a pool of straight starts).  The library COPIES them on `stream` into
+ *       buffers it owns, allocated in this call and never inside a step: the caller's arrays may be released once the
+ *       copy has run, and a captured graph sees stable pointers.  A call also sets every env's `index` to -1 and its
+ *       `episode` to 0: a new pool starts a new sequence; it shapes nothing itself, so envs in mid-episode stay as
+ *       they are and the pool takes effect at each env's next reset.  count == 0 clears the pool: starts are straight
+ *       again and the steps launch nothing extra.  The call waits for the device where it releases an earlier pool.
+ *       A graph captured before the call holds the old pool's pointers (or no pass at all): CAPTURE AGAIN after
+ *       softrod_set_reset_shapes, as after softrod_autoreset_same_step.
+ *   softrod_apply_reset_shapes(h, mask, stream)
+ *       for the host-driven reset paths: call it right after softrod_reset* / softrod_reset_octo with the same envs
+ *       (mask: DEVICE [n_envs] uint8, or NULL: every env), before softrod_observe.  For each env of the mask it draws
+ *       index(e, episode[e]), shapes the env's rods from that entry, records the index and increments episode[e].
+ *       Two kernels on `stream`; no synchronisation, allocation or upload; capturable.
+ *   softrod_reset_shapes_view(h, &index, &episode)
+ *       device pointers, valid for the handle's life once a pool has been set: index int32 [n_envs], the entry each
+ *       env's current episode started from (-1: no shaped start yet) — what credits returns to start shapes —, and
+ *       episode int32 [n_envs], the next reset's ordinal j.  The caller may write `episode` (the Python layer zeroes
+ *       it for the envs a reset re-seeds, so that a seed reproduces the starts together with the base poses).
+ *
+ * THE DEVICE MODES need no call: while a pool is set softrod_step / softrod_step_packed launch the same pass for exactly
+ * the envs the call's auto-reset pass restarted — under NEXT_STEP right behind that pass, in front of the step's first
+ * dispatch; under SAME_STEP behind softrod_autoreset_same_step's pass; both outside the step's time stamps, so
+ * softrod_kernel_times_ms keeps meaning the step.  The pass rewrites those envs' observation rows (dense or packed;
+ * SOFTROD_ENV_SOFTPENDULUM3D's aux tilt; SOFTROD_ENV_ARM_TWO's prev_kappa moves as in any get_state); final_obs /
+ * final_time / final_aux stay the finished step's.  An env that found no staged record did not restart: it is neither
+ * shaped nor counted, and is shaped once a record arrives.  A manual reset in a device mode is shaped by
+ * softrod_apply_reset_shapes alone.  Three small kernels per step, none without a pool (csrc/softrod_reset_shapes.hpp).
+ * softrod_copy_envs copies an env's `index` and `episode` with the rest of it.  The pool itself is no part of the state
+ * view.  Errors, each found before a device is looked for (SOFTROD_EINVAL): "set reset shapes: null handle", "set reset
+ * shapes: negative count", "apply reset shapes: null handle", "apply reset shapes: no pool is set
+ * (softrod_set_reset_shapes)", "reset shapes view: null handle", "reset shapes view: null argument", "reset shapes view:
+ * no pool is set (softrod_set_reset_shapes)".                                                                         */
+int softrod_set_reset_shapes(softrod_handle* h, int count, const double* kappa, const double* sigma, const double* velocity,
+                             const double* omega, uint64_t seed, void* stream);
+int softrod_apply_reset_shapes(softrod_handle* h, const uint8_t* mask, void* stream);
+int softrod_reset_shapes_view(softrod_handle* h, int32_t** index, int32_t** episode);
+uint32_t softrod_reset_shape_index(uint64_t seed, uint32_t env, uint32_t episode, uint32_t count);
 
 /* Run `n` bare PositionVerlet substeps with fixed per-env forcing inputs and no
  * env epilogue (the inner loop of soft_pendulum.py:183-184 alone); `actions`
