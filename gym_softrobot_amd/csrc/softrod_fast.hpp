@@ -71,7 +71,12 @@ __device__ __forceinline__ void fma_inplace_u(double& x, double m, double a) {
 //   sinc(2p) = sinc(p) cos(p),  cosc(2p) = sinc(p)^2 / 2,  cos(p) = 1 - cosc(p) p^2.
 // (LEAN = false: plain fma, for the one place — the planar loop's out-of-range tier — where the
 // scalar registers of the literals are not to spare)
-template <bool LEAN = true>
+// ON_CIRCLE (the 3-D rotation): the doubling steps carry the pair's distance from the unit circle,
+// d = sin^2 + cos^2 - 1 = t (sc^2 - 2 cc + cc^2 t), along with its angle error and grow it up to fourfold per step:
+// at 8-10 rad (k = 9) R(a) Q left the orthogonal matrices by 38 ulp where its entries were good to 22.  One
+// first-order correction behind the loop, sin and cos both times 1 - d/2, brings d back to the rounding of its own
+// evaluation (<= 4 ulp); the in-range path is untouched.
+template <bool LEAN = true, bool ON_CIRCLE = false>
 __device__ __forceinline__ void sinc_cosc(double t, double& sc, double& cc) {
     if (!wave_any(t >= 1.0e-3)) {     // the whole wave is in range: straight-line, one s_cbranch
         if constexpr (LEAN) {
@@ -94,6 +99,12 @@ __device__ __forceinline__ void sinc_cosc(double t, double& sc, double& cc) {
         cc = 0.5 * sc * sc;
         sc = sc * c;
         t *= 4.0;
+    }
+    if constexpr (ON_CIRCLE) {
+        const double e = fma(sc, sc, fma(cc * t, cc, -2.0 * cc));      // d / t
+        const double c = fma(-cc, t, 1.0);                             // cos
+        cc = fma(0.5 * e, c, cc);                                      // 1 - cos (1 - d/2), over t
+        sc = fma(-(0.5 * t) * e, sc, sc);
     }
 }
 
@@ -274,7 +285,10 @@ namespace softrod {
 #endif
 
 // ---- kinematic step, per slot ------------------------------------------------------------------
-template <int EPL>
+// ON_CIRCLE: sinc_cosc's correction behind its out-of-range tier.  The rigid-body kernel (softrod_octo.hpp) passes
+// false: it is out of scalar registers, and the correction's code in the loop's cold block moved its allocation —
+// two more spilled scalars reloaded with v_readlane on the IN-RANGE path of every substep (tests/test_codegen.py).
+template <int EPL, bool ON_CIRCLE = true>
 __device__ __forceinline__ void kinematic_n(double h, const ConstN<EPL>& C, LaneN<EPL>& L) {
 #pragma unroll
     for (int s = 0; s < EPL; ++s) {
@@ -286,7 +300,7 @@ __device__ __forceinline__ void kinematic_n(double h, const ConstN<EPL>& C, Lane
         const double a0 = hh * L.w[s][0], a1 = hh * L.w[s][1], a2 = hh * L.w[s][2];
         const double q0 = a0 * a0, q1 = a1 * a1, q2 = a2 * a2;
         double sc, cc;
-        sinc_cosc(q0 + q1 + q2, sc, cc);
+        sinc_cosc<true, ON_CIRCLE>(q0 + q1 + q2, sc, cc);
         const double s0 = sc * a0, s1 = sc * a1, s2 = sc * a2;
         const double ca0 = cc * a0, ca1 = cc * a1;
         const double c01 = ca0 * a1, c02 = ca0 * a2, c12 = ca1 * a2;
@@ -656,12 +670,15 @@ __device__ __forceinline__ void general_substeps(const RodParams& P, const RodPa
     if (has<F>(P, SOFTROD_FEAT_SPLINE_MUSCLE_TORQUES) || slot_local<F>(P, lane * EPL) <= P.n_elem)
 #endif
     {
-        kinematic_n<EPL>(P.half_dt, C, L);
+        // (the planar kernel's out-of-line fallback keeps the uncorrected tier: with the correction the per-env-material
+        // instantiation needed 8 B more scratch than its uniform twin — tests/test_env_material.py holds the two alike)
+        constexpr bool kOnCircle = F == kRuntimeFeatures || (F & ~kFeatEnvMaterial) != SOFTROD_FEATURES_SOFTPENDULUM;
+        kinematic_n<EPL, kOnCircle>(P.half_dt, C, L);
         ProgressPriority prio(n_sub);
         for (int s = 0; s < n_sub; ++s) {
             dynamic_n<F, EPL, TAPER>(Pk, C, B, lane, L);
             const bool last = (s == n_sub - 1);
-            kinematic_n<EPL>(last ? P.half_dt : P.dt, C, L);
+            kinematic_n<EPL, kOnCircle>(last ? P.half_dt : P.dt, C, L);
             prio.tick(s);
         }
     }

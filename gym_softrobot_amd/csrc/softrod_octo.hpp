@@ -501,7 +501,7 @@ softrod_octo_step_kernel(const RodParams P, const StatePtrs S, const float* __re
 #define SOFTROD_OCTO_GHOST_MASK 1
 #endif
     if (n_sub > 0 && !dead && live && (!SOFTROD_OCTO_GHOST_MASK || (arm_ok && r <= n))) {
-        kinematic_n<1>(P.half_dt, C, L);
+        kinematic_n<1, false>(P.half_dt, C, L);
         head_normalize(H);                       // hk = dt/2 and zero loads: the head's first half step
         head_step();
         for (int s = 0; s < n_sub; ++s) {
@@ -509,7 +509,7 @@ softrod_octo_step_kernel(const RodParams P, const StatePtrs S, const float* __re
             dynamic_n<F, 1, kMusclesCompiled<F>>(Pk, C, B, tid, L, joints, es);
             const bool last = (s == n_sub - 1);
             const double h = last ? P.half_dt : P.dt;
-            kinematic_n<1>(h, C, L);
+            kinematic_n<1, false>(h, C, L);
             exchange();
             hk = h;
             head_step();
