@@ -7,9 +7,9 @@
 // observation in its obs row when the call returns.  reward / terminated / truncated stay the finished step's own;
 // `skip` is never set, so the next call steps the fresh episode with that call's action and no env ever idles.
 //
-// Cold path: the reset, the observation and the queue arithmetic are the NEXT_STEP passes' own (reset_rod,
-// octo_reset_env, env_observe_n, octo_write_obs, mocto_write_obs, push_get_state_n), so both modes, a manual masked
-// reset and the host-driven mode give the same bits.  The new buffers are kernel arguments: StatePtrs and RodParams
+// Cold path: the queue arithmetic, the reset and the observation are the calls the NEXT_STEP passes make
+// (staged_record, record_target, reset_rod + observe_rod, octo_reset_env + observe_body), so both modes, a manual
+// masked reset and the host-driven mode give the same bits.  The new buffers are kernel arguments: StatePtrs and RodParams
 // keep their fields, and no step kernel knows this mode exists.
 //
 // An env that finds no staged record stays finished: its obs row keeps the final observation (final_obs holds the
@@ -40,31 +40,16 @@ softrod_autoreset_same_step_kernel(const RodParams P, const StatePtrs S, float* 
         if (tilt) final_aux[rod] = aux[rod];
     }
     const int k = S.q_consumed[rod];
-    if (k >= S.q_produced[rod]) {              // nothing staged: the env stays finished, the host is told
-        if (lane == 0) atomicAdd(S.q_underflow, 1);
-        return;
-    }
+    const double* in = staged_record(S, N, rod, k);
+    if (!in) return;
     __syncthreads();                           // the finished row has been read before any lane overwrites it
-    const double* in = S.queue + ((size_t)(k % S.q_depth) * N + rod) * (size_t)S.q_record;
     LaneN<EPL> L;
     reset_rod<EPL>(P, S, N, rod, lane, in, L); // (clears needs_reset and the clock)
-    EnvAction A;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) A.a[i] = 0.0f;
-    A.force = 0.0;
-    A.mu_set = false;
-    ConstN<EPL> C;
-    const EnvMaterial E = env_material_rt(P, S, rod);
-    if (S.mat) build_const_m<kRuntimeFeatures, EPL, true>(P, E, lane, A, C, S.mat);
-    else build_const_m<kRuntimeFeatures, EPL>(P, E, lane, A, C);
     float pa[7];
 #pragma unroll
-    for (int i = 0; i < 7; ++i) pa[i] = S.prev_action[7 * (size_t)rod + i];
-    env_observe_n<kRuntimeEnv, EPL>(P, S, N, rod, lane, C, L, pa, o);
-    if (lane == 0) {
-        if (tilt) aux[rod] = (double)o[8];
-        S.q_consumed[rod] = k + 1;
-    }
+    for (int i = 0; i < 7; ++i) pa[i] = S.prev_action[7 * (size_t)rod + i];     // (after reset_rod cleared SoftPendulum3D's)
+    observe_rod<EPL>(P, S, N, rod, lane, L, pa, obs, pack, aux);
+    if (lane == 0) S.q_consumed[rod] = k + 1;
 }
 
 // One workgroup of kLanes * nw threads per env: OctoFlat / OctoFlatLite, OctoArmPullWeight and the muscle octopus envs
@@ -79,11 +64,8 @@ softrod_octo_autoreset_same_step_kernel(const RodParams P, const StatePtrs S, fl
     const int nt = blockDim.x;
     const bool finished = S.needs_reset[env] != 0;
     const int k = S.q_consumed[env];
-    const bool staged = k < S.q_produced[env];
     const size_t N = (size_t)P.n_envs;
-    const bool push = is_push_env(P.env_kind);
-    const bool mocto = is_mocto_env(P.env_kind);
-    const int od = push ? env_obs_dim(P) : (mocto ? mocto_obs_dim(P) : octo_obs_dim(P));
+    const int od = body_obs_dim(P);
     float* o = out_row(obs, env, od, pack);
     if (finished) {
         for (int i = tid; i < od; i += nt) final_obs[(size_t)od * env + i] = o[i];
@@ -91,24 +73,15 @@ softrod_octo_autoreset_same_step_kernel(const RodParams P, const StatePtrs S, fl
     }
     __syncthreads();                           // every thread has read needs_reset / q_consumed and its part of the row
     if (!finished) return;
-    if (!staged) {
-        if (tid == 0) atomicAdd(S.q_underflow, 1);
-        return;
-    }
-    const double* in = S.queue + ((size_t)(k % S.q_depth) * N + env) * (size_t)S.q_record;
-    const double tgt[4] = {in[P.n_arm * 18], in[P.n_arm * 18 + 1], mocto ? in[P.n_arm * 18 + 2] : 0.0,
-                           mocto ? in[P.n_arm * 18 + 3] : 0.0};
+    const double* in = staged_record(S, N, env, k);
+    if (!in) return;
+    double tgt[4];
+    record_target(P, in, tgt);
     LaneN<1> L;
     HeadState H;
     octo_reset_env(P, S, env, in, tgt, L, H);
-    if (mocto) {
-        __syncthreads();                       // thread 0's target rows are there (get_state reads them)
-        mocto_write_obs(P, S, env, tid, L.x[0], L.v[0], 0.0, H, o);
-    } else if (push) {
-        float pa[2] = {S.prev_action[7 * (size_t)env], S.prev_action[7 * (size_t)env + 1]};
-        (void)push_get_state_n<1>(P, tid & 63, L, pa, o, false);
-    } else
-        octo_write_obs(P, tid, L, H, tgt, S.prev_action + (size_t)env * (P.n_arm * P.n_action), o);
+    if (is_mocto_env(P.env_kind)) __syncthreads();     // thread 0's target rows are there (get_state reads them)
+    observe_body(P, S, env, tid, L, H, tgt, S.prev_action, obs, pack);
     if (tid == 0) S.q_consumed[env] = k + 1;
 }
 

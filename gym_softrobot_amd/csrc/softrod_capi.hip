@@ -292,6 +292,11 @@ bool is_pull(const softrod_handle* h) { return h->cfg.env_kind == SOFTROD_ENV_AR
 // the muscle octopus envs (softrod_mocto.hpp): FlatEnv's host API (arm frames + target), the muscle arm's tables
 bool mocto_kind(int e) { return e == SOFTROD_ENV_CRAWL || e == SOFTROD_ENV_ARM_TWO || e == SOFTROD_ENV_REACH; }
 bool is_mocto(const softrod_handle* h) { return mocto_kind(h->cfg.env_kind); }
+// Which kernel a cold pass launches: the body one (a workgroup of kLanes * nw threads per env) or the one-rod one (a
+// 64-lane block per env).  Two rules on purpose: the muscle arm with a weight restarts as a body (octo_reset_env resets
+// its weight with it) but observes as the single rod it is (softrod_observe_kernel's push_get_state_n).
+bool restarts_as_body(const softrod_handle* h) { return is_octo(h); }
+bool observes_as_body(const softrod_handle* h) { return is_mocto(h) || (is_octo(h) && !is_pull(h)); }
 // the one- or the two-slot instantiation of a kernel, by the handle's slots per lane
 template <class K> K by_epl(const softrod_handle* h, K one, K two) { return h->epl == 2 ? two : one; }
 // A device buffer whose lifetime is the handle's: allocated, zero-filled and recorded for softrod_destroy.
@@ -341,7 +346,7 @@ void env_contact_row(const double c[8], EnvContact& R) {
 int launch_autoreset(softrod_handle* h, float* obs, double* reward, uint8_t* term, uint8_t* trunc, double* aux, int pack,
                      hipStream_t st) {
     const dim3 grid((unsigned)h->cfg.n_envs), block(kLanes * h->nw);
-    if (is_octo(h))
+    if (restarts_as_body(h))
         hipLaunchKernelGGL(softrod_octo_autoreset_kernel, grid, block, 0, st, h->P, h->S, obs, reward, term, trunc, pack);
     else
         hipLaunchKernelGGL(by_epl(h, softrod_autoreset_kernel<1>, softrod_autoreset_kernel<2>), grid, block, 0, st, h->P, h->S,
@@ -354,7 +359,7 @@ int launch_autoreset(softrod_handle* h, float* obs, double* reward, uint8_t* ter
 // observation and restart within the call
 int launch_autoreset_same_step(softrod_handle* h, float* obs, double* aux, int pack, hipStream_t st) {
     const dim3 grid((unsigned)h->cfg.n_envs), block(kLanes * h->nw);
-    if (is_octo(h))
+    if (restarts_as_body(h))
         hipLaunchKernelGGL(softrod_octo_autoreset_same_step_kernel, grid, block, 0, st, h->P, h->S, obs, pack, h->d_final_obs,
                            h->d_final_time);
     else
@@ -384,12 +389,12 @@ int launch_reset_shapes(softrod_handle* h, int mode, const uint8_t* mask, float*
     hipLaunchKernelGGL(by_epl(h, softrod_rod_shape_kernel<1>, softrod_rod_shape_kernel<2>), dim3((unsigned)(N * y.rods)),
                        dim3(kLanes), 0, st, h->P, h->S, y.rods, y.lane_stride, y.arm_stride, args);
     if (obs) {      // the kernel softrod_observe would launch for this handle, for the picked envs
-        if (is_mocto(h) || (is_octo(h) && !is_pull(h)))
+        if (observes_as_body(h))
             hipLaunchKernelGGL(softrod_reset_shapes_octo_observe_kernel, dim3((unsigned)N), dim3(kLanes * h->nw), 0, st, h->P, h->S,
                                h->d_rs_picked, obs, pack);
         else
-            hipLaunchKernelGGL(by_epl(h, softrod_reset_shapes_observe_kernel<1>, softrod_reset_shapes_observe_kernel<2>),
-                               dim3((unsigned)N), dim3(kLanes), 0, st, h->P, h->S, h->d_rs_picked, obs, aux, pack);
+            hipLaunchKernelGGL(by_epl(h, softrod_observe_kernel<1>, softrod_observe_kernel<2>), dim3((unsigned)N), dim3(kLanes), 0,
+                               st, h->P, h->S, h->d_rs_picked, nullptr, obs, aux, pack);
     }
     SR_HIP(h, hipGetLastError());
     return SOFTROD_OK;
@@ -751,6 +756,34 @@ void straight_init(const softrod_config& c, const double start[3], const double 
     out[13] = t[2] * normal[0] - t[0] * normal[2];
     out[14] = t[0] * normal[1] - t[1] * normal[0];
     for (int i = 0; i < 3; ++i) out[15 + i] = t[i];
+}
+
+// ---- One start record per kind of draw, written once for the masked reset (frames in h_init, the targets in a block
+// of their own behind N * n_arm * 18) and for the staged queue (a record carries its target inline): the callers differ
+// only in where `frames` and `tgt` point and in the index of the draw.
+// SoftPendulum's theta0 -> its frame (build.py:46-52)
+void theta_record(const softrod_handle* h, double th, double* frames) {
+    const double start[3] = {0.0, 0.0, 0.0};
+    const double direction[3] = {1.0 * std::cos(th), 1.0 * std::sin(th), 0.0};
+    const double normal[3] = {1.0 * std::sin(th), -1.0 * std::cos(th), 0.0};
+    straight_init(h->cfg, start, direction, normal, frames);
+}
+// start / direction / normal -> frame.  ArmPullWeightEnv: the one arm's record where the rigid-body reset kernel expects
+// the arms', a zero target behind it (the slot is unused); every other env has no target and `tgt` is not touched
+void straight_record(const softrod_handle* h, const double* start, const double* direction, const double* normal,
+                     double* frames, double* tgt) {
+    straight_init(h->cfg, start, direction, normal, frames);
+    if (is_pull(h)) { tgt[0] = 0.0; tgt[1] = 0.0; }
+}
+// one env's n_arm starts and directions -> its frames (normal e_z: octopus/build.py:82, build_muscle_octopus.py:92) and its
+// target: 2 numbers, or the muscle octopus' 4 (x, y, z and the episode's final_time; 0: the config's)
+size_t octo_target_dim(const softrod_handle* h) { return is_mocto(h) ? 4 : 2; }
+void octo_record(const softrod_handle* h, const double* arm_start, const double* arm_direction, const double* target,
+                 double* frames, double* tgt) {
+    const double normal[3] = {0.0, 0.0, 1.0};
+    for (int a = 0; a < h->cfg.n_arm; ++a)
+        straight_init(h->cfg, arm_start + 3 * a, arm_direction + 3 * a, normal, frames + (size_t)a * 18);
+    for (size_t i = 0; i < octo_target_dim(h); ++i) tgt[i] = target[i];
 }
 
 void config_common(softrod_config* cfg, int n_envs) {
@@ -1376,18 +1409,12 @@ int softrod_reset_octo(softrod_handle* h, const double* arm_start, const double*
     if (!is_flat(h) && !is_mocto(h)) return fail(h, SOFTROD_EINVAL, "softrod_reset_octo is for SOFTROD_ENV_OCTO_FLAT and the muscle octopus envs");
     SR_ON_DEVICE(h);
     SR_HIP(h, hipEventSynchronize(h->ev_reset));
-    const int N = h->cfg.n_envs, na = h->cfg.n_arm;
-    const double normal[3] = {0.0, 0.0, 1.0};             // octopus/build.py:82, build_muscle_octopus.py:92
-    double* tgt = h->h_init + (size_t)N * na * 18;
-    const size_t td = is_mocto(h) ? 4 : 2;                // the muscle octopus: target x, y, z and the episode's final_time (0: the config's)
-    for (int e = 0; e < N; ++e) {
+    const size_t N = (size_t)h->cfg.n_envs, na = (size_t)h->cfg.n_arm, td = octo_target_dim(h);
+    double* tgt = h->h_init + N * na * 18;
+    for (size_t e = 0; e < N; ++e) {
         if (mask) h->h_mask[e] = mask[e];
         if (mask && !mask[e]) continue;
-        for (int a = 0; a < na; ++a) {
-            const size_t k = (size_t)e * na + a;
-            straight_init(h->cfg, arm_start + 3 * k, arm_direction + 3 * k, normal, h->h_init + k * 18);
-        }
-        for (size_t i = 0; i < td; ++i) tgt[td * (size_t)e + i] = target[td * (size_t)e + i];
+        octo_record(h, arm_start + 3 * na * e, arm_direction + 3 * na * e, target + td * e, h->h_init + e * na * 18, tgt + td * e);
     }
     return upload_and_reset(h, (hipStream_t)stream, mask != nullptr);
 }
@@ -1565,13 +1592,8 @@ int softrod_queue_push(softrod_handle* h, const double* theta0, const int32_t* c
     const int rc = queue_begin(h, counts, max_count);
     if (rc != SOFTROD_OK) return rc;
     for (int e = 0; e < h->cfg.n_envs; ++e)
-        for (int j = 0; j < counts[e]; ++j) {
-            const double th = theta0[(size_t)e * max_count + j];
-            const double start[3] = {0.0, 0.0, 0.0};
-            const double direction[3] = {1.0 * std::cos(th), 1.0 * std::sin(th), 0.0};
-            const double normal[3] = {1.0 * std::sin(th), -1.0 * std::cos(th), 0.0};
-            straight_init(h->cfg, start, direction, normal, queue_slot(h, e, h->h_produced[e]++));
-        }
+        for (int j = 0; j < counts[e]; ++j)
+            theta_record(h, theta0[(size_t)e * max_count + j], queue_slot(h, e, h->h_produced[e]++));
     return queue_commit(h, (hipStream_t)stream);
 }
 
@@ -1586,8 +1608,7 @@ int softrod_queue_push_straight(softrod_handle* h, const double* start, const do
         for (int j = 0; j < counts[e]; ++j) {
             const size_t k = ((size_t)e * max_count + j) * 3;
             double* rec = queue_slot(h, e, h->h_produced[e]++);
-            straight_init(h->cfg, start + k, direction + k, normal + k, rec);
-            if (is_pull(h)) { rec[18] = 0.0; rec[19] = 0.0; }      // the rigid-body record's target slot: unused
+            straight_record(h, start + k, direction + k, normal + k, rec, rec + 18);
         }
     return queue_commit(h, (hipStream_t)stream);
 }
@@ -1599,17 +1620,12 @@ int softrod_queue_push_octo(softrod_handle* h, const double* arm_start, const do
     SR_ON_DEVICE(h);
     const int rc = queue_begin(h, counts, max_count);
     if (rc != SOFTROD_OK) return rc;
-    const int na = h->cfg.n_arm;
-    const double normal[3] = {0.0, 0.0, 1.0};
+    const size_t na = (size_t)h->cfg.n_arm, td = octo_target_dim(h);
     for (int e = 0; e < h->cfg.n_envs; ++e)
         for (int j = 0; j < counts[e]; ++j) {
             double* rec = queue_slot(h, e, h->h_produced[e]++);
             const size_t k = (size_t)e * max_count + j;
-            for (int a = 0; a < na; ++a)
-                straight_init(h->cfg, arm_start + (k * na + a) * 3, arm_direction + (k * na + a) * 3, normal,
-                              rec + (size_t)a * 18);
-            const size_t td = is_mocto(h) ? 4 : 2;
-            for (size_t i = 0; i < td; ++i) rec[(size_t)na * 18 + i] = target[td * k + i];
+            octo_record(h, arm_start + 3 * na * k, arm_direction + 3 * na * k, target + td * k, rec, rec + na * 18);
         }
     return queue_commit(h, (hipStream_t)stream);
 }
@@ -1686,12 +1702,7 @@ int softrod_reset(softrod_handle* h, const double* theta0, const uint8_t* mask, 
     for (int e = 0; e < N; ++e) {
         if (mask) h->h_mask[e] = mask[e];
         if (mask && !mask[e]) continue;
-        const double th = theta0[e];
-        // build.py:46-52
-        const double start[3] = {0.0, 0.0, 0.0};
-        const double direction[3] = {1.0 * std::cos(th), 1.0 * std::sin(th), 0.0};
-        const double normal[3] = {1.0 * std::sin(th), -1.0 * std::cos(th), 0.0};
-        straight_init(h->cfg, start, direction, normal, h->h_init + (size_t)e * 18);
+        theta_record(h, theta0[e], h->h_init + (size_t)e * 18);
     }
     return upload_and_reset(h, (hipStream_t)stream, mask != nullptr);
 }
@@ -1703,13 +1714,11 @@ int softrod_reset_straight(softrod_handle* h, const double* start, const double*
     SR_ON_DEVICE(h);
     SR_HIP(h, hipEventSynchronize(h->ev_reset));
     const int N = h->cfg.n_envs;
-    // ArmPullWeightEnv: the one arm's record where the rigid-body reset kernel expects the arms', a zero target behind them
     double* tgt = h->h_init + (size_t)N * 18;
     for (int e = 0; e < N; ++e) {
         if (mask) h->h_mask[e] = mask[e];
         if (mask && !mask[e]) continue;
-        straight_init(h->cfg, start + 3 * e, direction + 3 * e, normal + 3 * e, h->h_init + (size_t)e * 18);
-        if (is_pull(h)) { tgt[2 * (size_t)e] = 0.0; tgt[2 * (size_t)e + 1] = 0.0; }
+        straight_record(h, start + 3 * e, direction + 3 * e, normal + 3 * e, h->h_init + (size_t)e * 18, tgt + 2 * (size_t)e);
     }
     return upload_and_reset(h, (hipStream_t)stream, mask != nullptr);
 }
@@ -2056,12 +2065,12 @@ int softrod_observe(softrod_handle* h, const float* prev_action, float* obs, voi
         if (prev_action) return fail(h, SOFTROD_EINVAL, "the muscle octopus envs observe with their resident prev_action (pass NULL)");
         hipLaunchKernelGGL(softrod_mocto_epilogue_kernel, grid, dim3(kLanes * h->nw), 0, (hipStream_t)stream, h->P, h->S, obs,
                            nullptr, nullptr, nullptr, 0, 0);
-    } else if (is_octo(h) && !is_pull(h))
+    } else if (observes_as_body(h))
         hipLaunchKernelGGL(softrod_octo_observe_kernel, grid, dim3(kLanes * h->nw), 0, (hipStream_t)stream,
                            h->P, h->S, prev_action, obs);
     else
         hipLaunchKernelGGL(by_epl(h, softrod_observe_kernel<1>, softrod_observe_kernel<2>), grid, block, 0,
-                           (hipStream_t)stream, h->P, h->S, prev_action, obs);
+                           (hipStream_t)stream, h->P, h->S, nullptr, prev_action, obs, nullptr, 0);
     SR_HIP(h, hipGetLastError());
     return SOFTROD_OK;
 }

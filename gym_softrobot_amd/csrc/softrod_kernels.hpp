@@ -25,7 +25,10 @@
 // reaction), softrod_strains.hpp (the strains and internal loads), softrod_muscle_readout.hpp (the muscle loads),
 // softrod_joint_readout.hpp (the joint loads), softrod_dynamics_readout.hpp (the rod dynamics);
 // this file holds the state layout, the env prologues/epilogues, the reset /
-// observe / auto-reset kernels and the LIBM kernel.
+// observe / auto-reset kernels and the LIBM kernel.  An episode start is described once, next to reset_rod:
+// no_action_const, observe_rod, unit_tangents and staged_record here, record_target, body_obs_dim and observe_body in
+// softrod_octo.hpp; the reset, observe and NEXT_STEP auto-reset kernels of both files, the SAME_STEP passes
+// (softrod_autoreset.hpp), softrod_shape.hpp and the shaped restarts of softrod_reset_shapes.hpp all call them.
 //
 // Two step kernels share this file's state layout and env prologue/epilogue:
 //   softrod_step_libm_kernel  SOFTROD_MATH_LIBM (EPL = 1): the substep exactly as PyElastica
@@ -1979,32 +1982,87 @@ struct ResetArgs {
     const uint8_t* mask;  // [N] or nullptr
 };
 
+// ---- What an episode start is made of, each decision once: the reset, observe, auto-reset (here, softrod_octo.hpp,
+// softrod_autoreset.hpp), reset-shape and rod-shape passes call these, so every mode gives the same bits by construction.
+
+// A rod's constants with no action applied: what reset and every get_state outside a step are built from.
+template <int EPL>
+__device__ __forceinline__ void no_action_const(const RodParams& P, const StatePtrs& S, int rod, int lane, ConstN<EPL>& C) {
+    EnvAction A;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) A.a[i] = 0.0f;
+    A.force = 0.0;
+    A.mu_set = false;
+    const EnvMaterial E = env_material_rt(P, S, rod);
+    if (S.mat) build_const_m<kRuntimeFeatures, EPL, true>(P, E, lane, A, C, S.mat);
+    else build_const_m<kRuntimeFeatures, EPL>(P, E, lane, A, C);
+}
+
+// One rod's observation from the state in L, no action applied, into its dense or packed row (returned); with `aux`,
+// SoftPendulum3D's tilt follows (lane 0 wrote o[8] itself).  pa: the previous action as the caller loaded it.
+template <int EPL>
+__device__ __forceinline__ float* observe_rod(const RodParams& P, const StatePtrs& S, size_t N, int rod, int lane,
+                                              const LaneN<EPL>& L, const float* pa, float* obs, int pack, double* aux) {
+    ConstN<EPL> C;
+    no_action_const<EPL>(P, S, rod, lane, C);
+    float* o = out_row(obs, rod, env_obs_dim(P), pack);
+    env_observe_n<kRuntimeEnv, EPL>(P, S, N, rod, lane, C, L, pa, o);
+    if (lane == 0 && aux && P.env_kind == SOFTROD_ENV_SOFTPENDULUM3D) aux[rod] = (double)o[8];
+    return o;
+}
+
+// Unit tangents of the nodes x: the difference to the next node over its length + eps_length (the last slot's next
+// node is the next lane's first).
+template <int EPL>
+__device__ __forceinline__ void unit_tangents(const RodParams& P, const double (&x)[EPL][3], double (&t)[EPL][3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double a[EPL], o[EPL];
+#pragma unroll
+        for (int s = 0; s < EPL; ++s) a[s] = x[s][c];
+        shift_next<EPL>(a, o);
+#pragma unroll
+        for (int s = 0; s < EPL; ++s) t[s][c] = o[s] - x[s][c];
+    }
+#pragma unroll
+    for (int s = 0; s < EPL; ++s) {
+        const double len = sqrt(t[s][0] * t[s][0] + t[s][1] * t[s][1] + t[s][2] * t[s][2]) + P.eps_length;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) t[s][c] /= len;
+    }
+}
+
+// The env's next staged reset record k = q_consumed[env] of the ring [depth][N][record], or nullptr with the underflow
+// counted (by thread 0: call it block-uniformly) when nothing is staged.  The caller stores k + 1 once it has restarted.
+__device__ __forceinline__ const double* staged_record(const StatePtrs& S, size_t N, int env, int k) {
+    if (k >= S.q_produced[env]) {          // nothing staged: the env stays finished, the host is told
+        if (threadIdx.x == 0) atomicAdd(S.q_underflow, 1);
+        return nullptr;
+    }
+    return S.queue + ((size_t)(k % S.q_depth) * N + env) * (size_t)S.q_record;
+}
+
+// get_state after reset (or at any time), one 64-lane block per env: the single-rod envs and the muscle arm with a
+// weight.  prev_action: `adim` entries per env as given, or the resident copy.  picked (or nullptr: every env), pack and
+// aux serve the shaped restarts of softrod_reset_shapes.hpp.
 template <int EPL>
 __global__ void __launch_bounds__(kLanes)
-softrod_observe_kernel(const RodParams P, const StatePtrs S, const float* __restrict__ prev_action,
-                            float* __restrict__ obs) {
+softrod_observe_kernel(const RodParams P, const StatePtrs S, const uint8_t* __restrict__ picked,
+                       const float* __restrict__ prev_action, float* __restrict__ obs, double* __restrict__ aux,
+                       const int pack) {
     const int rod = blockIdx.x;
+    if (picked && !picked[rod]) return;          // block-uniform
     const int lane = threadIdx.x;
     const size_t N = (size_t)P.n_envs;
     LaneN<EPL> L;
     load_lane<EPL, kRuntimeFeatures>(S, N, rod, lane, L);
-    EnvAction A;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) A.a[i] = 0.0f;
-    A.force = 0.0;
-    A.mu_set = false;
-    ConstN<EPL> C;
-    const EnvMaterial E = env_material_rt(P, S, rod);
-    if (S.mat) build_const_m<kRuntimeFeatures, EPL, true>(P, E, lane, A, C, S.mat);
-    else build_const_m<kRuntimeFeatures, EPL>(P, E, lane, A, C);
     const int adim = (P.env_kind == SOFTROD_ENV_SOFTPENDULUM3D) ? 2
                    : (P.env_kind == SOFTROD_ENV_ARM_SINGLE) ? 7 : (P.env_kind == SOFTROD_ENV_SOFT_ARM) ? 0
                    : is_push_env(P.env_kind) ? (P.push_mode == 0 ? 1 : 2) : 1;
     float pa[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     for (int i = 0; i < adim; ++i)
         pa[i] = prev_action ? prev_action[adim * (size_t)rod + i] : S.prev_action[7 * (size_t)rod + i];
-    const int od = env_obs_dim(P);
-    env_observe_n<kRuntimeEnv, EPL>(P, S, N, rod, lane, C, L, pa, obs + (size_t)od * rod);
+    observe_rod<EPL>(P, S, N, rod, lane, L, pa, obs, pack, aux);
 }
 
 // One rod's reset from its 18-double record; leaves the fresh state in L as well.
@@ -2026,22 +2084,7 @@ __device__ __forceinline__ void reset_rod(const RodParams& P, const StatePtrs& S
 #pragma unroll
         for (int c = 0; c < 9; ++c) L.Q[s][c] = in[9 + c];
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        double a[EPL], o[EPL];
-#pragma unroll
-        for (int s = 0; s < EPL; ++s) a[s] = L.x[s][c];
-        shift_next<EPL>(a, o);
-#pragma unroll
-        for (int s = 0; s < EPL; ++s) L.t[s][c] = o[s] - L.x[s][c];
-    }
-#pragma unroll
-    for (int s = 0; s < EPL; ++s) {
-        const double len = sqrt(L.t[s][0] * L.t[s][0] + L.t[s][1] * L.t[s][1] + L.t[s][2] * L.t[s][2]) +
-                           P.eps_length;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) L.t[s][c] /= len;
-    }
+    unit_tangents<EPL>(P, L.x, L.t);
     store_lane<EPL, kRuntimeFeatures>(S, N, rod, lane, L);
 #pragma unroll
     for (int s = 0; s < EPL; ++s) {
@@ -2052,14 +2095,8 @@ __device__ __forceinline__ void reset_rod(const RodParams& P, const StatePtrs& S
     }
     double com[2] = {0.0, 0.0};
     if (P.env_kind == SOFTROD_ENV_ARM_SINGLE) {
-        EnvAction A0;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) A0.a[i] = 0.0f;
-        A0.force = 0.0;
         ConstN<EPL> C;
-        const EnvMaterial E = env_material_rt(P, S, rod);
-        if (S.mat) build_const_m<kRuntimeFeatures, EPL, true>(P, E, lane, A0, C, S.mat);
-        else build_const_m<kRuntimeFeatures, EPL>(P, E, lane, A0, C);
+        no_action_const<EPL>(P, S, rod, lane, C);
         com_xy_n<EPL>(P, C, lane, L, com);
     }
     if (P.features & SOFTROD_FEAT_COOMM_MUSCLES) {
@@ -2095,8 +2132,6 @@ __device__ __forceinline__ void reset_rod(const RodParams& P, const StatePtrs& S
         }
     }
 }
-
-
 
 template <int EPL>
 __global__ void __launch_bounds__(kLanes)
@@ -2136,31 +2171,16 @@ softrod_autoreset_kernel(const RodParams P, const StatePtrs S, float* __restrict
     if (!S.needs_reset[rod]) return;
     const size_t N = (size_t)P.n_envs;
     const int k = S.q_consumed[rod];
-    if (k >= S.q_produced[rod]) {          // nothing staged: the env stays finished, the host is told
-        if (lane == 0) atomicAdd(S.q_underflow, 1);
-        return;
-    }
-    const double* in = S.queue + ((size_t)(k % S.q_depth) * N + rod) * (size_t)S.q_record;
+    const double* in = staged_record(S, N, rod, k);
+    if (!in) return;
     LaneN<EPL> L;
     reset_rod<EPL>(P, S, N, rod, lane, in, L);
-    EnvAction A;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) A.a[i] = 0.0f;
-    A.force = 0.0;
-    A.mu_set = false;
-    ConstN<EPL> C;
-    const EnvMaterial E = env_material_rt(P, S, rod);
-    if (S.mat) build_const_m<kRuntimeFeatures, EPL, true>(P, E, lane, A, C, S.mat);
-    else build_const_m<kRuntimeFeatures, EPL>(P, E, lane, A, C);
     float pa[7];
 #pragma unroll
-    for (int i = 0; i < 7; ++i) pa[i] = S.prev_action[7 * (size_t)rod + i];
-    const int od = env_obs_dim(P);
-    float* o = out_row(obs, rod, od, pack);
-    env_observe_n<kRuntimeEnv, EPL>(P, S, N, rod, lane, C, L, pa, o);
+    for (int i = 0; i < 7; ++i) pa[i] = S.prev_action[7 * (size_t)rod + i];     // (after reset_rod cleared SoftPendulum3D's)
+    float* o = observe_rod<EPL>(P, S, N, rod, lane, L, pa, obs, pack, aux);
     if (lane == 0) {
-        emit_scalars(o, od, pack, rod, 0.0, false, false, reward, terminated, truncated, S.needs_reset);
-        if (aux && P.env_kind == SOFTROD_ENV_SOFTPENDULUM3D) aux[rod] = (double)o[8];
+        emit_scalars(o, env_obs_dim(P), pack, rod, 0.0, false, false, reward, terminated, truncated, S.needs_reset);
         S.skip[rod] = 1;
         S.q_consumed[rod] = k + 1;
     }

@@ -594,7 +594,31 @@ softrod_octo_step_kernel(const RodParams P, const StatePtrs S, const float* __re
     octo_write_obs(P, tid, L, H, tgt, actions + (size_t)env * adim, o);
 }
 
-// get_state after reset (or at any time): prev_action = the resident copy unless given.
+// The width of a body's observation row, by the writer observe_body picks
+__device__ __forceinline__ int body_obs_dim(const RodParams& P) {
+    return is_push_env(P.env_kind) ? env_obs_dim(P) : (is_mocto_env(P.env_kind) ? mocto_obs_dim(P) : octo_obs_dim(P));
+}
+
+// One body's observation from the per-thread state in L and the head, into its dense or packed row (returned): get_state of the muscle octopus envs, of the muscle arm with a weight,
+// or FlatEnv's.  prev_action: FlatEnv's, the other two read the resident copy.  After a reset the muscle octopus needs
+// a __syncthreads() between octo_reset_env's target rows and this call: it stays at the call site, in plain view.
+__device__ __forceinline__ float* observe_body(const RodParams& P, const StatePtrs& S, int env, int tid, const LaneN<1>& L,
+                                               const HeadState& H, const double tgt[2],
+                                               const float* __restrict__ prev_action, float* obs, int pack) {
+    float* o = out_row(obs, env, body_obs_dim(P), pack);
+    if (is_mocto_env(P.env_kind))
+        mocto_write_obs(P, S, env, tid, L.x[0], L.v[0], L.kap[0][0], H, o);
+    else if (is_push_env(P.env_kind)) {
+        float pa[2] = {S.prev_action[7 * (size_t)env], S.prev_action[7 * (size_t)env + 1]};
+        (void)push_get_state_n<1>(P, tid & 63, L, pa, o, false);
+    } else
+        octo_write_obs(P, tid, L, H, tgt, prev_action + (size_t)env * (P.n_arm * P.n_action), o);
+    return o;
+}
+
+// get_state after reset (or at any time): prev_action = the resident copy unless given.  OctoFlat / OctoFlatLite only,
+// and octo_write_obs directly: observe_body's other writers would bring the muscle octopus' scratch rows into a
+// kernel that runs without any (measured: 6 us against 16 us per call at 4096 envs).
 __global__ void __launch_bounds__(1024)
 softrod_octo_observe_kernel(const RodParams P, const StatePtrs S, const float* __restrict__ prev_action,
                             float* __restrict__ obs) {
@@ -624,6 +648,15 @@ struct OctoResetArgs {
     const uint8_t* mask;
 };
 
+// The target behind the n_arm frames of a staged record: two numbers, four for the muscle octopus envs (octo_reset_env)
+__device__ __forceinline__ void record_target(const RodParams& P, const double* __restrict__ in, double (&tgt)[4]) {
+    const bool mocto = is_mocto_env(P.env_kind);
+    tgt[0] = in[P.n_arm * 18];
+    tgt[1] = in[P.n_arm * 18 + 1];
+    tgt[2] = mocto ? in[P.n_arm * 18 + 2] : 0.0;
+    tgt[3] = mocto ? in[P.n_arm * 18 + 3] : 0.0;
+}
+
 // One env's reset from its n_arm straight-rod records and its target; the fresh per-lane
 // state is left in L, the head in H.
 __device__ __forceinline__ void octo_reset_env(const RodParams& P, const StatePtrs& S, int env,
@@ -647,15 +680,7 @@ __device__ __forceinline__ void octo_reset_env(const RodParams& P, const StatePt
     }
 #pragma unroll
     for (int c = 0; c < 9; ++c) L.Q[0][c] = in[9 + c];
-    double len2 = 0.0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        L.t[0][c] = from_next(L.x[0][c]) - L.x[0][c];
-        len2 += L.t[0][c] * L.t[0][c];
-    }
-    const double len = sqrt(len2) + P.eps_length;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) L.t[0][c] /= len;
+    unit_tangents<1>(P, L.x, L.t);
     store_lane<1, kRuntimeFeatures>(S, NR, row, lane, L);
     const size_t m = (size_t)row * kLanes + lane;
 #pragma unroll
@@ -727,31 +752,18 @@ softrod_octo_autoreset_kernel(const RodParams P, const StatePtrs S, float* __res
     if (!S.needs_reset[env]) return;
     const size_t N = (size_t)P.n_envs;
     const int k = S.q_consumed[env];
-    if (k >= S.q_produced[env]) {
-        if (tid == 0) atomicAdd(S.q_underflow, 1);
-        return;
-    }
-    const double* in = S.queue + ((size_t)(k % S.q_depth) * N + env) * (size_t)S.q_record;
-    const bool mocto = is_mocto_env(P.env_kind);
-    const double tgt[4] = {in[P.n_arm * 18], in[P.n_arm * 18 + 1], mocto ? in[P.n_arm * 18 + 2] : 0.0,
-                           mocto ? in[P.n_arm * 18 + 3] : 0.0};
+    const double* in = staged_record(S, N, env, k);
+    if (!in) return;
+    double tgt[4];
+    record_target(P, in, tgt);
     LaneN<1> L;
     HeadState H;
     octo_reset_env(P, S, env, in, tgt, L, H);
-    const bool push = is_push_env(P.env_kind);
-    const int od = push ? env_obs_dim(P) : (mocto ? mocto_obs_dim(P) : octo_obs_dim(P));
-    float* o = out_row(obs, env, od, pack);
-    if (mocto) {
-        __syncthreads();                       // thread 0's target rows are there (get_state reads them)
-        mocto_write_obs(P, S, env, tid, L.x[0], L.v[0], 0.0, H, o);
-    } else if (push) {
-        float pa[2] = {S.prev_action[7 * (size_t)env], S.prev_action[7 * (size_t)env + 1]};
-        (void)push_get_state_n<1>(P, tid & 63, L, pa, o, false);
-    } else
-        octo_write_obs(P, tid, L, H, tgt, S.prev_action + (size_t)env * (P.n_arm * P.n_action), o);
+    if (is_mocto_env(P.env_kind)) __syncthreads();     // thread 0's target rows are there (get_state reads them)
+    float* o = observe_body(P, S, env, tid, L, H, tgt, S.prev_action, obs, pack);
     __syncthreads();                           // every thread has read needs_reset / q_consumed
     if (tid == 0) {
-        emit_scalars(o, od, pack, env, 0.0, false, false, reward, terminated, truncated, S.needs_reset);
+        emit_scalars(o, body_obs_dim(P), pack, env, 0.0, false, false, reward, terminated, truncated, S.needs_reset);
         S.skip[env] = 1;
         S.q_consumed[env] = k + 1;
     }

@@ -12,12 +12,13 @@
 //                                        count the reset in episode[e] and mark the env in `picked`
 //   softrod_rod_shape_kernel             softrod_shape.hpp itself, with mask = picked and pool_index = index: the same
 //                                        statements as softrod_set_rod_shape, hence the same bits
-//   softrod_reset_shapes_observe_kernel  (softrod_apply_reset_shapes leaves this one to the caller's softrod_observe)
-//   / _octo_observe_kernel               the picked envs' observation rows again, from the shaped state, with the
-//                                        statements of softrod_observe_kernel / softrod_octo_observe_kernel / the muscle
-//                                        octopus' get_state, into the dense or the packed row; SoftPendulum3D's aux tilt
-//                                        follows as in the auto-reset passes; ArmTwoEnv's _prev_kappa moves as in any
-//                                        get_state
+//   softrod_observe_kernel               (softrod_apply_reset_shapes leaves this one to the caller's softrod_observe)
+//   / softrod_reset_shapes_octo_observe_kernel
+//                                        the picked envs' observation rows again, from the shaped state and the resident
+//                                        prev_action, into the dense or the packed row: softrod_observe's own one-rod
+//                                        kernel with `picked` set (SoftPendulum3D's aux tilt follows as in the auto-reset
+//                                        passes), or observe_body, the auto-reset passes' call, for the envs of several
+//                                        arms (ArmTwoEnv's _prev_kappa moves as in any get_state)
 // WHICH ENVS A CALL RESTARTED is read from what the auto-reset passes leave behind, so no step kernel and no auto-reset
 // kernel changes:
 //   kPickMask      softrod_apply_reset_shapes: the caller's mask (the host-driven reset paths)
@@ -85,43 +86,8 @@ softrod_reset_shapes_pick_kernel(const RodParams P, const StatePtrs S, const Res
     A.episode[e] = j + 1;
 }
 
-// The picked envs' observation rows from the resident state: softrod_observe_kernel's statements (prev_action: the
-// resident copy), into the dense or the packed row.  One 64-lane block per env, the single-rod envs and the muscle arm
-// with a weight, as softrod_observe launches them.
-template <int EPL>
-__global__ void __launch_bounds__(kLanes)
-softrod_reset_shapes_observe_kernel(const RodParams P, const StatePtrs S, const uint8_t* __restrict__ picked,
-                                    float* __restrict__ obs, double* __restrict__ aux, const int pack) {
-    const int rod = blockIdx.x;
-    if (!picked[rod]) return;                    // block-uniform
-    const int lane = threadIdx.x;
-    const size_t N = (size_t)P.n_envs;
-    LaneN<EPL> L;
-    load_lane<EPL, kRuntimeFeatures>(S, N, rod, lane, L);
-    EnvAction A;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) A.a[i] = 0.0f;
-    A.force = 0.0;
-    A.mu_set = false;
-    ConstN<EPL> C;
-    const EnvMaterial E = env_material_rt(P, S, rod);
-    if (S.mat) build_const_m<kRuntimeFeatures, EPL, true>(P, E, lane, A, C, S.mat);
-    else build_const_m<kRuntimeFeatures, EPL>(P, E, lane, A, C);
-    const int adim = (P.env_kind == SOFTROD_ENV_SOFTPENDULUM3D) ? 2
-                   : (P.env_kind == SOFTROD_ENV_ARM_SINGLE) ? 7 : (P.env_kind == SOFTROD_ENV_SOFT_ARM) ? 0
-                   : is_push_env(P.env_kind) ? (P.push_mode == 0 ? 1 : 2) : 1;
-    float pa[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    for (int i = 0; i < adim; ++i) pa[i] = S.prev_action[7 * (size_t)rod + i];
-    const int od = env_obs_dim(P);
-    float* o = out_row(obs, rod, od, pack);
-    env_observe_n<kRuntimeEnv, EPL>(P, S, N, rod, lane, C, L, pa, o);
-    // the tilt the auto-reset passes report for a restarted env (lane 0 wrote o[8] itself)
-    if (lane == 0 && aux && P.env_kind == SOFTROD_ENV_SOFTPENDULUM3D) aux[rod] = (double)o[8];
-}
-
-// The same for the envs of several arms: softrod_octo_observe_kernel's statements (OctoFlat / OctoFlatLite), or
-// get_state of the muscle octopus envs as softrod_mocto_epilogue_kernel runs it without scalars.  One workgroup of
-// kLanes * nw threads per env.
+// The picked envs' observation rows from the resident state, for the envs of several arms (OctoFlat / OctoFlatLite and
+// the muscle octopus envs): one workgroup of kLanes * nw threads per env, as softrod_octo_observe_kernel.
 __global__ void __launch_bounds__(1024)
 softrod_reset_shapes_octo_observe_kernel(const RodParams P, const StatePtrs S, const uint8_t* __restrict__ picked,
                                          float* __restrict__ obs, const int pack) {
@@ -130,22 +96,12 @@ softrod_reset_shapes_octo_observe_kernel(const RodParams P, const StatePtrs S, c
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nw = blockDim.x >> 6;
     const size_t N = (size_t)P.n_envs, NR = N * (size_t)nw;
+    LaneN<1> L;
+    load_lane<1, kRuntimeFeatures>(S, NR, env * nw + wave, lane, L);
     HeadState H;
     double tgt[2];
     load_head(S, N, env, H, tgt);
-    if (is_mocto_env(P.env_kind)) {
-        const size_t m = ((size_t)env * nw + wave) * kLanes + lane;
-        double x[3], v[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { x[c] = S.pos[c * NR * kLanes + m]; v[c] = S.vel[c * NR * kLanes + m]; }
-        const double kap0 = S.kap[m];
-        mocto_write_obs(P, S, env, tid, x, v, kap0, H, out_row(obs, env, mocto_obs_dim(P), pack));
-    } else {
-        LaneN<1> L;
-        load_lane<1, kRuntimeFeatures>(S, NR, env * nw + wave, lane, L);
-        const int adim = P.n_arm * P.n_action;
-        octo_write_obs(P, tid, L, H, tgt, S.prev_action + (size_t)env * adim, out_row(obs, env, octo_obs_dim(P), pack));
-    }
+    observe_body(P, S, env, tid, L, H, tgt, S.prev_action, obs, pack);
 }
 
 }  // namespace softrod

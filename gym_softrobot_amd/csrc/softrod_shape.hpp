@@ -17,9 +17,9 @@
 // apply — seeded with the base directors in slot 0 and the identity in slots past the rod; the nodes are the same
 // scan of 3-vector sums, added to the base node.  The order is fixed: a repeated call is bitwise repeatable.
 //
-// What reset derives from the shape is derived again, with reset's statements: the tangent rows (reset_rod's
-// division with eps_length), the kappa rows (slot_kappa: what a force evaluation at this state caches), OctoArmSingle's
-// prev_com_state in ctrl[0..1] (reset_rod's build_const_m + com_xy_n).  Velocity and omega are written as given.
+// What reset derives from the shape is derived again, by reset's own calls: the tangent rows (unit_tangents), the kappa
+// rows (slot_kappa: what a force evaluation at this state caches), OctoArmSingle's prev_com_state in ctrl[0..1]
+// (no_action_const + com_xy_n).  Velocity and omega are written as given.
 // A wave writes only its own rod's node slots 1..n_elem (position), 0..n_elem (velocity), element slots 1..n_elem - 1
 // (directors), 0..n_elem - 1 (omega, tangents) and Voronoi slots 0..n_elem - 2 (kappa): slot 0 of position and
 // directors, the ghost slots between packed arms and every other array stay as they are.  A NULL field is zero.
@@ -179,23 +179,9 @@ softrod_rod_shape_kernel(const RodParams P, const StatePtrs S, const int rods, c
             }
         }
     }
-    // ---- what reset derives from the shape: tangents (reset_rod's division), kappa (slot_kappa)
+    // ---- what reset derives from the shape: tangents, kappa (slot_kappa)
     double tg[EPL][3], kp[EPL][3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        double a[EPL], o[EPL];
-#pragma unroll
-        for (int s = 0; s < EPL; ++s) a[s] = x[s][c];
-        shift_next<EPL>(a, o);
-#pragma unroll
-        for (int s = 0; s < EPL; ++s) tg[s][c] = o[s] - x[s][c];
-    }
-#pragma unroll
-    for (int s = 0; s < EPL; ++s) {
-        const double len = sqrt(tg[s][0] * tg[s][0] + tg[s][1] * tg[s][1] + tg[s][2] * tg[s][2]) + P.eps_length;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) tg[s][c] /= len;
-    }
+    unit_tangents<EPL>(P, x, tg);
     {
         double Qn[EPL][9];
 #pragma unroll
@@ -251,14 +237,8 @@ softrod_rod_shape_kernel(const RodParams P, const StatePtrs S, const int rods, c
         for (int s = 0; s < EPL; ++s)
 #pragma unroll
             for (int c = 0; c < 3; ++c) L.x[s][c] = x[s][c];
-        EnvAction A0;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) A0.a[i] = 0.0f;
-        A0.force = 0.0;
         ConstN<EPL> C;
-        const EnvMaterial E = env_material_rt(P, S, R.env);
-        if (S.mat) build_const_m<kRuntimeFeatures, EPL, true>(P, E, lane, A0, C, S.mat);
-        else build_const_m<kRuntimeFeatures, EPL>(P, E, lane, A0, C);
+        no_action_const<EPL>(P, S, R.env, lane, C);
         double com[2];
         com_xy_n<EPL>(P, C, lane, L, com);
         if (lane == 0) {
