@@ -1037,17 +1037,30 @@ def copy_envs_pairs(src, dst):
     ints (a range, a list, an integer array or tensor), a scalar `src` broadcast over `dst`.  ValueError for anything
     that is not integers, more than one dimension, or lengths that differ.  Which indices are acceptable is the
     library's to say (softrod_copy_envs)."""
+    return _index_pairs("copy_envs", src, dst, ("src", "dst"))
+
+
+def state_bank_pairs(a, b, names):
+    """copy_envs_pairs for the state bank's calls: bank_save(envs, slots) has names = ("envs", "slots"),
+    bank_load(slots, envs) has ("slots", "envs").  The same coercion — a scalar first argument broadcasts over the
+    second — and the same ValueErrors, under "state_bank:" and these names.  Which indices are acceptable is the
+    library's to say (softrod_bank_save / softrod_bank_load)."""
+    return _index_pairs("state_bank", a, b, names)
+
+
+def _index_pairs(what, first, second, names):
+    """Two index arguments as two contiguous int32 arrays of one length (copy_envs_pairs, state_bank_pairs)."""
     import numpy as np
 
     out = []
-    for name, v in (("src", src), ("dst", dst)):
+    for name, v in zip(names, (first, second)):
         a = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else list(v) if isinstance(v, range) else v)
         if a.size and a.dtype.kind not in "iu":
-            raise ValueError(f"copy_envs: {name} must hold integers, got dtype {a.dtype}")
+            raise ValueError(f"{what}: {name} must hold integers, got dtype {a.dtype}")
         if a.ndim > 1:
-            raise ValueError(f"copy_envs: {name} must be a scalar or one-dimensional, got shape {a.shape}")
+            raise ValueError(f"{what}: {name} must be a scalar or one-dimensional, got shape {a.shape}")
         if a.size and (a.min() < -2**31 or a.max() >= 2**31):
-            raise ValueError(f"copy_envs: {name} does not fit an int32")
+            raise ValueError(f"{what}: {name} does not fit an int32")
         out.append(a.astype(np.int32))
     s, d = out
     if d.ndim == 0:
@@ -1055,7 +1068,7 @@ def copy_envs_pairs(src, dst):
     if s.ndim == 0:
         s = np.full(d.shape, s, np.int32)
     if s.shape != d.shape:
-        raise ValueError(f"copy_envs: src has {s.size} entries, dst has {d.size}")
+        raise ValueError(f"{what}: {names[0]} has {s.size} entries, {names[1]} has {d.size}")
     return np.ascontiguousarray(s), np.ascontiguousarray(d)
 
 
@@ -1112,6 +1125,10 @@ _EXPORTS = {
     "softrod_set_env_material": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_set_env_contact": (C.c_int, [_VP, _VP, _VP, _VP]),
     "softrod_copy_envs": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP]),
+    "softrod_bank_create": (C.c_int, [_VP, C.c_int]),
+    "softrod_bank_save": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP]),
+    "softrod_bank_load": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP]),
+    "softrod_bank_info": (C.c_int, [_VP, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), _VP]),
     "softrod_camera_default": (C.c_int, [C.POINTER(SoftrodConfig), C.POINTER(SoftrodCamera)]),
     "softrod_camera_check": (C.c_int, [C.POINTER(SoftrodCamera)]),
     "softrod_render": (C.c_int, [_VP, C.POINTER(SoftrodCamera), _VP, _VP, _VP]),

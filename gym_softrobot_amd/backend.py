@@ -183,6 +183,51 @@ class HipRodBackend:
             if tab is not None:
                 tab[d] = tab[s]
 
+    # -- the state bank (softrod_bank_create / _save / _load / _info) ---------------------------------
+    def bank_create(self, slots: int) -> None:
+        """softrod_bank_create: `slots` off-batch slots on the device, each holding one complete env state — everything
+        copy_envs copies.  Steps and resets never touch a slot.  Once per backend.  SoftrodError where the library
+        refuses (include/softrod.h): a second bank, slots < 1, a handle with device-side auto-reset, no memory."""
+        check(self._lib.softrod_bank_create(self._h, int(slots)), self._h)
+        # the per-slot mirrors of _env_material / _env_contact: the config's row until a save brings another
+        self._bank_tables = {name: np.tile(getattr(_capi, f"env_{name}_defaults")(self.cfg), (int(slots), 1))
+                             for name in ("material", "contact")}
+
+    def bank_save(self, envs, slots) -> None:
+        """softrod_bank_save: slot slots[i] becomes a bitwise copy of env envs[i], its row of the per-env material /
+        contact tables included.  Array-likes of ints of one length; a scalar `envs` broadcasts over `slots`.  An env
+        may go into several slots, a slot may appear once.  One small upload and one kernel on the current stream, no
+        synchronisation.  Not graph-capturable.  SoftrodError where the library refuses; a refused call changes nothing."""
+        e, s = _capi.state_bank_pairs(envs, slots, ("envs", "slots"))
+        check(self._lib.softrod_bank_save(self._h, e.ctypes.data if e.size else None, s.ctypes.data if s.size else None,
+                                          int(e.size), self._stream()), self._h)
+        for name, rows in getattr(self, "_bank_tables", {}).items():
+            tab = getattr(self, f"_env_{name}", None)
+            if tab is not None:         # no table yet: every env and every slot is at the config's row
+                rows[s] = tab[e]
+
+    def bank_load(self, slots, envs) -> None:
+        """softrod_bank_load: env envs[i] becomes a bitwise copy of slot slots[i].  A scalar `slots` broadcasts over
+        `envs`; a slot may feed many envs, an env may appear once, a slot never saved is refused.  env_material() /
+        env_contact() and a later snapshot() follow the load.  Otherwise as bank_save."""
+        s, e = _capi.state_bank_pairs(slots, envs, ("slots", "envs"))
+        check(self._lib.softrod_bank_load(self._h, s.ctypes.data if s.size else None, e.ctypes.data if e.size else None,
+                                          int(s.size), self._stream()), self._h)
+        for name, rows in getattr(self, "_bank_tables", {}).items():
+            tab = getattr(self, f"_env_{name}", None)
+            if tab is not None:
+                tab[e] = rows[s]
+
+    def bank_info(self) -> Tuple[int, int, np.ndarray]:
+        """softrod_bank_info: (slots, bytes_per_slot, filled) — slots 0 without a bank; bytes_per_slot the device bytes
+        of one env's state, what a save or load moves per pair; filled (slots,) bool, True where a slot holds a state."""
+        slots, nbytes = C.c_int32(0), C.c_uint64(0)
+        check(self._lib.softrod_bank_info(self._h, C.byref(slots), C.byref(nbytes), None), self._h)
+        filled = np.zeros(slots.value, np.uint8)
+        if slots.value:
+            check(self._lib.softrod_bank_info(self._h, C.byref(slots), C.byref(nbytes), filled.ctypes.data), self._h)
+        return int(slots.value), int(nbytes.value), filled.astype(bool)
+
     def set_rod_shape(self, mask=None, *, kappa=None, sigma=None, velocity=None, omega=None) -> torch.Tensor:
         """softrod_set_rod_shape: rebuild every rod of the envs with mask != 0 (None: all) from its base pose and the
         strain fields, in rod_strains()' conventions (include/softrod.h) — kappa (n_envs, rods_per_env, 3, n_elem - 1),

@@ -19,6 +19,7 @@
 #include "softrod_kernels.hpp"
 #include "softrod_dynamics_readout.hpp"
 #include "softrod_copy_envs.hpp"
+#include "softrod_state_bank.hpp"
 #include "softrod_shape.hpp"
 #include "softrod_reset_shapes.hpp"
 
@@ -34,6 +35,32 @@ struct EnvTable {
         (void)hipFree(dev);
         if (host) (void)hipHostFree(host);
         if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
+// The state bank (softrod_bank_create): a twin with `slots` rows of every array copy_table(h) lists, keyed by the
+// batch array it twins, so that the bank's table is the batch's with the bases swapped (bank_table).
+struct StateBank {
+    int slots = 0;                  // 0: the handle has no bank
+    struct Twin { const void* of; unsigned char* dev; };
+    std::vector<Twin> twins;        // `of`: the batch array's base
+    std::vector<uint8_t> filled;    // [slots] the slot holds a saved state
+    std::vector<uint8_t> seen;      // [max(N, slots)] scratch of the validation, all zero between calls
+    std::vector<EnvMaterial> mat;   // [slots] the slot's row of env_mat.host, where that table exists
+    std::vector<EnvContact> contact;    // [slots] the same for env_contact.host
+    int2* d_pairs = nullptr;        // [max(N, slots)] the (from, to) pairs of a call on their way to the device
+    int2* h_pairs = nullptr;        // pinned, the same size
+    hipEvent_t ev_pairs = nullptr;  // guards reuse of h_pairs
+    unsigned char* twin_of(const void* base) const {
+        for (const Twin& t : twins) if (t.of == base) return t.dev;
+        return nullptr;
+    }
+    void release() {
+        for (const Twin& t : twins) (void)hipFree(t.dev);
+        (void)hipFree(d_pairs);
+        if (h_pairs) (void)hipHostFree(h_pairs);
+        if (ev_pairs) (void)hipEventDestroy(ev_pairs);
+        *this = StateBank{};
     }
 };
 
@@ -112,6 +139,7 @@ struct softrod_handle {
     int2* h_pairs = nullptr;        // pinned [N]
     hipEvent_t ev_pairs = nullptr;  // guards reuse of h_pairs
     std::vector<uint8_t> is_dst;    // [N] scratch of its validation, all zero between calls
+    StateBank bank;                 // softrod_bank_create
     std::string err;
 };
 
@@ -613,6 +641,9 @@ StepChoice select_step(const softrod_handle* h, int epilogue = 1, unsigned with 
     return {nullptr, why ? why : "no step kernel is compiled for this handle's feature set, env kind and options"};
 }
 
+template <class Row>
+hipError_t bank_adopt_table(softrod_handle* h, const Row* table, const Row& row);      // the state bank, below
+
 // softrod_set_env_material / softrod_set_env_contact: W doubles per env in, one Row per env on the device.  Refused
 // unless a step kernel honours `option` on this handle; `bad` names what is wrong with an env's values (nullptr: nothing);
 // the first call allocates the table with every row at the config's `own` values; only rows with mask != 0 change.
@@ -635,6 +666,11 @@ int set_env_table(softrod_handle* h, EnvTable<Row>& T, const Row*& slot, unsigne
         Row R0;
         build(own, R0);
         for (size_t i = 0; i < N; ++i) T.host[i] = R0;
+        if (const hipError_t e = bank_adopt_table(h, T.dev, R0)) {     // no twin, no table: copy_table must not list it
+            T.release();
+            T = EnvTable<Row>{};
+            return fail(h, SOFTROD_EHIP, std::string("state bank: ") + hipGetErrorString(e));
+        }
         slot = T.dev;
         SR_HIP(h, hipMemcpy(h->d_state, &h->S, sizeof(StatePtrs), hipMemcpyHostToDevice));
     } else {
@@ -1034,6 +1070,132 @@ hipError_t copy_table_rows(EnvTable<Row>& T, const int2* pairs, int n) {
     if (e != hipSuccess) return e;
     for (int i = 0; i < n; ++i) T.host[pairs[i].y] = T.host[pairs[i].x];
     return hipSuccess;
+}
+
+// ---- the state bank (softrod_state_bank.hpp) ----
+// The bank's side of a batch table: the same arrays in the same order, each at its twin, `slots` rows per component.
+// false: an array of the batch has no twin (every call that creates a per-env array after the bank adopts it: bank_adopt).
+bool bank_table(const StateBank& bank, const CopyTable& batch, CopyTable& out) {
+    out = batch;
+    out.n_envs = bank.slots;
+    for (int k = 0; k < batch.n; ++k)
+        if (!(out.a[k].base = bank.twin_of(batch.a[k].base))) return false;
+    return true;
+}
+
+// Allocate, zeroed, the twin of every array of copy_table(h) that `bank` has none for yet.  A failed call frees what it
+// allocated and leaves `bank` as it was.
+hipError_t bank_adopt(const softrod_handle* h, StateBank& bank) {
+    const CopyTable T = copy_table(h);
+    const size_t had = bank.twins.size();
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < T.n && e == hipSuccess; ++k) {
+        if (bank.twin_of(T.a[k].base)) continue;
+        const size_t bytes = (size_t)T.a[k].comps * (size_t)bank.slots * (size_t)T.a[k].row_bytes;
+        unsigned char* p = nullptr;
+        e = hipMalloc((void**)&p, bytes);
+        if (e == hipSuccess) {
+            bank.twins.push_back({T.a[k].base, p});
+            e = hipMemset(p, 0, bytes);
+        }
+    }
+    if (e != hipSuccess) {
+        for (size_t i = had; i < bank.twins.size(); ++i) (void)hipFree(bank.twins[i].dev);
+        bank.twins.resize(had);
+    }
+    return e;
+}
+
+std::vector<EnvMaterial>& bank_host_rows(StateBank& b, const EnvMaterial*) { return b.mat; }
+std::vector<EnvContact>& bank_host_rows(StateBank& b, const EnvContact*) { return b.contact; }
+
+// A per-env table created after the bank: its twin, with every slot at the row the new table gives an untouched env
+// (`row`), so that a slot saved before the table existed loads as its env would be now.
+template <class Row>
+hipError_t bank_adopt_table(softrod_handle* h, const Row* table, const Row& row) {
+    StateBank& bank = h->bank;
+    if (!bank.slots) return hipSuccess;
+    hipError_t e = bank_adopt(h, bank);
+    if (e != hipSuccess) return e;
+    std::vector<Row>& rows = bank_host_rows(bank, table);
+    rows.assign((size_t)bank.slots, row);
+    return hipMemcpy(bank.twin_of(table), rows.data(), rows.size() * sizeof(Row), hipMemcpyHostToDevice);
+}
+
+// The pinned copy of a per-env table and the bank's host rows follow the device rows, as copy_table_rows does for
+// softrod_copy_envs.  pairs: (env, slot) for a save, (slot, env) for a load.
+template <class Row>
+hipError_t bank_table_rows(StateBank& bank, EnvTable<Row>& T, const int2* pairs, int n, bool load) {
+    if (!T.dev) return hipSuccess;
+    std::vector<Row>& rows = bank_host_rows(bank, T.dev);
+    if (!load) {
+        for (int i = 0; i < n; ++i) rows[pairs[i].y] = T.host[pairs[i].x];
+        return hipSuccess;
+    }
+    const hipError_t e = hipEventSynchronize(T.ev);      // the previous upload has left the staging buffer
+    if (e != hipSuccess) return e;
+    for (int i = 0; i < n; ++i) T.host[pairs[i].y] = rows[pairs[i].x];
+    return hipSuccess;
+}
+
+// Why softrod_bank_save (load = false) or softrod_bank_load (load = true) refuses these arguments (empty: it does not).
+// Host only; leaves bank.seen all zero.  The side written — the slots of a save, the envs of a load — may name an index
+// once; the side read may repeat.
+std::string bank_why_not(softrod_handle* h, const int32_t* envs, const int32_t* slots, int count, bool load) {
+    const std::string what = load ? "bank load: " : "bank save: ";
+    StateBank& bank = h->bank;
+    const int N = h->cfg.n_envs, K = bank.slots;
+    if (!K) return what + "the handle has no state bank (softrod_bank_create)";
+    if (h->q_depth > 0)
+        return what + "not on a handle with device-side auto-reset (the pending-reset flags and the staged queue "
+                      "belong to each env's RNG future)";
+    const int limit = load ? N : K;
+    if (count < 0 || count > limit)
+        return what + "count " + std::to_string(count) + " is outside 0 .. " + (load ? "n_envs = " : "slots = ") + std::to_string(limit);
+    if (count > 0 && (!envs || !slots)) return what + "null envs or slots";
+    for (int i = 0; i < count; ++i) {
+        if (envs[i] < 0 || envs[i] >= N)
+            return what + "env index " + std::to_string(envs[i]) + " (pair " + std::to_string(i) + ") is outside 0 .. " + std::to_string(N - 1);
+        if (slots[i] < 0 || slots[i] >= K)
+            return what + "slot index " + std::to_string(slots[i]) + " (pair " + std::to_string(i) + ") is outside 0 .. " + std::to_string(K - 1);
+    }
+    if (load)
+        for (int i = 0; i < count; ++i)
+            if (!bank.filled[slots[i]]) return what + "slot " + std::to_string(slots[i]) + " holds no state";
+    const int32_t* written = load ? envs : slots;
+    std::string why;
+    for (int i = 0; i < count && why.empty(); ++i) {
+        if (bank.seen[written[i]])
+            why = what + (load ? "env " : "slot ") + std::to_string(written[i]) + " appears twice";
+        bank.seen[written[i]] = 1;
+    }
+    for (int i = 0; i < count; ++i) bank.seen[written[i]] = 0;
+    return why;
+}
+
+// softrod_bank_save / softrod_bank_load behind their validation: the pairs' upload and the one kernel.
+int bank_copy(softrod_handle* h, const int32_t* envs, const int32_t* slots, int count, bool load, void* stream) {
+    const std::string why = bank_why_not(h, envs, slots, count, load);
+    if (!why.empty()) return fail(h, SOFTROD_EINVAL, why);
+    if (count == 0) return SOFTROD_OK;
+    StateBank& bank = h->bank;
+    CopyTable batch = copy_table(h), twin;
+    if (!bank_table(bank, batch, twin))
+        return fail(h, SOFTROD_EINVAL, std::string(load ? "bank load" : "bank save") + ": a per-env array of the handle has no twin in the bank");
+    SR_ON_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    SR_HIP(h, hipEventSynchronize(bank.ev_pairs));     // the previous call's pairs have left the staging buffer
+    for (int i = 0; i < count; ++i) bank.h_pairs[i] = load ? make_int2(slots[i], envs[i]) : make_int2(envs[i], slots[i]);
+    SR_HIP(h, bank_table_rows(bank, h->env_mat, bank.h_pairs, count, load));
+    SR_HIP(h, bank_table_rows(bank, h->env_contact, bank.h_pairs, count, load));
+    SR_HIP(h, hipMemcpyAsync(bank.d_pairs, bank.h_pairs, (size_t)count * sizeof(int2), hipMemcpyHostToDevice, st));
+    SR_HIP(h, hipEventRecord(bank.ev_pairs, st));
+    hipLaunchKernelGGL(softrod_bank_copy_kernel, dim3((unsigned)count), dim3(kCopyThreads), 0, st,
+                       load ? twin : batch, load ? batch : twin, bank.d_pairs);
+    SR_HIP(h, hipGetLastError());
+    if (!load)
+        for (int i = 0; i < count; ++i) bank.filled[slots[i]] = 1;
+    return SOFTROD_OK;
 }
 }  // namespace
 
@@ -2155,6 +2317,63 @@ int softrod_copy_envs(softrod_handle* h, const int32_t* src, const int32_t* dst,
     return SOFTROD_OK;
 }
 
+// ---- the state bank (softrod_state_bank.hpp) ----
+int softrod_bank_create(softrod_handle* h, int slots) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "bank create: null handle");
+    if (h->q_depth > 0)
+        return fail(h, SOFTROD_EINVAL, "bank create: not on a handle with device-side auto-reset (the pending-reset flags and "
+                                       "the staged queue belong to each env's RNG future)");
+    if (h->bank.slots)
+        return fail(h, SOFTROD_EINVAL, "bank create: the handle already has a state bank of " + std::to_string(h->bank.slots) + " slots");
+    if (slots < 1) return fail(h, SOFTROD_EINVAL, "bank create: slots " + std::to_string(slots) + " is not positive");
+    SR_ON_DEVICE(h);
+    StateBank bank;
+    bank.slots = slots;
+    const size_t most = (size_t)(slots > h->cfg.n_envs ? slots : h->cfg.n_envs);
+    hipError_t e = bank_adopt(h, bank);
+    if (e == hipSuccess) e = hipMalloc((void**)&bank.d_pairs, most * sizeof(int2));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&bank.h_pairs, most * sizeof(int2), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&bank.ev_pairs, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        bank.release();
+        return fail(h, e == hipErrorOutOfMemory ? SOFTROD_ENOMEM : SOFTROD_EHIP, std::string("bank create: ") + hipGetErrorString(e));
+    }
+    try {
+        bank.filled.assign((size_t)slots, 0);
+        bank.seen.assign(most, 0);
+        if (h->env_mat.dev) bank.mat.assign((size_t)slots, EnvMaterial{});
+        if (h->env_contact.dev) bank.contact.assign((size_t)slots, EnvContact{});
+    } catch (const std::bad_alloc&) {
+        bank.release();
+        return fail(h, SOFTROD_ENOMEM, "bank create: out of host memory");
+    }
+    h->bank = std::move(bank);
+    return SOFTROD_OK;
+}
+
+int softrod_bank_save(softrod_handle* h, const int32_t* envs, const int32_t* slots, int count, void* stream) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "bank save: null handle");
+    return bank_copy(h, envs, slots, count, false, stream);
+}
+
+int softrod_bank_load(softrod_handle* h, const int32_t* slots, const int32_t* envs, int count, void* stream) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "bank load: null handle");
+    return bank_copy(h, envs, slots, count, true, stream);
+}
+
+int softrod_bank_info(softrod_handle* h, int32_t* slots, uint64_t* bytes_per_slot, uint8_t* filled) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "bank info: null handle");
+    if (!slots || !bytes_per_slot) return fail(h, SOFTROD_EINVAL, "bank info: null argument");
+    const CopyTable T = copy_table(h);
+    uint64_t bytes = 0;
+    for (int k = 0; k < T.n; ++k) bytes += (uint64_t)T.a[k].comps * T.a[k].row_bytes;
+    *slots = h->bank.slots;
+    *bytes_per_slot = bytes;
+    if (filled && h->bank.slots) std::memcpy(filled, h->bank.filled.data(), h->bank.filled.size());
+    return SOFTROD_OK;
+}
+
 namespace {
 // The env's target, where its kind has one: the point softrod_render draws (render.py draws the same) and
 // softrod_rod_clearance measures to.
@@ -2339,11 +2558,21 @@ int softrod_set_reset_shapes(softrod_handle* h, int count, const double* kappa, 
             return fail(h, SOFTROD_EHIP, std::string("set reset shapes: ") + hipGetErrorString(e));
         }
         h->d_rs_index = ix; h->d_rs_episode = ep; h->d_rs_picked = pk;
+        if (h->bank.slots && (e = bank_adopt(h, h->bank)) != hipSuccess) {      // no twins, no rows: copy_table must not list them
+            h->d_rs_index = h->d_rs_episode = nullptr; h->d_rs_picked = nullptr;
+            for (double* p : fresh) if (p) (void)hipFree(p);
+            return fail(h, SOFTROD_EHIP, std::string("set reset shapes: state bank: ") + hipGetErrorString(e));
+        }
     }
     // a new pool starts a new sequence of starts: no env has a shaped start yet, every ordinal is zero
     if (h->d_rs_index) {
         SR_HIP(h, hipMemsetAsync(h->d_rs_index, 0xFF, N * sizeof(int), st));     // -1
         SR_HIP(h, hipMemsetAsync(h->d_rs_episode, 0, N * sizeof(int), st));
+        if (h->bank.slots) {        // and so does every slot: it loads as its env would be now
+            const size_t K = (size_t)h->bank.slots;
+            SR_HIP(h, hipMemsetAsync(h->bank.twin_of(h->d_rs_index), 0xFF, K * sizeof(int), st));
+            SR_HIP(h, hipMemsetAsync(h->bank.twin_of(h->d_rs_episode), 0, K * sizeof(int), st));
+        }
     }
     // hipFree waits for the device: kernels still reading the old pool have finished
     for (int f = 0; f < 4; ++f) {
@@ -2478,6 +2707,7 @@ int softrod_destroy(softrod_handle* h) {
     if (h->ev_reset) (void)hipEventDestroy(h->ev_reset);
     if (h->h_pairs) (void)hipHostFree(h->h_pairs);
     if (h->ev_pairs) (void)hipEventDestroy(h->ev_pairs);
+    h->bank.release();
     delete h;
     return SOFTROD_OK;
 }

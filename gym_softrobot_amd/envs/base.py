@@ -26,6 +26,7 @@ SURVEY.md §8(f) N2:
 """
 from __future__ import annotations
 
+import copy
 from collections import deque
 from typing import Any, Dict, List, Optional, Sequence, Union
 
@@ -220,6 +221,29 @@ class SingleRodEnv(GymEnv):
     def reset_shape_episode(self) -> int:
         """The ordinal of this env's next reset in the sequence of shaped starts."""
         return int(self._vec.reset_shape_episode[0])
+
+    # the host counters the _book_reset / _book_step hooks of the classes keep: saved and loaded with a state
+    booked = ("time", "counter", "tick", "time_tracker", "_prev_action", "final_time")
+
+    def create_state_bank(self, slots: int) -> None:
+        """VecRodEnvBase.create_state_bank of this env: `slots` saved states on the device beside the env, for tree
+        search and any other method that returns to a state it has visited.  Once per env."""
+        self._vec.create_state_bank(slots)
+        self._bank_book = [None] * int(slots)
+
+    def save_state(self, slot: int) -> None:
+        """Keep the env's current state in `slot` (VecRodEnvBase.save_states): the resident state, the host counters
+        and the state of env.np_random where the env's resets draw from it."""
+        self._vec.save_states([0], [slot])
+        self._bank_book[slot] = {k: copy.deepcopy(getattr(self, k)) for k in self.booked if hasattr(self, k)}
+
+    def load_state(self, slot: int, copy_rng: bool = True) -> None:
+        """Return to the state saved in `slot` (VecRodEnvBase.load_states): the same actions then give the same
+        observations, rewards and flags again, bit for bit.  `copy_rng=False`: the env keeps its random stream where
+        it is.  The slot keeps its state; load it as often as needed."""
+        self._vec.load_states([slot], [0], copy_rng=copy_rng)
+        for k, v in self._bank_book[slot].items():
+            setattr(self, k, copy.deepcopy(v))
 
     def save_data(self, filename_video, fps):
         """The reference renders `rod_parameters_dict` to a video here (soft_pendulum.py:253-256, flat_env.py:410-420);
@@ -1234,13 +1258,103 @@ class VecRodEnvBase:
                         self._rngs[j], _ = np_random(0)
                     self._rngs[j].bit_generator.state = self._rngs[i].bit_generator.state
 
+    # -- the state bank: states held beside the batch, loaded into any envs, many times ---------
+    def _state_bank_backend(self, what: str):
+        if self.device_autoreset:
+            raise NotImplementedError(f"{what}() with autoreset='{'same_step' if self.same_step else 'device'}': "
+                                      "staged reset records are not copied")
+        if not hasattr(self.backend, "bank_create"):
+            raise NotImplementedError(f"{what} needs the HIP backend, not {type(self.backend).__name__}")
+        return self.backend
+
+    def create_state_bank(self, slots: int) -> None:
+        """Give this batch a state bank: `slots` off-batch slots on the device, each holding one complete env state —
+        everything fork() copies — that no step and no reset touches.  save_states() fills slots from envs,
+        load_states() makes envs copies of slots, any subset, any number of times: restart distributions over visited
+        states (Go-Explore archives, backplay, demonstration states), branched rollouts from stored states, tree
+        search that returns to a node, a planner that parks its trajectory while all N envs explore.  Where fork()
+        needs a live env per kept state, and snapshot() / restore() move the whole batch through the host.  The
+        reference has no counterpart.  Once per env; `state_bank_bytes` device bytes per slot.
+
+        The bank is no part of state_dict(): a checkpoint carries the batch, not the slots.  NotImplementedError with
+        autoreset="device" / "same_step" (as fork()) and on a backend without bank_create.  Not offered on the
+        sharded env (distributed.py).  softrod_bank_create, include/softrod.h."""
+        self._state_bank_backend("create_state_bank").bank_create(slots)
+        self._bank_book: List[Optional[dict]] = [None] * int(slots)      # the host bookkeeping saved with each slot
+
+    def save_states(self, envs, slots) -> None:
+        """Slot slots[i] becomes an exact copy of env envs[i], now, without leaving the GPU.  Array-likes of indices of
+        one length; a scalar `envs` broadcasts over `slots`.  An env may go into several slots, a slot may appear once;
+        saving into a filled slot replaces what it held.  Saved with the resident state (backend.bank_save:
+        softrod_bank_save) is the host bookkeeping fork() moves: steps since reset, a pending host auto-reset, the
+        reset target (`targets`) and the tracked trajectory where the env has them, and the state of the env's NumPy
+        stream.  SoftrodError for an index outside the batch or the bank, or a slot twice; nothing changes then."""
+        be = self._state_bank_backend("save_states")
+        e, s = _capi.state_bank_pairs(envs, slots, ("envs", "slots"))
+        be.bank_save(e, s)
+        for i, k in zip(e.tolist(), s.tolist()):
+            book = {"steps": int(self._steps[i]), "needs_reset": bool(self._needs_reset[i]),
+                    "rng": None if self._rngs[i] is None else self._rngs[i].bit_generator.state}
+            for name in ("targets", "_traj"):
+                rows = getattr(self, name, None)
+                if rows is not None:
+                    book[name] = np.array(rows[i])
+            self._bank_book[k] = book
+
+    def load_states(self, slots, envs, copy_rng: bool = True) -> None:
+        """Env envs[i] becomes an exact copy of slot slots[i] — of the env that was saved there, as it stood then — and,
+        stepped with the same actions, continues bitwise as that env did.  A scalar `slots` broadcasts over `envs`; a
+        slot may feed many envs, an env may appear once; the slot keeps its state.  The host bookkeeping saved with
+        the slot comes back too (save_states).  With `copy_rng=True` the env also takes the NumPy stream saved with
+        the slot: its next reset draws what the saved env's would have.  With `copy_rng=False` it keeps its own
+        stream and, with a pool of reset shapes, its own `reset_shape_episode`, as fork(copy_rng=False) does.  A
+        per-env material / contact table or a pool of reset shapes set after the save: the slot loads as its env would
+        be now, had nothing touched it since (the config's row; reset_shape_index -1, episode 0).  SoftrodError for an
+        index outside the batch or the bank, an env twice, or a slot that was never saved; nothing changes then."""
+        be = self._state_bank_backend("load_states")
+        s, d = _capi.state_bank_pairs(slots, envs, ("slots", "envs"))
+        own = be.reset_shape_episode[d.tolist()].clone() if self._reset_shapes and not copy_rng and d.size else None
+        be.bank_load(s, d)
+        if own is not None:
+            be.reset_shape_episode[d.tolist()] = own
+        for k, j in zip(s.tolist(), d.tolist()):
+            book = self._bank_book[k]
+            self._steps[j] = book["steps"]
+            self._needs_reset[j] = book["needs_reset"]
+            for name in ("targets", "_traj"):
+                if name in book:
+                    getattr(self, name)[j] = book[name]
+            if copy_rng:
+                if book["rng"] is None:
+                    self._rngs[j] = None
+                else:
+                    if self._rngs[j] is None:
+                        self._rngs[j], _ = np_random(0)
+                    self._rngs[j].bit_generator.state = book["rng"]
+
+    @property
+    def state_bank_slots(self) -> int:
+        """Slots of the state bank; 0 before create_state_bank."""
+        return self.backend.bank_info()[0] if hasattr(self.backend, "bank_info") else 0
+
+    @property
+    def state_bank_filled(self) -> np.ndarray:
+        """(state_bank_slots,) bool: True where a slot holds a saved state."""
+        return self.backend.bank_info()[2] if hasattr(self.backend, "bank_info") else np.zeros(0, bool)
+
+    @property
+    def state_bank_bytes(self) -> int:
+        """Device bytes of one slot: one env's whole resident state, what a save or a load moves per pair."""
+        return self.backend.bank_info()[1] if hasattr(self.backend, "bank_info") else 0
+
     # -- checkpoint / resume ----------------------------------------------------------
     def state_dict(self) -> Dict[str, Any]:
         """Everything needed to continue this batch exactly where it is: the resident state
         (backend.snapshot()) and the host bookkeeping (steps since reset, pending auto-resets,
         every env's RNG state).  The reference never serialises an env; this is
         an addition.  Not available with autoreset="device" (reset records staged on the device
-        belong to the RNG streams' future)."""
+        belong to the RNG streams' future).  The state bank (create_state_bank) is not part of it:
+        the slots' states stay on the device and are not carried by a checkpoint."""
         if self.device_autoreset:
             raise NotImplementedError(f"state_dict() with autoreset='{'same_step' if self.same_step else 'device'}': "
                                       "staged reset records are not captured")

@@ -935,6 +935,64 @@ int softrod_set_env_contact(softrod_handle* h, const double* contact, const uint
  *       result would depend on scheduling; copy in two calls instead).                                            */
 int softrod_copy_envs(softrod_handle* h, const int32_t* src, const int32_t* dst, int count, void* stream);
 
+/* State bank: `slots` off-batch slots on the device, each holding one complete env state — everything
+ * softrod_copy_envs copies — saved from any env and loaded into any env, any number of times.  What restart
+ * distributions over visited states (Go-Explore archives, backplay, resets to demonstration states), branched rollouts
+ * from stored states, tree search that returns to a node, and a planner that parks its controlled trajectory while the
+ * whole batch explores are built on.  Upstream has no counterpart.  Here it replaces the host path backend.snapshot()
+ * -> row surgery -> restore(), two round trips of the whole batch for a change to a few envs, and it frees the live
+ * env that softrod_copy_envs needs to keep a state in: steps and resets never touch a slot.
+ * softrod_bank_create allocates, for every per-env array the handle has (the list under softrod_copy_envs: the arrays
+ * of softrod_state_view, the tables of softrod_set_env_material / _contact and the rows of softrod_set_reset_shapes
+ * where they exist), a twin with `slots` rows in place of n_envs, zeroed, and a pinned staging buffer of its own for
+ * max(n_envs, slots) pairs.  The list is the one softrod_copy_envs walks, not a second one.  Once per handle; the bank
+ * lives until softrod_destroy.  A per-env table or the reset-shape rows created AFTER the bank get their twin at that
+ * moment, every slot's row at the value the new array gives an untouched env (the config's material or contact;
+ * index -1, episode 0), and softrod_set_reset_shapes, which restarts every env's sequence of starts, restarts every
+ * slot's.  The rule: a slot loads as the env it was saved from would be now, had nothing touched it since the save.
+ * Errors (SOFTROD_EINVAL unless noted; the handle is unchanged and has no bank):
+ *   "bank create: null handle"
+ *   "bank create: not on a handle with device-side auto-reset ..." (softrod_copy_envs' reason)
+ *   "bank create: the handle already has a state bank of <K> slots"
+ *   "bank create: slots <k> is not positive"
+ *   SOFTROD_ENOMEM "bank create: ..." when the device or the host cannot hold it.                                 */
+int softrod_bank_create(softrod_handle* h, int slots);
+
+/* Save: after the call, on `stream`, slot slots[i] is an exact (bitwise) copy of env envs[i] as it stood before the
+ * call, for i = 0 .. count - 1, and holds a state from then on.  envs, slots: host [count].  One env may go into any
+ * number of slots; a slot may appear once.  Asynchronous on `stream`: one small upload of the pairs through the bank's
+ * pinned buffer and one cold kernel, softrod_bank_copy_kernel (csrc/softrod_state_bank.hpp), one workgroup per pair —
+ * the bytes softrod_copy_envs moves per pair.  NOT graph-capturable: the arguments are validated on the host and the
+ * pairs are uploaded by the call.  count == 0 is a successful no-op.
+ * Errors, each SOFTROD_EINVAL with its text in softrod_last_error, found on the host before anything is enqueued (a
+ * refused call changes nothing):
+ *   "bank save: null handle"
+ *   "bank save: the handle has no state bank ..." (softrod_bank_create)
+ *   "bank save: not on a handle with device-side auto-reset ..."
+ *   "bank save: count <c> is outside 0 .. slots = <K>"
+ *   "bank save: null envs or slots" (with count > 0)
+ *   "bank save: env index <e> (pair <i>) is outside 0 .. <N - 1>"
+ *   "bank save: slot index <k> (pair <i>) is outside 0 .. <K - 1>"
+ *   "bank save: slot <k> appears twice".                                                                          */
+int softrod_bank_save(softrod_handle* h, const int32_t* envs, const int32_t* slots, int count, void* stream);
+
+/* Load: after the call, on `stream`, env envs[i] is an exact (bitwise) copy of slot slots[i], for i = 0 .. count - 1:
+ * stepped with the same actions it continues bitwise as the env it was saved from did.  slots, envs: host [count].
+ * One slot may feed any number of envs; an env may appear once.  The slot keeps its state.  The pinned host copies of
+ * the material and contact tables follow the load, so a later softrod_set_env_* uploads the loaded rows.  Asynchronous
+ * and NOT graph-capturable, as softrod_bank_save; count == 0 is a successful no-op.
+ * Errors (SOFTROD_EINVAL, host only, a refused call changes nothing): softrod_bank_save's with "bank load: " in front,
+ * and in place of its last two
+ *   "bank load: count <c> is outside 0 .. n_envs = <N>"
+ *   "bank load: slot <k> holds no state" (never saved)
+ *   "bank load: env <e> appears twice".                                                                           */
+int softrod_bank_load(softrod_handle* h, const int32_t* slots, const int32_t* envs, int count, void* stream);
+
+/* The bank's shape: *slots (0: the handle has no bank), *bytes_per_slot — the device bytes of one env's state, the sum
+ * over the arrays softrod_copy_envs walks, which is what one slot takes and one save or load moves — and, where `filled`
+ * is not NULL, filled[k] != 0 for every slot k that holds a state (host [slots]).  Host only.                        */
+int softrod_bank_info(softrod_handle* h, int32_t* slots, uint64_t* bytes_per_slot, uint8_t* filled);
+
 /* Render: batched RGB and depth frames of the resident envs, on the device.  Replaces: render() of
  * render_mode="rgb_array", which upstream ships on every env (metadata["render_modes"]) and draws one env at a time on
  * the host; here it is what pixel observations, RGB-D policies and per-env video logging of a resident batch need.  A
