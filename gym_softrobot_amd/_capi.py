@@ -1140,6 +1140,8 @@ _EXPORTS = {
     "softrod_reset_shape_index": (C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]),
     "softrod_substeps": (C.c_int, [_VP, _VP, C.c_int, _VP]),
     "softrod_state_view_get": (C.c_int, [_VP, C.POINTER(SoftrodStateView)]),
+    "softrod_set_planar_certificates": (C.c_int, [_VP, C.c_int]),
+    "softrod_planar_certificates": (C.c_int, [_VP, _VP, _VP]),
     "softrod_set_timing": (C.c_int, [_VP, C.c_int]),
     "softrod_kernel_times_ms": (C.c_int, [_VP, _VP, C.c_int, C.POINTER(C.c_int)]),
     "softrod_last_kernel_ms": (C.c_int, [_VP, C.POINTER(C.c_float)]),

@@ -3,6 +3,7 @@ tensors.  torch is plumbing only (device memory, streams); all arithmetic of the
 path happens in libsoftrod_hip.so.  There is no CPU fallback here by design."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Dict, Optional, Tuple
 
@@ -661,13 +662,44 @@ class HipRodBackend:
     def prev_action_rows(self) -> torch.Tensor:
         """Writable (n_envs, action_dim) view of the resident `_prev_action`."""
         if getattr(self, "_prev_rows", None) is None:
-            self._prev_rows = self.state()["prev_action"]
+            with self._views() as st:
+                self._prev_rows = st["prev_action"]
             if not self.is_octo and not self.is_mocto:
                 self._prev_rows = self._prev_rows[:, : self.action_dim]
         return self._prev_rows
 
+    # -- planar certificates (softrod_set_planar_certificates; SoftPendulum-v0 under MATH_FAST, a no-op elsewhere) -----
+    def set_planar_certificates(self, on: bool) -> None:
+        """softrod_set_planar_certificates: let the SoftPendulum step kernels trust (and issue) per-env planar
+        certificates instead of proving planarity at every launch (include/softrod.h).  Default on; state() switches
+        them off for good, only this call switches them back on — do that only once nothing writes resident rows
+        through a view any more.  Waits for the device; every env is proved again at its next step."""
+        check(self._lib.softrod_set_planar_certificates(self._h, int(bool(on))), self._h)
+        self._planar_cert_on = bool(on)
+
+    def planar_certificates(self) -> torch.Tensor:
+        """softrod_planar_certificates: (n_envs,) uint8 device copy of the certificates on the current stream — 0
+        unknown, 1 / 2 certified planar with d2_z > 0 / < 0; all zero while they are off or the handle has none."""
+        out = torch.empty((self.n_envs,), dtype=torch.uint8, device=self.device)
+        check(self._lib.softrod_planar_certificates(self._h, C.c_void_p(out.data_ptr()), self._stream()), self._h)
+        return out
+
+    @contextlib.contextmanager
+    def _views(self):
+        """state() for this class's own use — reads and writes that are over (synchronised) when the block ends, or
+        views it keeps of arrays no certificate vouches for (prev_action, time): planar certificates that were on are
+        switched back on behind the block."""
+        was_on = getattr(self, "_planar_cert_on", True)
+        try:
+            yield self.state()
+        finally:
+            if was_on:
+                self.set_planar_certificates(True)
+
     def state(self) -> Dict[str, torch.Tensor]:
-        """Zero-copy torch views of the resident SoA state (softrod_state_view)."""
+        """Zero-copy torch views of the resident SoA state (softrod_state_view).  The caller may write through them
+        at any later time, so the call switches planar certificates off on this backend (set_planar_certificates)."""
+        self._planar_cert_on = False
         v = SoftrodStateView()
         check(self._lib.softrod_state_view_get(self._h, C.byref(v)), self._h)
         n, s = self.n_envs, int(v.lane_stride)
@@ -740,9 +772,9 @@ class HipRodBackend:
         if getattr(self, "queue_depth", 0):
             raise _capi.SoftrodError("snapshot/restore of a handle with device-side auto-reset is not supported: "
                                      "the pending-reset flags and the staged queue are not part of the state view")
-        st = self.state()
-        torch.cuda.synchronize(self.device)
-        snap = {k: st[k].cpu().clone() for k in self._snapshot_keys()}
+        with self._views() as st:
+            torch.cuda.synchronize(self.device)
+            snap = {k: st[k].cpu().clone() for k in self._snapshot_keys()}
         if getattr(self, "_env_material", None) is not None:        # per-env material (set_env_material)
             snap["env_material"] = torch.from_numpy(self._env_material.copy())
         if getattr(self, "_env_contact", None) is not None:         # per-env contact (set_env_contact)
@@ -762,11 +794,12 @@ class HipRodBackend:
             raise ValueError("snapshot was taken under a different softrod_config / ABI version / table set "
                              "(dt, n_substeps, features, env_kind, material, radius profile, spline table, "
                              "action basis ...): refusing to load it")
-        st = self.state()
-        for k in self._snapshot_keys():
-            if tuple(snap[k].shape) != tuple(st[k].shape):
-                raise ValueError(f"snapshot field {k!r} has shape {tuple(snap[k].shape)}, expected {tuple(st[k].shape)}")
-            st[k].copy_(snap[k].to(self.device))
+        with self._views() as st:       # (switching certificates back on waits for these copies and withdraws every one)
+            for k in self._snapshot_keys():
+                if tuple(snap[k].shape) != tuple(st[k].shape):
+                    raise ValueError(f"snapshot field {k!r} has shape {tuple(snap[k].shape)}, expected {tuple(st[k].shape)}")
+            for k in self._snapshot_keys():
+                st[k].copy_(snap[k].to(self.device))
         # the material the snapshot was taken under; no key: the config's own values
         if "env_material" in snap:
             self.set_env_material(snap["env_material"].numpy())
@@ -786,18 +819,17 @@ class HipRodBackend:
     def rod_snapshot(self, env_indices) -> Dict[str, np.ndarray]:
         """Host copy of a few rods only (diagnostic taps): x, v (k,3,n+1); Q (k,3,3,n);
         w (k,3,n); time (k,).  One small device->host copy per field."""
-        st = self.state()
         idx = torch.as_tensor(list(env_indices), dtype=torch.long, device=self.device)
         ne = int(self.cfg.n_elem)
+        with self._views() as st:
+            def rows(name, width):
+                return st[name].index_select(1, idx)[:, :, :width].permute(1, 0, 2).cpu().numpy()
 
-        def rows(name, width):
-            return st[name].index_select(1, idx)[:, :, :width].permute(1, 0, 2).cpu().numpy()
-
-        return {
-            "x": rows("position", ne + 1), "v": rows("velocity", ne + 1), "w": rows("omega", ne),
-            "Q": rows("director", ne).reshape(len(env_indices), 3, 3, ne),
-            "time": st["time"].index_select(0, idx).cpu().numpy(),
-        }
+            return {
+                "x": rows("position", ne + 1), "v": rows("velocity", ne + 1), "w": rows("omega", ne),
+                "Q": rows("director", ne).reshape(len(env_indices), 3, 3, ne),
+                "time": st["time"].index_select(0, idx).cpu().numpy(),
+            }
 
     def kernel_tier(self) -> str:
         """softrod_kernel_tier: which step kernel this batch runs (follows from the config alone; the
@@ -831,19 +863,19 @@ class HipRodBackend:
 
     def state_numpy(self) -> Dict[str, np.ndarray]:
         """Host copy in the reference's per-rod shapes: x,v (N,3,n+1); Q (N,3,3,n); w (N,3,n)."""
-        st = self.state()
         ne = int(self.cfg.n_elem)
-        torch.cuda.synchronize(self.device)
-        out = {
-            "x": st["position"][:, :, : ne + 1].permute(1, 0, 2).cpu().numpy(),
-            "v": st["velocity"][:, :, : ne + 1].permute(1, 0, 2).cpu().numpy(),
-            "w": st["omega"][:, :, :ne].permute(1, 0, 2).cpu().numpy(),
-            "tangents": st["tangents"][:, :, :ne].permute(1, 0, 2).cpu().numpy(),
-            "time": st["time"].cpu().numpy(),
-            "control": st["control"].permute(1, 0).cpu().numpy(),
-            "kappa": st["kappa"][:, :, : ne - 1].permute(1, 0, 2).cpu().numpy(),
-            "rest_kappa": st["rest_kappa"][:, :, : ne - 1].permute(1, 0, 2).cpu().numpy(),
-        }
-        q = st["director"][:, :, :ne].permute(1, 0, 2).cpu().numpy()
+        with self._views() as st:
+            torch.cuda.synchronize(self.device)
+            out = {
+                "x": st["position"][:, :, : ne + 1].permute(1, 0, 2).cpu().numpy(),
+                "v": st["velocity"][:, :, : ne + 1].permute(1, 0, 2).cpu().numpy(),
+                "w": st["omega"][:, :, :ne].permute(1, 0, 2).cpu().numpy(),
+                "tangents": st["tangents"][:, :, :ne].permute(1, 0, 2).cpu().numpy(),
+                "time": st["time"].cpu().numpy(),
+                "control": st["control"].permute(1, 0).cpu().numpy(),
+                "kappa": st["kappa"][:, :, : ne - 1].permute(1, 0, 2).cpu().numpy(),
+                "rest_kappa": st["rest_kappa"][:, :, : ne - 1].permute(1, 0, 2).cpu().numpy(),
+            }
+            q = st["director"][:, :, :ne].permute(1, 0, 2).cpu().numpy()
         out["Q"] = q.reshape(self.n_envs, 3, 3, ne)
         return out

@@ -140,6 +140,9 @@ struct softrod_handle {
     hipEvent_t ev_pairs = nullptr;  // guards reuse of h_pairs
     std::vector<uint8_t> is_dst;    // [N] scratch of its validation, all zero between calls
     StateBank bank;                 // softrod_bank_create
+    // planar certificates (StatePtrs.planar_cert, softrod_planar.hpp)
+    bool cert_on = true;            // softrod_set_planar_certificates; softrod_state_view_get switches it off for good
+    bool cert_live = false;         // a launch since the last clear may have issued certificates
     std::string err;
 };
 
@@ -370,6 +373,16 @@ void env_contact_row(const double c[8], EnvContact& R) {
     R.stat_am[0] = 0.5 * (R.stat_mu[0] + R.stat_mu[1]); R.stat_am[1] = 0.5 * (R.stat_mu[0] - R.stat_mu[1]);
 }
 
+// Withdraw every planar certificate of the handle on `st`: what each host entry point that may write an env's rows or
+// BC targets does first (cold paths all; the device passes clear the byte of the envs they restart inside their
+// kernels).  `always` = false: only if a launch may have issued one since the last clear.
+int clear_planar_certs(softrod_handle* h, hipStream_t st, bool always = true) {
+    if (!h->S.planar_cert || !(always || h->cert_live)) return SOFTROD_OK;
+    SR_HIP(h, hipMemsetAsync(h->S.planar_cert, 0, (size_t)h->cfg.n_envs, st));
+    h->cert_live = false;
+    return SOFTROD_OK;
+}
+
 // NEXT_STEP auto-reset pass in front of a step: finished envs restart instead of stepping
 int launch_autoreset(softrod_handle* h, float* obs, double* reward, uint8_t* term, uint8_t* trunc, double* aux, int pack,
                      hipStream_t st) {
@@ -449,6 +462,7 @@ struct StepRow {
     bool windowed;            // env.step of a two-window handle (window_refresh > 0 and the epilogue asked for)
     unsigned needs, honours;  // options it is compiled FOR (the handle must have them) / honours (the handle may)
     StepKernel step; OctoKernel octo; WindowKernel window;    // exactly one of the three is set
+    bool cert;                // `step` is a SoftPendulum planar kernel: it reads and issues planar certificates
     int epb, waves;           // launch shape: envs per workgroup, waves per workgroup (0: the handle's waves per env)
     const char* label;        // softrod_kernel_tier; {waves}: the handle's waves per env, {refresh}: its window_refresh
 };
@@ -469,6 +483,7 @@ template <unsigned F, int E, int EPL, bool TAPER = false>
 constexpr StepRow fast_row(const char* label) {
     StepRow r = compiled_row(F, E, EPL, TAPER, 1, 1, label);
     r.step = softrod_step_fast_kernel<F, E, EPL, TAPER>;
+    r.cert = (F & ~kFeatEnvMaterial) == SOFTROD_FEATURES_SOFTPENDULUM;      // (kPlanarKernel)
     return r;
 }
 template <unsigned F, int MAXW, int EPB>
@@ -721,6 +736,10 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
     // a windowed env.step: its substeps, then reward / observation by the row of the same handle's plain substeps
     const StepChoice after = c.row->windowed ? select_step(h, 0) : StepChoice{nullptr, nullptr};
     if (c.row->windowed && !after.row) return fail(h, SOFTROD_EINVAL, after.why);
+    // Planar certificates: a kernel that knows them may issue some (it reads the switch itself, from device memory);
+    // any other kernel writes rows without knowing of them, so what earlier launches issued is withdrawn in front of it.
+    if (c.row->cert) h->cert_live = true;
+    else if (const int rc = clear_planar_certs(h, st, false)) return rc;
     auto launch = [&](const StepRow& r, int n, int epi, hipEvent_t t0, hipEvent_t t1) {
         const dim3 grid((unsigned)((h->cfg.n_envs + r.epb - 1) / r.epb)), block(kLanes * (r.waves ? r.waves : h->nw));
         if (r.window) launch_stamped(r.window, grid, block, st, t0, t1, h->P, h->S, actions, n, h->window_refresh);
@@ -754,6 +773,7 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
 
 int upload_and_reset(softrod_handle* h, hipStream_t st, bool use_mask) {
     const size_t N = (size_t)h->cfg.n_envs;
+    if (const int rc = clear_planar_certs(h, st)) return rc;
     SR_HIP(h, hipMemcpyAsync(h->d_init, h->h_init, N * h->init_stride * sizeof(double), hipMemcpyHostToDevice, st));
     if (use_mask)
         SR_HIP(h, hipMemcpyAsync(h->d_mask, h->h_mask, N, hipMemcpyHostToDevice, st));
@@ -1058,7 +1078,9 @@ CopyTable copy_table(const softrod_handle* h) {
     add(h->env_contact.dev, 1, sizeof(EnvContact));
     // shaped starts: where the copy's episode started, and its resets' count (fork(copy_rng=False) puts dst's back)
     add(h->d_rs_index, 1, sizeof(int)); add(h->d_rs_episode, 1, sizeof(int));
-    static_assert(kCopyMaxArrays >= 22, "copy_table adds up to 22 arrays");
+    // planar certificates: a byte vouches for the rows above, so it travels with them (a bank slot keeps its own)
+    add(S.planar_cert, 1, sizeof(uint8_t));
+    static_assert(kCopyMaxArrays >= 23, "copy_table adds up to 23 arrays");
     return T;
 }
 
@@ -1193,6 +1215,7 @@ int bank_copy(softrod_handle* h, const int32_t* envs, const int32_t* slots, int 
     hipLaunchKernelGGL(softrod_bank_copy_kernel, dim3((unsigned)count), dim3(kCopyThreads), 0, st,
                        load ? twin : batch, load ? batch : twin, bank.d_pairs);
     SR_HIP(h, hipGetLastError());
+    if (load && h->S.planar_cert) h->cert_live = true;      // (a slot's certificate travels with its rows)
     if (!load)
         for (int i = 0; i < count; ++i) bank.filled[slots[i]] = 1;
     return SOFTROD_OK;
@@ -1497,6 +1520,13 @@ int softrod_create(const softrod_config* cfg, int device, softrod_handle** out) 
     alloc(h->S.envmem, rowb);
     alloc(h->S.prev_action, N * (adim > 7 ? adim : 7) * sizeof(float));
     alloc(h->S.head, 20 * N * sizeof(double));
+    // planar certificates, all 0 = unknown: for the handles a SoftPendulum planar kernel may step (StepRow.cert)
+    if (cfg->math_mode == SOFTROD_MATH_FAST && cfg->features == SOFTROD_FEATURES_SOFTPENDULUM &&
+        cfg->env_kind == SOFTROD_ENV_SOFTPENDULUM) {
+        alloc(h->S.planar_cert, N + 1);
+        const uint8_t on = 1;       // byte N, the switch (softrod_set_planar_certificates)
+        if (h->S.planar_cert) upload(h->S.planar_cert + N, &on, 1);
+    }
     alloc(h->d_spline, (size_t)(SOFTROD_MAX_SPLINE_PIECES + 1 + SOFTROD_MAX_SPLINE_PIECES * 4 * 4) * sizeof(double));
     h->P.spline = h->d_spline;
     alloc(h->d_ticket, sizeof(unsigned));    // softrod_scatter_rows' arrival counter, zero
@@ -2314,6 +2344,7 @@ int softrod_copy_envs(softrod_handle* h, const int32_t* src, const int32_t* dst,
     SR_HIP(h, hipEventRecord(h->ev_pairs, st));
     hipLaunchKernelGGL(softrod_copy_envs_kernel, dim3((unsigned)n), dim3(kCopyThreads), 0, st, copy_table(h), h->d_pairs);
     SR_HIP(h, hipGetLastError());
+    if (h->S.planar_cert) h->cert_live = true;      // (a certificate may have travelled with its rows)
     return SOFTROD_OK;
 }
 
@@ -2511,6 +2542,7 @@ int softrod_set_rod_shape(softrod_handle* h, const double* kappa, const double* 
     if (!h) return fail(h, SOFTROD_EINVAL, "set rod shape: null handle");
     // every handle's resident rows have rod_layout's form, so there is no refusal list
     SR_ON_DEVICE(h);
+    if (const int rc = clear_planar_certs(h, (hipStream_t)stream)) return rc;
     const RodLayout y = rod_layout(h);
     const RodShapeArgs args{kappa, sigma, velocity, omega, mask, nullptr};
     hipLaunchKernelGGL(by_epl(h, softrod_rod_shape_kernel<1>, softrod_rod_shape_kernel<2>), dim3((unsigned)(h->cfg.n_envs * y.rods)),
@@ -2588,6 +2620,7 @@ int softrod_apply_reset_shapes(softrod_handle* h, const uint8_t* mask, void* str
     if (!h) return fail(h, SOFTROD_EINVAL, "apply reset shapes: null handle");
     if (!h->rs_count) return fail(h, SOFTROD_EINVAL, "apply reset shapes: no pool is set (softrod_set_reset_shapes)");
     SR_ON_DEVICE(h);
+    if (const int rc = clear_planar_certs(h, (hipStream_t)stream)) return rc;
     return launch_reset_shapes(h, kPickMask, mask, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
@@ -2602,6 +2635,10 @@ int softrod_reset_shapes_view(softrod_handle* h, int32_t** index, int32_t** epis
 
 int softrod_state_view_get(softrod_handle* h, softrod_state_view* out) {
     if (!h || !out) return fail(h, SOFTROD_EINVAL, "null argument");
+    // The pointers handed out may be written at any later time, on any stream: from here on the handle's step kernels
+    // prove planarity at every launch again (softrod_set_planar_certificates alone switches the certificates back on).
+    if (h->S.planar_cert && h->cert_on)
+        if (const int rc = softrod_set_planar_certificates(h, 0)) return rc;
     out->n_envs = h->cfg.n_envs;
     out->n_elem = h->cfg.n_elem;
     const RodLayout y = rod_layout(h);
@@ -2626,6 +2663,31 @@ int softrod_state_view_get(softrod_handle* h, softrod_state_view* out) {
     out->material = h->d_mat;
     out->env_aux = h->S.aux;
     out->prev_kappa = h->S.prev_kappa;
+    return SOFTROD_OK;
+}
+
+int softrod_set_planar_certificates(softrod_handle* h, int on) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "set planar certificates: null handle");
+    if (!h->S.planar_cert) return SOFTROD_OK;       // nothing to switch: no kernel of this handle knows certificates
+    SR_ON_DEVICE(h);
+    // The switch is byte n_envs of the array, which the kernels read at every launch — a captured graph's too.  Behind
+    // everything the device still has in flight: a launch enqueued under the old setting neither reads the new one
+    // nor writes a certificate after the clear.
+    SR_HIP(h, hipDeviceSynchronize());
+    std::vector<uint8_t> bytes((size_t)h->cfg.n_envs + 1, 0);
+    bytes.back() = on ? 1 : 0;
+    SR_HIP(h, hipMemcpy(h->S.planar_cert, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+    h->cert_live = false;
+    h->cert_on = on != 0;
+    return SOFTROD_OK;
+}
+
+int softrod_planar_certificates(softrod_handle* h, uint8_t* out, void* stream) {
+    if (!h || !out) return fail(h, SOFTROD_EINVAL, "planar certificates: null argument");
+    SR_ON_DEVICE(h);
+    const size_t N = (size_t)h->cfg.n_envs;
+    if (!h->S.planar_cert) SR_HIP(h, hipMemsetAsync(out, 0, N, (hipStream_t)stream));
+    else SR_HIP(h, hipMemcpyAsync(out, h->S.planar_cert, N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return SOFTROD_OK;
 }
 

@@ -19,7 +19,8 @@
 // lanes' addresses are consecutive, so a wave's access is 1 KiB contiguous for the 512-byte rows (two rows per wave),
 // the widest there is.  Every base is a hipMalloc allocation (256-byte aligned), so those units are 16-byte aligned.
 // The other arrays (8-byte columns, 28-byte prev_action rows, ...) are a few dozen bytes per env and move as 4-byte
-// words, by the first lanes.
+// words, by the first lanes; a row that is no multiple of 4 bytes (the planar certificates: one byte per env, copied
+// with the rows they vouch for) moves byte by byte.
 //
 // The host guarantees (softrod_copy_envs validates before it enqueues anything): every index is inside 0 .. n_envs - 1,
 // no env is written twice, no env that is written is read by another pair, and no pair has src == dst — so the pairs'
@@ -34,7 +35,7 @@ constexpr int kCopyMaxArrays = 24;
 struct CopyArray {
     unsigned char* base;   // component 0 of env 0
     unsigned comps;        // components
-    unsigned row_bytes;    // bytes of one env in one component (the env stride); a multiple of 4
+    unsigned row_bytes;    // bytes of one env in one component (the env stride)
 };
 struct CopyTable {
     int n, n_envs;
@@ -58,12 +59,19 @@ softrod_copy_envs_kernel(const CopyTable T, const int2* __restrict__ pairs) {
                 const size_t off = (size_t)c * comp_stride + ((size_t)u << 4);
                 *reinterpret_cast<uint4*>(to + off) = *reinterpret_cast<const uint4*>(from + off);
             }
-        } else {
+        } else if ((A.row_bytes & 3u) == 0) {
             const unsigned per = A.row_bytes >> 2, total = A.comps * per;
             for (unsigned i = threadIdx.x; i < total; i += kCopyThreads) {
                 const unsigned c = i / per, u = i - c * per;
                 const size_t off = (size_t)c * comp_stride + ((size_t)u << 2);
                 *reinterpret_cast<unsigned*>(to + off) = *reinterpret_cast<const unsigned*>(from + off);
+            }
+        } else {
+            const unsigned per = A.row_bytes, total = A.comps * per;
+            for (unsigned i = threadIdx.x; i < total; i += kCopyThreads) {
+                const unsigned c = i / per, u = i - c * per;
+                const size_t off = (size_t)c * comp_stride + (size_t)u;
+                to[off] = from[off];
             }
         }
     }

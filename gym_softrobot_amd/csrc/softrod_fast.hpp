@@ -807,18 +807,40 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
     // first force evaluation), and the other paths reload the rod behind general_step_cold
     constexpr bool kPlanarKernel = (F & ~kFeatEnvMaterial) == SOFTROD_FEATURES_SOFTPENDULUM;
     LaneN<EPL> L;
-    load_lane<EPL, F, !kPlanarKernel>(S, N, rod, lane, L);
-    SR_PHASE(1);
-    if (has<F>(P, SOFTROD_FEAT_LAPLACE_FILTER)) sanitize_unused_rates<EPL>(P, lane, L);
-    if (has<F>(P, SOFTROD_FEAT_PLANE_CONTACT_ANISO)) sanitize_unused_slots<EPL>(P, lane, L);
     BcTargets B;
-    load_bc(S, N, rod, B);
-    load_suckers<F>(P, S, N, rod, B);
     EnvAction A;
-    set_action_n<F, E, EPL>(P, S, N, rod, lane, actions, A, B, L);
-    if (epilogue) push_store_prev_com<F, E, EPL>(P, S, N, rod, lane, L, n_sub);
-    if (has<F>(P, SOFTROD_FEAT_SPLINE_MUSCLE_TORQUES)) muscle_load<EPL>(P, S, rod, actions != nullptr, A, L);
-    {
+    // the SoftPendulum instantiation's way to its loop (dead elsewhere): what the proof of planarity found, or what a
+    // certificate says it would find (softrod_planar.hpp)
+    [[maybe_unused]] bool certified = false, cert_on = false, proof_ok = true, proof_nan = false;
+    [[maybe_unused]] double s2w = 1.0;
+    bool blown_up = false;
+    if constexpr (kPlanarKernel) {
+        // The certificate byte (and the byte that says the feature is on) is asked for ahead of the seven rows every
+        // rod needs, so that the branch on it waits for those two loads only and the rows are on their way meanwhile:
+        // a certified rod loads nothing further, any other loads the proof's eleven rows behind them.  With the
+        // feature off the kernel takes no notice of certificates: it proves every rod and writes no byte.
+        unsigned cert = 0, on = 0;
+        if (S.planar_cert) { on = S.planar_cert[N]; cert = S.planar_cert[rod]; }
+        double bc_in_plane[3];
+        planar_load_state<EPL>(S, N, rod, lane, L, bc_in_plane);
+        set_action_n<F, E, EPL>(P, S, N, rod, lane, actions, A, B, L);      // (this env's touches neither B nor L)
+        cert_on = __builtin_amdgcn_readfirstlane((int)on) != 0;
+        cert = cert_on ? (unsigned)__builtin_amdgcn_readfirstlane((int)cert) : 0u;
+        certified = cert != 0;
+        if (certified) s2w = cert == 1u ? 1.0 : -1.0;
+        else planar_prove<EPL>(P, S, N, rod, lane, L, bc_in_plane, s2w, proof_ok, proof_nan);
+        planar_constrain_state<EPL>(lane, bc_in_plane, L);
+        SR_PHASE(1);
+    } else {
+        load_lane<EPL, F>(S, N, rod, lane, L);
+        SR_PHASE(1);
+        if (has<F>(P, SOFTROD_FEAT_LAPLACE_FILTER)) sanitize_unused_rates<EPL>(P, lane, L);
+        if (has<F>(P, SOFTROD_FEAT_PLANE_CONTACT_ANISO)) sanitize_unused_slots<EPL>(P, lane, L);
+        load_bc(S, N, rod, B);
+        load_suckers<F>(P, S, N, rod, B);
+        set_action_n<F, E, EPL>(P, S, N, rod, lane, actions, A, B, L);
+        if (epilogue) push_store_prev_com<F, E, EPL>(P, S, N, rod, lane, L, n_sub);
+        if (has<F>(P, SOFTROD_FEAT_SPLINE_MUSCLE_TORQUES)) muscle_load<EPL>(P, S, rod, actions != nullptr, A, L);
         BcTargets B0 = B;
         if (has<F>(P, SOFTROD_FEAT_MOVING_BASE_BC)) {
             B0.vel[0] = __shfl(L.v[0][0], 0); B0.vel[1] = __shfl(L.v[0][1], 0); B0.vel[2] = __shfl(L.v[0][2], 0);
@@ -840,19 +862,19 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
     // 196-208) would only smear that NaN over all of its nodes while dragging every
     // range-reduction loop to its iteration cap.  It is not integrated: its state becomes NaN
     // throughout (where the reference's would end up after a few substeps), its clock advances.
-    bool blown_up = false;
-    if (n_sub > 0 && epilogue && rod_has_nan<EPL>(P, lane, L)) {
+    if constexpr (kPlanarKernel) {
+        blown_up = n_sub > 0 && epilogue && __any(proof_nan || planar_has_nan<EPL>(P, lane, L));
+    } else if (n_sub > 0 && epilogue && rod_has_nan<EPL>(P, lane, L)) {
         blown_up = true;
-        if constexpr (!kPlanarKernel) {
-            poison_rod<EPL>(L);
-            time = clock_after(P, S, time, n_sub);
-        }
+        poison_rod<EPL>(L);
+        time = clock_after(P, S, time, n_sub);
     }
     if constexpr (kPlanarKernel) {
         // SoftPendulum-v0 lives in the x-y plane: same substep without the identically
         // zero out-of-plane terms (softrod_planar.hpp); any other state takes the 3-D loop
         PlanarN<EPL> Z;
-        if (n_sub > 0 && !blown_up && planar_from_lane<EPL>(P, B, lane, L, Z)) {
+        const bool planar = n_sub > 0 && !blown_up && !__any(!(planar_from_lane<EPL>(P, lane, L, s2w, Z) && proof_ok));
+        if (__builtin_expect(planar, 1)) {      // (the hint keeps the loop ahead of the cold call in the kernel's text)
             PlanarC<EPL> K;
             planar_build_const<EPL, kEnvMaterial<F>>(Pk, C, lane, K);
             // The clock takes the reference's additions in the reference's order: 2 n_sub times
@@ -920,7 +942,9 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
             // velocities and tangents; everything else of the 3-D lane state is dead from here on
             // the planar path — said explicitly, so that none of it stays in registers (at 128:
             // in scratch) across the loop for the sake of the other path's merge.
-            planar_store<EPL>(S, N, rod, lane, Z, !SOFTROD_PLANAR_EXEC_MASK || lane * EPL <= P.n_elem);
+            planar_store<EPL>(S, N, rod, lane, Z, !SOFTROD_PLANAR_EXEC_MASK || lane * EPL <= P.n_elem, !certified);
+            // the rod has passed the proof and been stepped on the planar path: what it now holds is certified
+            if (cert_on && !certified && lane == 0) S.planar_cert[rod] = Z.s2 > 0.0 ? 1 : 2;
 #pragma unroll
             for (int s = 0; s < EPL; ++s) {
 #pragma unroll
@@ -934,6 +958,8 @@ softrod_step_fast_kernel(const RodParams P, const StatePtrs S, const float* __re
             // cold call and is read back for the epilogue.  The lane index passes through an opaque
             // register first: the reload's row addresses are formed here, not shared with the kernel's
             // first loads and kept (in scratch) across the planar block.
+            // Whatever it leaves behind carries no certificate.
+            if (cert_on && lane == 0) S.planar_cert[rod] = 0;
             general_step_cold<F, E, EPL>(S.params, S.self, rod, lane, actions, n_sub, blown_up);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             load_lane<EPL, F>(S, N, rod, opaque_lane(lane), L);

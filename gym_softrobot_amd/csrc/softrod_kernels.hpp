@@ -207,6 +207,10 @@ struct StatePtrs {
     float* prev_kappa;      // [N][n_arm * (n_elem - 1)] ArmTwoEnv._prev_kappa
     const EnvMaterial* env_mat;   // [N] per-env material rows (softrod_set_env_material), or nullptr (RodParams)
     const EnvContact* env_contact;   // [N] per-env contact rows (softrod_set_env_contact), or nullptr (RodParams)
+    uint8_t* planar_cert;   // [N + 1] planar certificates of the SoftPendulum step kernels (softrod_planar.hpp): 0 unknown,
+                            // 1 / 2 certified planar with d2_z > 0 / < 0; nullptr: the handle has none.  Whoever writes an
+                            // env's rows or BC targets clears its byte.  Byte N: the feature is on — in device memory, not
+                            // a kernel argument, so that a captured graph follows the switch
 };
 
 // ---------------------------------------------------------------------------------
@@ -2116,6 +2120,7 @@ __device__ __forceinline__ void reset_rod(const RodParams& P, const StatePtrs& S
     if (lane == 0) {
         S.time[rod] = 0.0;
         if (S.needs_reset) S.needs_reset[rod] = 0;
+        if (S.planar_cert) S.planar_cert[rod] = 0;        // the record's frame need not lie in the plane
         if (P.env_kind == SOFTROD_ENV_SOFTPENDULUM3D) {   // _prev_action.fill(0), soft_pendulum_3d.py:68
 #pragma unroll
             for (int i = 0; i < 7; ++i) S.prev_action[7 * (size_t)rod + i] = 0.0f;

@@ -33,9 +33,10 @@
 // stabilised inverted pendulum leaves the 1e-5 tolerance after 89 env.steps instead of 107
 // (profiles/r3_fastmath_cost.json; every other reformulation in this file costs no horizon).
 //
-// The step kernel takes this path only if the loaded state IS planar (planar_from_lane:
-// exact zeros where the argument above needs them, d1 consistent with d3 to 1e-12); any
-// other state — e.g. one written through softrod_state_view — runs the general 3-D loop.
+// The step kernel takes this path only if the loaded state IS planar (planar_prove, planar_from_lane:
+// exact zeros where the argument above needs them, d1 consistent with d3 to 1e-12) or holds the
+// certificate of an earlier launch's proof ("planar certificates" below); any other state — e.g. one
+// written through softrod_state_view — runs the general 3-D loop.
 //
 // The loop is VALU-issue bound, so what is left is written to the instruction:
 //   * the state carries the rotation rate about z, wz = s2 w, instead of w: every s2 in the
@@ -154,26 +155,155 @@ __device__ __forceinline__ double exp_one(const PlanarC<EPL>& K, double x) {
     return e;
 }
 
-// Wave-uniform: true if the whole rod (and its forcing) is planar in the sense above.
+// ---- planar certificates (StatePtrs.planar_cert) --------------------------------------------------------------
+// What planar_from_lane proves about a rod at every launch is, by the exactness argument at the top of this file,
+// still true of the state the planar step leaves behind — until somebody else writes that state.  So the kernel
+// that has stepped a rod on the planar path leaves one byte per env saying so (1: d2_z > 0, 2: d2_z < 0), every other
+// writer of an env's rows or BC targets clears it (softrod.h lists them), and a launch that finds the byte set loads
+// the seven rows the planar state consists of — x, y, v_x, v_y, d3_x, d3_y, omega_2 — instead of the eighteen the
+// proof reads, takes every other value as the constant the proof found there, and skips the proof.
+//
+// A certificate says, of the rod as the kernel's prologue leaves it (constrain_rates_n / constrain_values_n applied):
+//   * the nine out-of-plane rows hold exact zeros where the rod has nodes / elements (x_z, v_z, d1_z, d2_x, d2_y, d3_z,
+//     omega_1, omega_3) and d2_z is +-1 to 1e-12 with the sign the byte records, the same on every element;
+//   * d1 = d2 x d3 to 1e-12 (planar_store rebuilds it from d3, so after the first planar step: exactly);
+//   * the BC targets pass their four comparisons (gravity_z is a kernel argument that never changes on a handle).
+// What it does NOT say is that d3 is still a unit vector to 1e-12: that comparison is about the integrator's own
+// rounding (400 rotations per env.step, each good to an ulp), not about another writer, so a certified launch keeps it —
+// three FMAs and a compare on rows it loads anyway — and a rod that fails it takes the 3-D loop exactly when it
+// would have without certificates.
+//
+// rod_has_nan on a certified rod needs the seven loaded rows only: the zeros and +-1 are finite, d1 is a signed copy
+// of d3 (a NaN there is a NaN here), and the tangents are no part of that test — a NaN tangent comes out of a NaN
+// edge vector, which the same planar_dynamic_n puts into the velocities.
+//
+// So the way to the loop has a part every rod takes — planar_load_state, planar_has_nan, planar_from_lane: the seven
+// rows, the three in-plane BC targets, the pendulum constraint on them, d3's length — and a part behind one
+// wave-uniform branch that only a rod without a certificate takes: planar_prove, the other eleven rows and nine
+// targets, loaded, constrained, tested for NaN and compared.
+
+// The planar state: the seven rows, and in `bc` the three BC targets the pendulum constraint puts into them on node 0 /
+// element 0 (planar_constrain_state: constrain_rates_n and constrain_values_n on these rows — v_y = 0, y and d3 from
+// the targets).  Every other entry of L is zero: no path reads it before it is written.
 template <int EPL>
-__device__ __forceinline__ bool planar_from_lane(const RodParams& P, const BcTargets& B, int lane,
-                                                 const LaneN<EPL>& L, PlanarN<EPL>& Z) {
-    const int n = P.n_elem;
-    bool ok = (P.gravity[2] == 0.0) && (B.pos[2] == 0.0) && (B.Q[2] == 0.0) && (B.Q[8] == 0.0);
-    // d2_z = -(cos^2 + sin^2) as straight_rod's cross product rounds it: +-1 to an ulp; the
-    // planar update leaves row 1 of Q untouched, exactly like the 3-D one (R4 = 1)
-    Z.s2 = __shfl((L.Q[0][5] < 0.0) ? -1.0 : 1.0, 0);
+__device__ __forceinline__ void planar_load_state(const StatePtrs& S, size_t N, int rod, int lane, LaneN<EPL>& L,
+                                                  double (&bc)[3]) {
+    constexpr size_t W = (size_t)kLanes * EPL;
+    const size_t base = (size_t)rod * W + (size_t)lane * EPL;
+    bc[0] = S.bc[(size_t)1 * N + rod];
+    bc[1] = S.bc[(size_t)(3 + 6) * N + rod];
+    bc[2] = S.bc[(size_t)(3 + 7) * N + rod];
+#pragma unroll
+    for (int s = 0; s < EPL; ++s) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { L.x[s][c] = 0.0; L.v[s][c] = 0.0; L.w[s][c] = 0.0; L.t[s][c] = 0.0; L.kap[s][c] = 0.0; L.rk[s][c] = 0.0; }
+#pragma unroll
+        for (int c = 0; c < 9; ++c) L.Q[s][c] = 0.0;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            L.x[s][c] = S.pos[c * N * W + base + s];
+            L.v[s][c] = S.vel[c * N * W + base + s];
+            L.Q[s][6 + c] = S.dir[(6 + c) * N * W + base + s];
+        }
+        L.w[s][1] = S.omg[1 * N * W + base + s];
+    }
+}
+// (apart from the loads, so that nothing waits for them ahead of the branch that issues planar_prove's)
+template <int EPL>
+__device__ __forceinline__ void planar_constrain_state(int lane, const double (&bc)[3], LaneN<EPL>& L) {
+    const bool l0 = (lane == 0);
+    L.x[0][1] = l0 ? bc[0] : L.x[0][1];
+    L.v[0][1] = l0 ? 0.0 : L.v[0][1];
+    L.Q[0][6] = l0 ? bc[1] : L.Q[0][6];
+    L.Q[0][7] = l0 ? bc[2] : L.Q[0][7];
+}
+
+// rod_has_nan over the seven rows (per lane; the caller reduces)
+template <int EPL>
+__device__ __forceinline__ bool planar_has_nan(const RodParams& P, int lane, const LaneN<EPL>& L) {
+    bool bad = false;
 #pragma unroll
     for (int s = 0; s < EPL; ++s) {
         const int idx = lane * EPL + s;
-        const double* Q = L.Q[s];
-        const double s2 = (Q[5] < 0.0) ? -1.0 : 1.0, c = Q[6], sn = Q[7];
-        const bool node_ok = (L.x[s][2] == 0.0) && (L.v[s][2] == 0.0);
-        const bool elem_ok = (Q[2] == 0.0) && (Q[3] == 0.0) && (Q[4] == 0.0) && (Q[8] == 0.0) && (s2 == Z.s2) &&
-                             (fabs(fabs(Q[5]) - 1.0) <= 1.0e-12) && (L.w[s][0] == 0.0) && (L.w[s][2] == 0.0) &&
-                             (fabs(fma(s2, sn, Q[0])) <= 1.0e-12) && (fabs(fma(-s2, c, Q[1])) <= 1.0e-12) &&
-                             (fabs(fma(c, c, fma(sn, sn, -1.0))) <= 1.0e-12);
+        const bool b = isnan(L.x[s][0]) || isnan(L.x[s][1]) || isnan(L.v[s][0]) || isnan(L.v[s][1]);
+        const bool q = isnan(L.w[s][1]) || isnan(L.Q[s][6]) || isnan(L.Q[s][7]);
+        bad = bad || (idx <= P.n_elem && b) || (idx < P.n_elem && q);
+    }
+    return bad;
+}
+
+// What a certificate stands for, established from memory: the other eleven rows and nine BC targets with the pendulum
+// constraint applied, their share of rod_has_nan (`nan`, per lane) and of the planarity comparisons (`ok`, per lane),
+// and d2_z's sign on element 0 (`s2`, wave-uniform).  L, bc: planar_load_state's, before planar_constrain_state.
+template <int EPL>
+__device__ __forceinline__ void planar_prove(const RodParams& P, const StatePtrs& S, size_t N, int rod, int lane,
+                                             const LaneN<EPL>& L, const double (&bc)[3], double& s2_out, bool& ok_out,
+                                             bool& nan_out) {
+    constexpr size_t W = (size_t)kLanes * EPL;
+    const size_t base = (size_t)rod * W + (size_t)lane * EPL;
+    const int n = P.n_elem;
+    const bool l0 = (lane == 0);
+    const double bpz = S.bc[(size_t)2 * N + rod];
+    double bq[9];      // (rows 0 and 2 of the target frame, less the two planar_load_state has applied)
+#pragma unroll
+    for (int i = 0; i < 9; ++i) bq[i] = (i < 3 || i == 8) ? S.bc[(size_t)(3 + i) * N + rod] : 0.0;
+    double xz[EPL], vz[EPL], w0[EPL], w2[EPL], Q[EPL][9];
+#pragma unroll
+    for (int s = 0; s < EPL; ++s) {
+        xz[s] = S.pos[2 * N * W + base + s];
+        vz[s] = S.vel[2 * N * W + base + s];
+        w0[s] = S.omg[0 * N * W + base + s];
+        w2[s] = S.omg[2 * N * W + base + s];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) Q[s][c] = (c == 6 || c == 7) ? L.Q[s][c] : S.dir[c * N * W + base + s];
+    }
+    // constrain_rates_n / constrain_values_n on these rows
+    xz[0] = l0 ? bpz : xz[0];
+    vz[0] = l0 ? 0.0 : vz[0];
+    w0[0] = l0 ? 0.0 : w0[0];
+    w2[0] = l0 ? 0.0 : w2[0];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Q[0][j] = l0 ? bq[j] : Q[0][j];
+    Q[0][6] = l0 ? bc[1] : Q[0][6];
+    Q[0][7] = l0 ? bc[2] : Q[0][7];
+    Q[0][8] = l0 ? bq[8] : Q[0][8];
+    bool ok = (P.gravity[2] == 0.0) && (bpz == 0.0) && (bq[2] == 0.0) && (bq[8] == 0.0);
+    // d2_z = -(cos^2 + sin^2) as straight_rod's cross product rounds it: +-1 to an ulp; the
+    // planar update leaves row 1 of Q untouched, exactly like the 3-D one (R4 = 1)
+    const double s2w = __shfl((Q[0][5] < 0.0) ? -1.0 : 1.0, 0);
+    bool bad = false;
+#pragma unroll
+    for (int s = 0; s < EPL; ++s) {
+        const int idx = lane * EPL + s;
+        const double s2 = (Q[s][5] < 0.0) ? -1.0 : 1.0, c = Q[s][6], sn = Q[s][7];
+        const bool node_ok = (xz[s] == 0.0) && (vz[s] == 0.0);
+        const bool elem_ok = (Q[s][2] == 0.0) && (Q[s][3] == 0.0) && (Q[s][4] == 0.0) && (Q[s][8] == 0.0) && (s2 == s2w) &&
+                             (fabs(fabs(Q[s][5]) - 1.0) <= 1.0e-12) && (w0[s] == 0.0) && (w2[s] == 0.0) &&
+                             (fabs(fma(s2, sn, Q[s][0])) <= 1.0e-12) && (fabs(fma(-s2, c, Q[s][1])) <= 1.0e-12);
         ok = ok && (idx > n || node_ok) && (idx >= n || elem_ok);
+        bool q = isnan(w0[s]) || isnan(w2[s]);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) q = q || (k != 6 && k != 7 && isnan(Q[s][k]));
+        bad = bad || (idx <= n && (isnan(xz[s]) || isnan(vz[s]))) || (idx < n && q);
+    }
+    s2_out = s2w;
+    ok_out = ok;
+    nan_out = bad;
+}
+
+// The planar state Z of a rod from planar_load_state's L and d2_z's sign; per lane: d3 is a unit vector to 1e-12 on
+// every element (the one comparison a certificate does not stand for).
+template <int EPL>
+__device__ __forceinline__ bool planar_from_lane(const RodParams& P, int lane, const LaneN<EPL>& L, double s2w,
+                                                 PlanarN<EPL>& Z) {
+    const int n = P.n_elem;
+    bool ok = true;
+    Z.s2 = s2w;
+#pragma unroll
+    for (int s = 0; s < EPL; ++s) {
+        const int idx = lane * EPL + s;
+        const double c = L.Q[s][6], sn = L.Q[s][7];
+        ok = ok && (idx >= n || fabs(fma(c, c, fma(sn, sn, -1.0))) <= 1.0e-12);
         Z.x[s][0] = L.x[s][0]; Z.x[s][1] = L.x[s][1];
         Z.v[s][0] = L.v[s][0]; Z.v[s][1] = L.v[s][1];
         Z.c[s] = c; Z.s[s] = sn;
@@ -207,7 +337,7 @@ __device__ __forceinline__ bool planar_from_lane(const RodParams& P, const BcTar
 #ifdef SOFTROD_DIAG_NO_PLANAR
     return false;
 #endif
-    return !__any(!ok);
+    return ok;
 }
 
 template <int EPL>
@@ -225,7 +355,8 @@ __device__ __forceinline__ void planar_to_lane(const PlanarN<EPL>& Z, LaneN<EPL>
 
 // What a planar step changes, written to the resident rows: x, y, v_x, v_y, d1 = (-s2 s, s2 c), d3 = (c, s),
 // omega_2 and the tangents — 12 of the rod's 21 rows.  The other nine (z components, d2, the
-// out-of-plane directors and rates) hold the exact values planar_from_lane has just checked.
+// out-of-plane directors and rates) hold the exact values planar_prove has checked, at this launch or — certified —
+// at an earlier one.
 // Plain stores: measured against __builtin_nontemporal_store and a relaxed agent-scope __hip_atomic_store
 // (global_store_dwordx2 ... sc1) with tools/step_ab.py, seven alternating passes each at 4096 envs — all three inside
 // one another's spread (profiles/planar_launch_ab.json), so the plain store stays.
@@ -236,16 +367,21 @@ __device__ __forceinline__ void planar_to_lane(const PlanarN<EPL>& Z, LaneN<EPL>
 // wrote a lane past the end node would have to be stored here, as the whole-row store before this one did.)  d1, omega_2 and the tangents' z are written in every lane:
 // they are REBUILT (d1 from d3, one rounding away from a frame a reset wrote; s2 * 0 with s2's sign; 0), so a
 // padding lane's bytes may move the first time — as they always did.
+// `tan_z`: write the tangents' z row.  Not on a certified rod (wave-uniform): the planar step that issued the
+// certificate wrote these zeros into every lane, and whoever writes the row afterwards clears the certificate.
 template <int EPL>
 __device__ __forceinline__ void planar_store(const StatePtrs& S, size_t N, int rod, int lane, const PlanarN<EPL>& Z,
-                                             bool stepped) {
+                                             bool stepped, bool tan_z) {
     constexpr size_t W = (size_t)kLanes * EPL;
     // the row addresses are formed here, behind the loop (opaque_lane): shared with the kernel's first loads they
     // stayed live across it, 26 registers' worth, and the allocator parked what did not fit in scratch
     const size_t base = (size_t)rod * W + (size_t)opaque_lane(lane) * EPL;
+    if (tan_z) {
+#pragma unroll
+        for (int s = 0; s < EPL; ++s) S.tan[2 * N * W + base + s] = 0.0;
+    }
 #pragma unroll
     for (int s = 0; s < EPL; ++s) {
-        S.tan[2 * N * W + base + s] = 0.0;
         S.dir[0 * N * W + base + s] = -Z.s2 * Z.s[s];
         S.dir[1 * N * W + base + s] = Z.s2 * Z.c[s];
         S.omg[1 * N * W + base + s] = Z.s2 * Z.wz[s];

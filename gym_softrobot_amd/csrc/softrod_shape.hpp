@@ -85,6 +85,7 @@ softrod_rod_shape_kernel(const RodParams P, const StatePtrs S, const int rods, c
     const size_t NW = R.N * R.W;
     // the row of the fields this rod reads: its own, or its arm's row of the env's pool entry
     const size_t rod = A.pool_index ? (size_t)A.pool_index[R.env] * (size_t)rods + (size_t)R.arm : (size_t)R.rod;
+    if (lane == 0 && S.planar_cert) S.planar_cert[R.env] = 0;      // the shape need not lie in the plane
 
     // ---- the per-slot factors: the base directors in slot 0, exp([-kappa D^]x) of vertex j - 1 in slot j, identity past the rod
     double M[EPL][9];

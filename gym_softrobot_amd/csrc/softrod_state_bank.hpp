@@ -49,13 +49,19 @@ softrod_bank_copy_kernel(const CopyTable From, const CopyTable To, const int2* _
                 *reinterpret_cast<uint4*>(to + (size_t)c * to_stride + in) =
                     *reinterpret_cast<const uint4*>(from + (size_t)c * from_stride + in);
             }
-        } else {
+        } else if ((A.row_bytes & 3u) == 0) {
             const unsigned per = A.row_bytes >> 2, total = A.comps * per;
             for (unsigned i = threadIdx.x; i < total; i += kCopyThreads) {
                 const unsigned c = i / per, u = i - c * per;
                 const size_t in = ((size_t)u << 2);
                 *reinterpret_cast<unsigned*>(to + (size_t)c * to_stride + in) =
                     *reinterpret_cast<const unsigned*>(from + (size_t)c * from_stride + in);
+            }
+        } else {      // the planar certificates: one byte per env
+            const unsigned per = A.row_bytes, total = A.comps * per;
+            for (unsigned i = threadIdx.x; i < total; i += kCopyThreads) {
+                const unsigned c = i / per, u = i - c * per;
+                to[(size_t)c * to_stride + u] = from[(size_t)c * from_stride + u];
             }
         }
     }

@@ -649,7 +649,13 @@ class VecRodEnvBase:
         obs, reward, term, trunc = self.backend.step(a)    # auto-reset pass + step kernel
         self._top_up_tick()
         if getattr(self, "_dev_time", None) is None:
-            self._dev_time = self.backend.state()["time"]
+            # the clock row, kept and only read: on the HIP backend through the view that leaves planar certificates on
+            views = getattr(self.backend, "_views", None)
+            if views is None:
+                self._dev_time = self.backend.state()["time"]
+            else:
+                with views() as st:
+                    self._dev_time = st["time"]
         # TimeLimit.truncated is the time limit alone; with ArmPush's early termination `truncated` carries the
         # cut-off as well, and the epilogue writes the time-limit flag on its own (backend.time_limit)
         tl = self.backend.time_limit() if getattr(self.cfg, "early_termination", 0) else trunc.view(torch.bool)

@@ -1227,7 +1227,44 @@ uint32_t softrod_reset_shape_index(uint64_t seed, uint32_t env, uint32_t episode
  * Used by the known-answer tests and by the kernel micro-benchmarks.        */
 int softrod_substeps(softrod_handle* h, const float* actions, int n, void* stream);
 
+/* Raw device pointers to the resident state.  On a handle with planar certificates (below) the call switches them off
+ * for good (the first such call waits for the device): the caller may write through these pointers at any later time,
+ * so from here on every launch proves planarity again.  Only softrod_set_planar_certificates(h, 1) switches them back
+ * on.                                                                                                                  */
 int softrod_state_view_get(softrod_handle* h, softrod_state_view* out);
+
+/* PLANAR CERTIFICATES — SOFTROD_ENV_SOFTPENDULUM with SOFTROD_FEATURES_SOFTPENDULUM under SOFTROD_MATH_FAST only; on
+ * every other handle both calls succeed and do nothing (softrod_planar_certificates writes zeros).
+ *
+ * The SoftPendulum step kernels take their planar substep loop after proving, at every launch, that the rod lies in the
+ * x-y plane: eighteen state rows loaded, eleven of them only to be compared with constants.  The state a planar step
+ * leaves behind is planar again, exactly, until somebody else writes it.  So the kernel leaves one byte per env —
+ * 0 unknown, 1 certified planar with d2_z > 0, 2 with d2_z < 0 — and a launch that finds it set loads the seven rows
+ * of the planar state and skips the proof (csrc/softrod_planar.hpp says what a certificate vouches for and why the
+ * results are the same bits).  An env that takes the 3-D loop, holds a NaN or is launched with zero substeps loses its
+ * certificate.  Every other writer of an env's rows or boundary-condition targets withdraws certificates:
+ *   softrod_reset / softrod_reset_straight (full or masked), softrod_set_rod_shape, softrod_apply_reset_shapes
+ *                          all of them, on the call's stream;
+ *   the NEXT_STEP and SAME_STEP auto-reset passes, with or without a pool of reset shapes
+ *                          those of the envs they restart, inside their kernels;
+ *   softrod_copy_envs, softrod_bank_save, softrod_bank_load
+ *                          copy the byte with the rows it vouches for (a bank slot keeps its own);
+ *   softrod_state_view_get all of them, and the feature goes off on this handle (above);
+ *   a step by a kernel that does not know certificates (after softrod_set_radius_profile)
+ *                          all of them, in front of it.
+ * A caller that writes resident rows by any other means — through a view taken before certificates were switched back
+ * on, say — must switch them off first.
+ *
+ *   softrod_set_planar_certificates(h, on)
+ *       default: on.  Waits for the device and withdraws every certificate.  on = 0: from the next launch on the kernels
+ *       neither read nor write one and run the proof at every launch.  on != 0: they issue and trust them again.
+ *       Synchronous; not capturable.  The switch lives in device memory and the kernels read it at every launch, so a
+ *       graph captured earlier follows it (and follows softrod_state_view_get's switching off).
+ *   softrod_planar_certificates(h, out, stream)
+ *       copies the bytes, uint8 [n_envs], to DEVICE memory `out` on `stream` (diagnostics and tests).
+ * Errors (SOFTROD_EINVAL): "set planar certificates: null handle", "planar certificates: null argument".             */
+int softrod_set_planar_certificates(softrod_handle* h, int on);
+int softrod_planar_certificates(softrod_handle* h, uint8_t* out, void* stream);
 
 /* Kernel timing with one pair of HIP events per softrod_step / softrod_substeps
  * call, attached to the call's own kernel dispatches (start: begin of its first

@@ -6,7 +6,11 @@ does a step cost.
                           [--attach NAME=file.json ...] [--no-bench] [--no-states]
 
 The first library is the parent (a build of the parent commit, e.g. under variants/, which is git-ignored), the
-second the branch; further libraries (store flavours and the like) are measured alongside.  Per pass and per
+second the branch; further libraries (store flavours and the like) are measured alongside.  A library written
+LIB@TREE runs under the checkout TREE instead of this one — its bench.py, its Python package, its copy of this tool
+for the state check — which is how a parent is measured whose library this tree's Python layer cannot load (an entry
+point added since: the loader binds every declared symbol), e.g. `git archive HEAD~1 | tar -x -C variants/parent_tree`
+built in place.  Per pass and per
 library, alternating A, B, ..., A, B, ..., a FRESH child process runs the driver's own command
 
   python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
@@ -55,10 +59,17 @@ def find_key(doc, key):
     return None
 
 
+def split_spec(spec):
+    """LIB or LIB@TREE -> (absolute library path, absolute checkout the children run under)."""
+    lib, _, tree = spec.partition("@")
+    return str(Path(lib).resolve()), str(Path(tree).resolve() if tree else ROOT)
+
+
 def run_child(cmd, lib, timeout, **kw):
-    """The child under `timeout -k 10`, SOFTROD_HIP_LIB set -> (exit status, CompletedProcess)."""
+    """The child under `timeout -k 10` in the library's checkout, SOFTROD_HIP_LIB set -> (exit status, CompletedProcess)."""
+    lib, tree = lib
     full = ["timeout", "-k", "10", str(int(timeout))] + cmd
-    p = subprocess.run(full, env={**os.environ, "SOFTROD_HIP_LIB": lib}, cwd=str(ROOT), **kw)
+    p = subprocess.run(full, env={**os.environ, "SOFTROD_HIP_LIB": lib}, cwd=tree, **kw)
     return p.returncode, p
 
 
@@ -131,8 +142,8 @@ def main():
         ap.error("a parent and a branch library are needed")
     if args.passes < 5 and not args.no_bench:
         ap.error("at least five passes")
-    libs = [str(Path(p).resolve()) for p in args.libs]
-    names = ["parent", "branch"] + [Path(p).stem for p in libs[2:]]
+    libs = [split_spec(p) for p in args.libs]
+    names = ["parent", "branch"] + [Path(p[0]).stem for p in libs[2:]]
     doc = {"about": "written by tools/step_ab.py: one run of it (state_check, passes, summary) on one box in one session; `attached` "
                     "holds the JSON files named with --attach, as they are (each says in its own `about` what it is)",
            "command": "python " + " ".join(BENCH) + " --dump-outputs DIR", "libraries": dict(zip(names, args.libs))}
@@ -141,7 +152,8 @@ def main():
             states = {}
             for name, lib in zip(names, libs):
                 out = os.path.join(tmp, f"states_{name}.json")
-                rc, _ = run_child([sys.executable, __file__, "--state-child", out], lib, args.timeout)
+                tool = str(Path(lib[1]) / "tools" / "step_ab.py")      # (the checkout's own copy imports its own package)
+                rc, _ = run_child([sys.executable, tool, "--state-child", out], lib, args.timeout)
                 if rc != 0:
                     print(f"state check: the child on {lib} ended with {rc}; stopping", flush=True)
                     return rc if rc > 0 else 1
