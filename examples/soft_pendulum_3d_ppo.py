@@ -82,6 +82,7 @@ def main():
     boot_buf = torch.empty((T, N), device=dev)        # what a finished step bootstraps from
     val_buf = torch.empty((T + 1, N), device=dev)
 
+    env.record_episode_statistics(100)                # returns and lengths of finished episodes, kept on the device
     obs, _ = env.reset(seed=args.seed)
     obs = obs.clone()
     for update in range(args.updates):
@@ -128,7 +129,10 @@ def main():
                 nn.utils.clip_grad_norm_(net.parameters(), 0.5)
                 opt.step()
         steps = (update + 1) * T * N
-        print(f"update {update + 1:3d}  env-steps {steps:9d}  mean reward/step {rew_buf.mean().item():+.4f}  "
+        ep = env.episode_statistics()                 # the ring of the last 100 finished episodes (one synchronise)
+        recent = (f"episodes {ep.count:6d}  mean return {ep.returns.mean():+.3f}  mean length {ep.lengths.mean():.1f}  "
+                  if ep.count else "episodes      0  ")
+        print(f"update {update + 1:3d}  env-steps {steps:9d}  {recent}mean reward/step {rew_buf.mean().item():+.4f}  "
               f"mean tilt {obs_buf[..., 8].mean().item():.4f}  rollout {T * N / t_roll:,.0f} env-steps/s (policy included)")
     env.close()
 

@@ -199,6 +199,22 @@ class SoftrodStateView(C.Structure):
     ]
 
 
+# the arrays of `struct softrod_episode_stats_view`, in its order: (name, typestr, "n" per env | "k" per ring slot | "1")
+EPISODE_STATS_ARRAYS = (
+    ("acc_return", "<f8", "n"), ("acc_length", "<i4", "n"), ("latch", "|u1", "n"), ("finished", "<i4", "n"),
+    ("ep_r", "<f8", "n"), ("ep_l", "<i4", "n"), ("ep_t", "<f8", "n"), ("ep_mask", "|u1", "n"),
+    ("ring_r", "<f8", "k"), ("ring_l", "<i4", "k"), ("ring_t", "<f8", "k"), ("ring_env", "<i4", "k"),
+    ("count", "<i8", "1"),      # u64 on the device; torch views it as int64
+)
+EPISODE_STATS_MANUAL, EPISODE_STATS_NEXT_STEP, EPISODE_STATS_SAME_STEP = 0, 1, 2     # softrod_episode_stats_update's mode
+
+
+class SoftrodEpisodeStatsView(C.Structure):
+    """Mirror of `struct softrod_episode_stats_view` (include/softrod.h)."""
+
+    _fields_ = [(name, C.c_void_p) for name, _, _ in EPISODE_STATS_ARRAYS] + [("n_envs", C.c_int32), ("ring", C.c_int32)]
+
+
 class SoftrodCamera(C.Structure):
     """Mirror of `struct softrod_camera` (include/softrod.h, softrod_render): the orthographic camera all envs of a
     handle share."""
@@ -1129,6 +1145,10 @@ _EXPORTS = {
     "softrod_bank_save": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP]),
     "softrod_bank_load": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP]),
     "softrod_bank_info": (C.c_int, [_VP, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), _VP]),
+    "softrod_episode_stats_enable": (C.c_int, [_VP, C.c_int]),
+    "softrod_episode_stats_update": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, _VP]),
+    "softrod_episode_stats_reset": (C.c_int, [_VP, _VP, _VP]),
+    "softrod_episode_stats_view": (C.c_int, [_VP, C.POINTER(SoftrodEpisodeStatsView)]),
     "softrod_camera_default": (C.c_int, [C.POINTER(SoftrodConfig), C.POINTER(SoftrodCamera)]),
     "softrod_camera_check": (C.c_int, [C.POINTER(SoftrodCamera)]),
     "softrod_render": (C.c_int, [_VP, C.POINTER(SoftrodCamera), _VP, _VP, _VP]),

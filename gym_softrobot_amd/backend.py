@@ -465,9 +465,67 @@ class HipRodBackend:
             ),
             self._h,
         )
+        if self.episode_stats is not None:       # softrod_episode_stats_update behind the step, on the same stream
+            self.episode_stats_update(self.reward, self.terminated, self.truncated,
+                                      self.final_time if self.episode_stats_mode == _capi.EPISODE_STATS_SAME_STEP
+                                      else self._episode_clock, self.episode_stats_mode)
         return self.obs, self.reward, self.terminated, self.truncated
 
-    supports_early_termination = True     # softrod_config.early_termination runs in the step kernels' epilogue
+    # -- episode statistics (softrod_episode_stats_enable / _update / _reset / _view) ------------------
+    episode_stats: Optional[Dict[str, torch.Tensor]] = None     # the resident arrays while the feature is on
+    episode_stats_mode = _capi.EPISODE_STATS_MANUAL             # what step() passes as `mode`
+
+    def episode_stats_enable(self, ring: int, mode: Optional[int] = None) -> None:
+        """softrod_episode_stats_enable: ring >= 1 allocates (or allocates anew) and zeroes the statistics arrays with a
+        ring of `ring` finished episodes, 0 switches the feature off and frees them.  While it is on `episode_stats`
+        holds zero-copy device views of every array (_capi.EPISODE_STATS_ARRAYS; `count` as int64) — new ones after
+        every call — and step() runs the update behind softrod_step with its own reward / terminated / truncated and
+        `mode` (None: SAME_STEP on a same-step handle, NEXT_STEP with device auto-reset, else MANUAL; a host-driven
+        NEXT_STEP loop passes 1), the env clock row or, in SAME_STEP mode, `final_time` as the end time.  While it is
+        off step() does one attribute test and nothing else.  A captured graph must be captured again after the
+        call."""
+        check(self._lib.softrod_episode_stats_enable(self._h, int(ring)), self._h)
+        self.episode_stats = None
+        if int(ring) == 0:
+            return
+        v = _capi.SoftrodEpisodeStatsView()
+        check(self._lib.softrod_episode_stats_view(self._h, C.byref(v)), self._h)
+        size = {"n": self.n_envs, "k": int(v.ring), "1": 1}
+        views = {name: torch.as_tensor(_DevArray(getattr(v, name), (size[per],), typestr, self), device=self.device)
+                 for name, typestr, per in _capi.EPISODE_STATS_ARRAYS}
+        if mode is None:
+            mode = (_capi.EPISODE_STATS_SAME_STEP if getattr(self, "same_step", False)
+                    else _capi.EPISODE_STATS_NEXT_STEP if getattr(self, "queue_depth", 0) else _capi.EPISODE_STATS_MANUAL)
+        self.episode_stats_mode = int(mode)
+        if getattr(self, "_episode_clock", None) is None:
+            with self._views() as st:           # the clock row, kept and only read
+                self._episode_clock = st["time"]
+        self.episode_stats = views
+
+    def episode_stats_update(self, reward, terminated, truncated, end_time, mode: int) -> None:
+        """softrod_episode_stats_update: one update from device tensors reward f64 (n_envs,), terminated / truncated
+        uint8 or bool (n_envs,), end_time f64 (n_envs,) or None (t = 0); mode 0 manual, 1 NEXT_STEP, 2 SAME_STEP.  One
+        kernel on the current stream; capturable.  step() calls it itself while the feature is on."""
+        check(self._lib.softrod_episode_stats_update(
+            self._h, reward.data_ptr() if reward is not None else None,
+            terminated.data_ptr() if terminated is not None else None,
+            truncated.data_ptr() if truncated is not None else None,
+            end_time.data_ptr() if end_time is not None else None, int(mode), self._stream()), self._h)
+
+    def episode_stats_reset(self, mask=None) -> None:
+        """softrod_episode_stats_reset: zero the accumulators, the latch and the info rows of the envs with mask != 0
+        (None: all); the ring, `finished` and `count` stay.  `mask`: anything (n_envs,), uploaded once unless it is a
+        uint8 / bool tensor on this device."""
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask, device=self.device)
+            if m.dtype not in (torch.uint8, torch.bool):
+                m = m != 0
+            m = m.reshape(self.n_envs).contiguous()
+        check(self._lib.softrod_episode_stats_reset(self._h, m.data_ptr() if m is not None else None, self._stream()),
+              self._h)
+
+    supports_early_termination = True    # softrod_config.early_termination runs in the step kernels' epilogue
 
     def _readout(self, entry: str, rods: int, *tail: int, args: tuple = ()) -> torch.Tensor:
         """One per-rod read-out softrod_<entry>: its (n_envs, rods, *tail) float64 device buffer, allocated on first
@@ -579,9 +637,12 @@ class HipRodBackend:
 
     def step_packed(self, actions, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """softrod_step_packed: (n_envs, packed_width(obs_dim)) float32 words per env, into
-        `out` if given (the overlapped multi-GPU path alternates two buffers)."""
+        `out` if given (the overlapped multi-GPU path alternates two buffers).  NotImplementedError while episode
+        statistics are on: the packed row keeps reward and flags as float32 words, not the buffers the update reads."""
         from .distributed import packed_width
 
+        if self.episode_stats is not None:
+            raise NotImplementedError("step_packed with episode statistics on (episode_stats_enable(0) switches them off)")
         a = self._actions(actions)
         if out is None:
             if getattr(self, "packed", None) is None:

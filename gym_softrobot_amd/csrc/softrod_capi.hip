@@ -20,6 +20,7 @@
 #include "softrod_dynamics_readout.hpp"
 #include "softrod_copy_envs.hpp"
 #include "softrod_state_bank.hpp"
+#include "softrod_episode_stats.hpp"
 #include "softrod_shape.hpp"
 #include "softrod_reset_shapes.hpp"
 
@@ -140,6 +141,9 @@ struct softrod_handle {
     hipEvent_t ev_pairs = nullptr;  // guards reuse of h_pairs
     std::vector<uint8_t> is_dst;    // [N] scratch of its validation, all zero between calls
     StateBank bank;                 // softrod_bank_create
+    // episode statistics (softrod_episode_stats_enable): one device block carved into the arrays of EpisodeStats
+    EpisodeStats stats{};           // stats.ring == 0: off
+    void* d_stats = nullptr;        // the block
     // planar certificates (StatePtrs.planar_cert, softrod_planar.hpp)
     bool cert_on = true;            // softrod_set_planar_certificates; softrod_state_view_get switches it off for good
     bool cert_live = false;         // a launch since the last clear may have issued certificates
@@ -2405,6 +2409,84 @@ int softrod_bank_info(softrod_handle* h, int32_t* slots, uint64_t* bytes_per_slo
     return SOFTROD_OK;
 }
 
+// ---- episode statistics (softrod_episode_stats.hpp) ----
+int softrod_episode_stats_enable(softrod_handle* h, int ring) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "episode stats: null handle");
+    if (ring < 0) return fail(h, SOFTROD_EINVAL, "episode stats: ring " + std::to_string(ring) + " is negative");
+    SR_ON_DEVICE(h);
+    // one block, every array at a multiple of 256 bytes: [N] arrays first, then the ring, then count
+    const size_t N = (size_t)h->cfg.n_envs, K = (size_t)ring;
+    size_t bytes = 0;
+    auto carve = [&bytes](size_t n) { const size_t at = bytes; bytes += (n + 255) & ~(size_t)255; return at; };
+    const size_t o_acc_r = carve(N * 8), o_acc_l = carve(N * 4), o_latch = carve(N), o_fin = carve(N * 4),
+                 o_ep_r = carve(N * 8), o_ep_l = carve(N * 4), o_ep_t = carve(N * 8), o_ep_m = carve(N),
+                 o_ring_r = carve(K * 8), o_ring_l = carve(K * 4), o_ring_t = carve(K * 8), o_ring_e = carve(K * 4),
+                 o_count = carve(8);
+    unsigned char* block = nullptr;
+    if (ring > 0) {
+        hipError_t e = hipMalloc((void**)&block, bytes);
+        if (e == hipSuccess) e = hipMemset(block, 0, bytes);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {          // the handle stays as it was
+            (void)hipGetLastError();
+            if (block) (void)hipFree(block);
+            return fail(h, e == hipErrorOutOfMemory ? SOFTROD_ENOMEM : SOFTROD_EHIP, std::string("episode stats: ") + hipGetErrorString(e));
+        }
+    }
+    if (h->d_stats) (void)hipFree(h->d_stats);      // waits for the device: no kernel still writes the old arrays
+    h->d_stats = block;
+    h->stats = EpisodeStats{};
+    if (!block) return SOFTROD_OK;
+    EpisodeStats& S = h->stats;
+    S.acc_return = (double*)(block + o_acc_r); S.acc_length = (int*)(block + o_acc_l);
+    S.latch = block + o_latch; S.finished = (int*)(block + o_fin);
+    S.ep_r = (double*)(block + o_ep_r); S.ep_l = (int*)(block + o_ep_l);
+    S.ep_t = (double*)(block + o_ep_t); S.ep_mask = block + o_ep_m;
+    S.ring_r = (double*)(block + o_ring_r); S.ring_l = (int*)(block + o_ring_l);
+    S.ring_t = (double*)(block + o_ring_t); S.ring_env = (int*)(block + o_ring_e);
+    S.count = (unsigned long long*)(block + o_count);
+    S.n_envs = h->cfg.n_envs;
+    S.ring = ring;
+    return SOFTROD_OK;
+}
+
+int softrod_episode_stats_update(softrod_handle* h, const double* reward, const uint8_t* terminated, const uint8_t* truncated,
+                                 const double* end_time, int mode, void* stream) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "episode stats: null handle");
+    if (!h->stats.ring) return fail(h, SOFTROD_EINVAL, "episode stats: the feature is off (softrod_episode_stats_enable)");
+    if (!reward || !terminated || !truncated) return fail(h, SOFTROD_EINVAL, "episode stats: null reward, terminated or truncated");
+    if (mode < 0 || mode > 2) return fail(h, SOFTROD_EINVAL, "episode stats: mode " + std::to_string(mode) + " is outside 0 .. 2");
+    SR_ON_DEVICE(h);
+    hipLaunchKernelGGL(softrod_episode_stats_kernel, dim3(1), dim3(kStatsThreads), 0, (hipStream_t)stream, h->stats, reward,
+                       terminated, truncated, end_time, mode);
+    SR_HIP(h, hipGetLastError());
+    return SOFTROD_OK;
+}
+
+int softrod_episode_stats_reset(softrod_handle* h, const uint8_t* mask, void* stream) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "episode stats: null handle");
+    if (!h->stats.ring) return fail(h, SOFTROD_EINVAL, "episode stats: the feature is off (softrod_episode_stats_enable)");
+    SR_ON_DEVICE(h);
+    hipLaunchKernelGGL(softrod_episode_stats_clear_kernel, dim3((unsigned)((h->cfg.n_envs + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, h->stats, mask);
+    SR_HIP(h, hipGetLastError());
+    return SOFTROD_OK;
+}
+
+int softrod_episode_stats_view(softrod_handle* h, struct softrod_episode_stats_view* out) {
+    if (!h) return fail(h, SOFTROD_EINVAL, "episode stats: null handle");
+    if (!out) return fail(h, SOFTROD_EINVAL, "episode stats: null argument");
+    if (!h->stats.ring) return fail(h, SOFTROD_EINVAL, "episode stats: the feature is off (softrod_episode_stats_enable)");
+    const EpisodeStats& S = h->stats;
+    out->acc_return = S.acc_return; out->acc_length = S.acc_length; out->latch = S.latch; out->finished = S.finished;
+    out->ep_r = S.ep_r; out->ep_l = S.ep_l; out->ep_t = S.ep_t; out->ep_mask = S.ep_mask;
+    out->ring_r = S.ring_r; out->ring_l = S.ring_l; out->ring_t = S.ring_t; out->ring_env = S.ring_env;
+    out->count = (uint64_t*)S.count;
+    out->n_envs = S.n_envs;
+    out->ring = S.ring;
+    return SOFTROD_OK;
+}
+
 namespace {
 // The env's target, where its kind has one: the point softrod_render draws (render.py draws the same) and
 // softrod_rod_clearance measures to.
@@ -2770,6 +2852,7 @@ int softrod_destroy(softrod_handle* h) {
     if (h->h_pairs) (void)hipHostFree(h->h_pairs);
     if (h->ev_pairs) (void)hipEventDestroy(h->ev_pairs);
     h->bank.release();
+    if (h->d_stats) (void)hipFree(h->d_stats);
     delete h;
     return SOFTROD_OK;
 }

@@ -355,6 +355,27 @@ def rod_clearance_views(buf, has_target: bool = True) -> RodClearance:
     return RodClearance(rods[..., 0], rods[..., 1], rods[..., 2:4], rods[..., 4:6], *target)
 
 
+class EpisodeStatistics(NamedTuple):
+    """What episode_statistics() returns (softrod_episode_stats_*, include/softrod.h), NumPy values: count = episodes
+    finished by the whole batch since record_episode_statistics(); returns (m,) float64, lengths (m,) int32, times (m,)
+    float64 — the simulated end time, the env clock — and envs (m,) int32, the env each episode ran in: the last
+    m = min(count, buffer_length) finished episodes in chronological order, oldest first (within one step the finished
+    envs in ascending env index); finished (N,) int32, the episodes ended per env."""
+    count: int
+    returns: np.ndarray
+    lengths: np.ndarray
+    times: np.ndarray
+    envs: np.ndarray
+    finished: np.ndarray
+
+
+def episode_ring_order(count: int, ring: int) -> np.ndarray:
+    """The ring's slots in chronological order, oldest first: finished episode number c (0-based) sits in slot
+    c % ring, so the last min(count, ring) episodes are numbers max(0, count - ring) .. count - 1."""
+    count, ring = int(count), int(ring)
+    return np.arange(max(0, count - ring), count, dtype=np.int64) % ring
+
+
 def _z_rotation(vector, theta):
     """joint.py:7-17."""
     theta = theta / 180.0 * np.pi

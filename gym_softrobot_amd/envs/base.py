@@ -403,6 +403,7 @@ class VecRodEnvBase:
         self._status_in_flight = False
         self.top_up_paused = False     # True: the caller reads the queue counters and stages records itself (tests)
         self._reset_shapes = 0         # entries of the pool of start shapes (set_reset_shapes); 0: straight starts
+        self._episode_ring = 0         # ring length of the episode statistics (record_episode_statistics); 0: off
         if self.same_step and not hasattr(self.backend, "autoreset_same_step"):
             raise NotImplementedError(f"same-step auto-reset needs the HIP backend, not {type(self.backend).__name__}")
         if self.device_autoreset:
@@ -603,6 +604,8 @@ class VecRodEnvBase:
                     self._popped[i] += 1
             self.backend.queue_advance(by)
         self._reset_backend(m, mask is not None, draws)
+        if self._episode_ring:      # a manual reset discards a partial episode and opens the latch
+            self.backend.episode_stats_reset(m if mask is not None else None)
         if self._reset_shapes:
             self._apply_reset_shapes(m if mask is not None else None, reseeded)
         self._steps[m] = 0
@@ -662,6 +665,8 @@ class VecRodEnvBase:
         infos = {"time": self._out(self._dev_time), "TimeLimit.truncated": self._out(tl)}
         if self.same_step:
             infos.update(self._final_infos(term, trunc))
+        if self._episode_ring:
+            infos.update(self._episode_infos())
         return (self._out(obs), self._out(reward), self._out(term.view(torch.bool)),
                 self._out(trunc.view(torch.bool)), infos)
 
@@ -722,6 +727,8 @@ class VecRodEnvBase:
             self.recorder.record()
         times = self._times()
         infos = self._infos(times)
+        if self._episode_ring:
+            infos.update(self._episode_infos())
         return (
             self._out(obs),
             self._out(reward),
@@ -1144,6 +1151,78 @@ class VecRodEnvBase:
         out = be.render(cam, depth=bool(depth))
         return (self._out(out[0]), self._out(out[1])) if depth else self._out(out)
 
+    # -- episode statistics: returns and lengths of finished episodes, kept on the device ---------
+    def record_episode_statistics(self, buffer_length: int = 100) -> None:
+        """Keep the return, length and end time of every episode that ends, on the device: what Gymnasium's
+        RecordEpisodeStatistics does for a host env, for a resident batch under every reset mode — by hand,
+        autoreset=True, "device" and "same_step" — where the host never sees which env finished on which call.
+        Upstream has a single env and no statistics.  `buffer_length` >= 1 switches them on (or on anew: everything
+        starts from zero, episodes under way are counted from this call) with a ring of that many recent episodes; 0
+        switches them off.  One cold kernel behind every step (csrc/softrod_episode_stats.hpp), none while they are off.
+
+        While they are on step() adds Gymnasium's vector keys to `infos`:
+          infos["episode"] = {"r": (N,) float64 return, "l": (N,) int32 length in steps, "t": (N,) float64}
+          infos["_episode"]  (N,) bool, True for the envs whose episode ended on this call
+        with zero rows where `_episode` is False.  "t" is the episode's SIMULATED end time — the env clock at its last
+        step — not elapsed wall-clock time as in Gymnasium's wrapper.  Device views overwritten by the next call (NumPy
+        copies with numpy_output=True); `episode_info` gives the same views to a capture_policy_step loop, whose
+        replay() keeps returning its four tensors.  Under NEXT_STEP auto-reset (True or "device") the call that
+        returns an env's reset observation counts in no episode.  reset(mask=...) discards the masked envs' partial
+        episodes; with autoreset=False an env that has finished is ignored until it is reset.  episode_statistics()
+        reads the ring.
+
+        Out of scope: step_packed raises NotImplementedError while statistics are on; not offered on the sharded env;
+        not part of state_dict(), snapshot(), fork() or the state bank — a forked or loaded env keeps its own
+        accumulators, so reset(mask=...) or a new record_episode_statistics() is the way to clear them; no reward or
+        observation normalisation; no single-env wrapper (Gymnasium's own serves those).  A graph captured with
+        capture_policy_step must be captured again after this call.
+
+        ValueError for a negative length; NotImplementedError on a backend other than the HIP one."""
+        ring = int(buffer_length)
+        if ring < 0:
+            raise ValueError(f"record_episode_statistics: buffer_length {ring} is negative")
+        be = self.backend
+        if not hasattr(be, "episode_stats_enable"):
+            raise NotImplementedError(f"episode statistics need the HIP backend, not {type(be).__name__}")
+        mode = (_capi.EPISODE_STATS_SAME_STEP if self.same_step
+                else _capi.EPISODE_STATS_NEXT_STEP if self.autoreset or self.device_autoreset
+                else _capi.EPISODE_STATS_MANUAL)
+        be.episode_stats_enable(ring, mode)
+        self._episode_ring = ring
+
+    def _episode_infos(self) -> Dict[str, Any]:
+        import torch
+
+        st = self.backend.episode_stats
+        return {"episode": {"r": self._out(st["ep_r"]), "l": self._out(st["ep_l"]), "t": self._out(st["ep_t"])},
+                "_episode": self._out(st["ep_mask"].view(torch.bool))}
+
+    @property
+    def episode_info(self) -> Dict[str, Any]:
+        """The infos["episode"] / infos["_episode"] entries of the last step or replay (record_episode_statistics):
+        {"episode": {"r", "l", "t"}, "_episode"}.  The device views are the same objects' memory at every call."""
+        if not self._episode_ring:
+            raise _capi.SoftrodError("episode statistics are off (record_episode_statistics)")
+        return self._episode_infos()
+
+    def episode_statistics(self):
+        """EpisodeStatistics(count, returns, lengths, times, envs, finished) as NumPy values (diagnostics.py): the
+        number of episodes the batch has finished since record_episode_statistics(), the last min(count,
+        buffer_length) of them in chronological order, oldest first — return, length, simulated end time and env —
+        and the episodes ended per env.  The logging call: it waits for the env's stream."""
+        from ..diagnostics import EpisodeStatistics, episode_ring_order
+
+        if not self._episode_ring:
+            raise _capi.SoftrodError("episode statistics are off (record_episode_statistics)")
+        import torch
+
+        st = self.backend.episode_stats
+        torch.cuda.synchronize(self.backend.device)
+        count = int(st["count"].cpu()[0])
+        order = episode_ring_order(count, self._episode_ring)
+        ring = [st[k].cpu().numpy()[order] for k in ("ring_r", "ring_l", "ring_t", "ring_env")]
+        return EpisodeStatistics(count, *ring, st["finished"].cpu().numpy().copy())
+
     def capture_policy_step(self, policy):
         """One HIP graph for `actions = policy(obs); step(actions)` — the launch-bound tail of an on-device
         rollout (a small policy is half a dozen tiny kernels per step) becomes ONE graph launch per env.step.
@@ -1160,7 +1239,9 @@ class VecRodEnvBase:
         bit-identical to the eager loop (tests/test_gpu_policy_loop.py, tests/test_gpu_same_step.py).
         The kernel arguments (RodParams, array pointers) are baked into the graph BY VALUE at capture: after
         anything that changes them (a radius profile, an action basis, enabling auto-reset, enabling per-env material or contact,
-        setting or clearing a pool of start shapes with set_reset_shapes) capture again.  Once per-env material is on, later set_material calls update its table in place: replays
+        setting or clearing a pool of start shapes with set_reset_shapes, switching episode statistics on or off with
+        record_episode_statistics) capture again.  With episode statistics on their update is one more kernel of the captured line and
+        `episode_info` holds its rows after every replay.  Once per-env material is on, later set_material calls update its table in place: replays
         issued on the env's stream see them.  The same holds for per-env contact (set_contact).
         Kernel timing (set_timing) is switched off by the capture and stays off."""
         import torch
@@ -1198,7 +1279,8 @@ class VecRodEnvBase:
 
     def step_packed(self, actions, out=None):
         """step() with every per-env output in one (N, packed_width) float32 buffer written
-        by the kernel itself (distributed.unpack_outputs gives views); no host auto-reset."""
+        by the kernel itself (distributed.unpack_outputs gives views); no host auto-reset.  NotImplementedError while
+        episode statistics are on (record_episode_statistics)."""
         import torch
 
         if self.autoreset:

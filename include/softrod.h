@@ -1221,6 +1221,63 @@ int softrod_apply_reset_shapes(softrod_handle* h, const uint8_t* mask, void* str
 int softrod_reset_shapes_view(softrod_handle* h, int32_t** index, int32_t** episode);
 uint32_t softrod_reset_shape_index(uint64_t seed, uint32_t env, uint32_t episode, uint32_t count);
 
+/* EPISODE STATISTICS on the device: the return, length and end time of every episode that ends, and a ring of the last
+ * `ring` finished episodes of the batch.  No reference counterpart: upstream has a single env and no statistics (a
+ * single Gymnasium env takes gymnasium.wrappers.RecordEpisodeStatistics; that wrapper cannot wrap a batch of device
+ * tensors, and in the device reset modes the host never sees which env finished on which call).  One cold kernel per
+ * env.step, softrod_episode_stats_kernel (csrc/softrod_episode_stats.hpp says what it keeps and in which order), on the
+ * caller's stream behind softrod_step.  softrod_step itself is unchanged and launches nothing for this: the update is
+ * the caller's call, and nothing runs while the feature is off.
+ *
+ *   softrod_episode_stats_enable(h, ring)
+ *       ring >= 1: allocates the resident arrays — acc_return f64, acc_length i32, latch u8, finished i32, the call's
+ *       info rows ep_r f64, ep_l i32, ep_t f64, ep_mask u8, all [n_envs]; ring_r f64, ring_l i32, ring_t f64,
+ *       ring_env i32, all [ring]; count u64 [1] — all zero.  On a handle that has them already they are released and
+ *       allocated anew (the pointers of an earlier softrod_episode_stats_view die; a graph captured with the update in
+ *       it must be captured again).  ring == 0: switches the feature off and releases them.  Waits for the device; not
+ *       capturable.  softrod_destroy releases them too.  SOFTROD_ENOMEM / SOFTROD_EHIP leave the handle as it was.
+ *   softrod_episode_stats_update(h, reward, terminated, truncated, end_time, mode, stream)
+ *       one update from the outputs of the softrod_step before it: DEVICE reward f64 [n_envs], terminated and truncated
+ *       u8 [n_envs], end_time f64 [n_envs] or NULL (t = 0) — the env clock row (softrod_state_view.time) in modes 0 and
+ *       1, softrod_final_view's final_time in mode 2.  mode 0: the caller resets finished envs by hand (an env that
+ *       finished is ignored until softrod_episode_stats_reset names it); 1: NEXT_STEP auto-reset (the call after an
+ *       env's last step is its reset call and counts in no episode); 2: SAME_STEP auto-reset (the env's next episode
+ *       starts with the next call).  Within a call the finished envs enter the ring in ascending env index; finished
+ *       episode number c since enabling (0-based) is in slot c % ring.  One kernel of one workgroup: its cost grows
+ *       with ceil(n_envs / 1024).  It only enqueues work — no allocation, synchronisation or host read: capturable.
+ *   softrod_episode_stats_reset(h, mask, stream)
+ *       mask: DEVICE u8 [n_envs], or NULL: every env.  Zeroes acc_return, acc_length, latch and the info rows of those
+ *       envs: a manual reset discards a partial episode.  The ring, finished and count stay.  Capturable.
+ *   softrod_episode_stats_view(h, &view)
+ *       the device pointers, n_envs and ring; good until the next softrod_episode_stats_enable or softrod_destroy.
+ * Errors, each SOFTROD_EINVAL and found before a device is looked for (a refused call changes nothing):
+ *   "episode stats: null handle", "episode stats: ring <k> is negative",
+ *   "episode stats: the feature is off (softrod_episode_stats_enable)" (update, reset, view),
+ *   "episode stats: null reward, terminated or truncated", "episode stats: mode <m> is outside 0 .. 2",
+ *   "episode stats: null argument" (view).                                                                          */
+struct softrod_episode_stats_view {      /* a struct tag only: the entry point of the same name fills it */
+    double* acc_return;
+    int32_t* acc_length;
+    uint8_t* latch;
+    int32_t* finished;
+    double* ep_r;
+    int32_t* ep_l;
+    double* ep_t;
+    uint8_t* ep_mask;
+    double* ring_r;
+    int32_t* ring_l;
+    double* ring_t;
+    int32_t* ring_env;
+    uint64_t* count;
+    int32_t n_envs;
+    int32_t ring;
+};
+int softrod_episode_stats_enable(softrod_handle* h, int ring);
+int softrod_episode_stats_update(softrod_handle* h, const double* reward, const uint8_t* terminated, const uint8_t* truncated,
+                                 const double* end_time, int mode, void* stream);
+int softrod_episode_stats_reset(softrod_handle* h, const uint8_t* mask, void* stream);
+int softrod_episode_stats_view(softrod_handle* h, struct softrod_episode_stats_view* out);
+
 /* Run `n` bare PositionVerlet substeps with fixed per-env forcing inputs and no
  * env epilogue (the inner loop of soft_pendulum.py:183-184 alone); `actions`
  * (device [n_envs] float32 or NULL) feeds SOFTROD_FEAT_POINT_FORCE_NODE0_X.
