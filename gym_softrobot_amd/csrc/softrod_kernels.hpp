@@ -669,6 +669,11 @@ __device__ __forceinline__ void sanitize_unused_rates(const RodParams& P, int la
 // past the last element feeds the tip node's element -> node average: a non-finite value written
 // into the unused slots through the state view would turn those zero factors into NaN (0 x NaN).
 // Positions, directors past the rod's end that are not finite become 0, the rates there exact zeros.
+// "Finite" is not enough: the zero factors multiply PRODUCTS of these values (Q t with t = d / 1, the series of
+// theta_over_sin in y = (3 - tr Q+ Q^T) / 4, to its 19th power), and two values of 1e300 multiply to inf before the zero
+// factor sees them — a NaN in the tip node's force and the last element's couple (tests/test_gpu_dyn_probe.py found it).
+// So the bounds are what a rod can hold: a director entry is at most 1 (2 lets rounding and a drifted frame through),
+// a coordinate is taken up to 1e8 m; every product behind them then stays far inside the double range.
 template <int EPL>
 __device__ __forceinline__ void sanitize_unused_slots(const RodParams& P, int lane, LaneN<EPL>& L) {
     sanitize_unused_rates<EPL>(P, lane, L);
@@ -677,10 +682,10 @@ __device__ __forceinline__ void sanitize_unused_slots(const RodParams& P, int la
         const int idx = slot_local(P, lane * EPL + s);
 #pragma unroll
         for (int c = 0; c < 3; ++c)
-            L.x[s][c] = (idx <= P.n_elem || fabs(L.x[s][c]) <= 1.0e300) ? L.x[s][c] : 0.0;
+            L.x[s][c] = (idx <= P.n_elem || fabs(L.x[s][c]) <= 1.0e8) ? L.x[s][c] : 0.0;
 #pragma unroll
         for (int c = 0; c < 9; ++c)
-            L.Q[s][c] = (idx < P.n_elem || fabs(L.Q[s][c]) <= 1.0e300) ? L.Q[s][c] : 0.0;
+            L.Q[s][c] = (idx < P.n_elem || fabs(L.Q[s][c]) <= 2.0) ? L.Q[s][c] : 0.0;
     }
 }
 

@@ -291,6 +291,32 @@ __device__ __forceinline__ void planar_prove(const RodParams& P, const StatePtrs
     nan_out = bad;
 }
 
+// planar_dynamic_n keeps its masks as zero stiffnesses, so what the slots behind the rod hold is multiplied by zero, not
+// skipped: it has to be finite, and small enough for its products to stay finite (the 3-D kernels' sanitize_unused_slots,
+// softrod_kernels.hpp, for the same reason).  Memory behind the rod is whatever the last writer left — a reset writes a
+// continuation of the rod there, softrod_state_view lets anything through — so the way into the loop makes it so: behind
+// the last element a director or edge component that no rod can hold (NaN, inf, |c| > 2, |d| > 1e8) becomes 0 and the
+// rotation rate is 0; behind the last vertex the bending angle is 0; behind the last node the velocity is 0.  Anything
+// finite stays as it is, so a rod that was reset keeps every byte.  Once per launch, nothing in the substep.
+template <int EPL>
+__device__ __forceinline__ void planar_sanitize_unused(const RodParams& P, int lane, PlanarN<EPL>& Z) {
+    const int n = P.n_elem;
+#pragma unroll
+    for (int s = 0; s < EPL; ++s) {
+        const int idx = lane * EPL + s;
+        Z.c[s] = (idx < n || fabs(Z.c[s]) <= 2.0) ? Z.c[s] : 0.0;
+        Z.s[s] = (idx < n || fabs(Z.s[s]) <= 2.0) ? Z.s[s] : 0.0;
+        Z.wz[s] = (idx < n) ? Z.wz[s] : 0.0;
+        Z.dl[s] = (idx < n - 1) ? Z.dl[s] : 0.0;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            Z.v[s][c] = (idx <= n) ? Z.v[s][c] : 0.0;
+            Z.d[s][c] = (idx < n || fabs(Z.d[s][c]) <= 1.0e8) ? Z.d[s][c] : 0.0;
+            Z.dv[s][c] = (idx < n || fabs(Z.dv[s][c]) <= 1.0e8) ? Z.dv[s][c] : 0.0;
+        }
+    }
+}
+
 // The planar state Z of a rod from planar_load_state's L and d2_z's sign; per lane: d3 is a unit vector to 1e-12 on
 // every element (the one comparison a certificate does not stand for).
 template <int EPL>
@@ -334,6 +360,7 @@ __device__ __forceinline__ bool planar_from_lane(const RodParams& P, int lane, c
             Z.dl[s] = vor_valid ? atan2(sinD, cosD) : 0.0;
         }
     }
+    planar_sanitize_unused<EPL>(P, lane, Z);
 #ifdef SOFTROD_DIAG_NO_PLANAR
     return false;
 #endif
@@ -487,7 +514,8 @@ __device__ __forceinline__ void planar_dynamic_n(const RodParams& P, const Const
     for (int s = 0; s < EPL; ++s) {
         d[s][0] = Z.d[s][0];
         d[s][1] = Z.d[s][1];
-        // slots past the last element have d = 0: clamped, they stay finite and their zero
+        // slots past the last element hold what memory held there, made finite at kernel entry
+        // (planar_sanitize_unused); |d|^2 is clamped from below, so they stay finite and their zero
         // stiffnesses keep them out of every sum
         const double dd = fmax(fma(d[s][1], d[s][1], d[s][0] * d[s][0]), 1.0e-20);
         const double r = rsqrt3(dd);
