@@ -9,6 +9,7 @@ host round trip inside the rollout.
 
     python examples/soft_pendulum_3d_ppo.py --num-envs 1024 --updates 30
     python examples/soft_pendulum_3d_ppo.py --num-envs 1024 --updates 30 --start-shapes 16     # bent starts, every episode
+    python examples/soft_pendulum_3d_ppo.py --num-envs 1024 --updates 30 --normalize           # VecNormalize, on the device
 
 Plain PPO (clipped surrogate, GAE); nothing here is tuned — it is a usage example.
 """
@@ -52,6 +53,9 @@ def main():
     ap.add_argument("--start-shapes", type=int, default=0, metavar="K",
                     help="train from a pool of K bent start shapes (exploring starts): every episode, the ones the device "
                          "restarts included, begins from one of them (env.set_reset_shapes)")
+    ap.add_argument("--normalize", action="store_true",
+                    help="normalise observations and rewards with running statistics kept on the device "
+                         "(env.set_normalization: what VecNormalize does for host envs)")
     args = ap.parse_args()
 
     torch.manual_seed(args.seed)
@@ -83,6 +87,10 @@ def main():
     val_buf = torch.empty((T + 1, N), device=dev)
 
     env.record_episode_statistics(100)                # returns and lengths of finished episodes, kept on the device
+    if args.normalize:
+        # obs, info["final_obs"] and the reward come back normalised (the raw ones are info["raw_obs"], ["raw_final_obs"],
+        # ["raw_reward"]); the episode statistics below keep reporting raw returns
+        env.set_normalization(gamma=args.gamma)
     obs, _ = env.reset(seed=args.seed)
     obs = obs.clone()
     for update in range(args.updates):
@@ -133,7 +141,7 @@ def main():
         recent = (f"episodes {ep.count:6d}  mean return {ep.returns.mean():+.3f}  mean length {ep.lengths.mean():.1f}  "
                   if ep.count else "episodes      0  ")
         print(f"update {update + 1:3d}  env-steps {steps:9d}  {recent}mean reward/step {rew_buf.mean().item():+.4f}  "
-              f"mean tilt {obs_buf[..., 8].mean().item():.4f}  rollout {T * N / t_roll:,.0f} env-steps/s (policy included)")
+              f"mean {'normalised ' if args.normalize else ''}tilt {obs_buf[..., 8].mean().item():.4f}  rollout {T * N / t_roll:,.0f} env-steps/s (policy included)")
     env.close()
 
 

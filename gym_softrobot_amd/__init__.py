@@ -24,7 +24,7 @@ from .envs import (
     VecSoftPendulumEnv,
 )
 from ._capi import reset_shape_index       # which pool entry a reset starts from (set_reset_shapes)
-from .diagnostics import EpisodeStatistics, RodClearance
+from .diagnostics import EpisodeStatistics, NormalizationState, RodClearance
 from .registration import make, parity_label, register, registered
 
 __version__ = "0.2.0"
@@ -86,5 +86,5 @@ def make_vec(id: str, num_envs: int, **kwargs):  # noqa: A002
 __all__ = [
     "SoftPendulumEnv", "VecSoftPendulumEnv", "SoftPendulum3DEnv", "VecSoftPendulum3DEnv",
     "ArmSingleEnv", "VecArmSingleEnv", "FlatEnv", "VecOctoFlatEnv", "SoftArmTrackingEnv", "VecSoftArmTrackingEnv", "ArmPushEnv", "VecArmPushEnv", "ArmPullWeightEnv", "VecArmPullWeightEnv", "CrawlEnv", "VecCrawlEnv", "ArmTwoEnv", "VecArmTwoEnv", "ReachEnv", "VecReachEnv", "parity_label", "make", "make_vec", "register", "registered", "_capi",
-    "RodClearance", "EpisodeStatistics", "reset_shape_index",
+    "RodClearance", "EpisodeStatistics", "NormalizationState", "reset_shape_index",
 ]

@@ -215,6 +215,25 @@ class SoftrodEpisodeStatsView(C.Structure):
     _fields_ = [(name, C.c_void_p) for name, _, _ in EPISODE_STATS_ARRAYS] + [("n_envs", C.c_int32), ("ring", C.c_int32)]
 
 
+# the arrays of `struct softrod_normalize_view`, in its order: (name, typestr, shape letters: "d" per observation
+# column, "n" per env, "1")
+NORMALIZE_ARRAYS = (
+    ("obs_mean", "<f8", "d"), ("obs_var", "<f8", "d"), ("obs_count", "<f8", "d"), ("obs_inv_std", "<f8", "d"),
+    ("ret_mean", "<f8", "1"), ("ret_var", "<f8", "1"), ("ret_count", "<f8", "1"), ("ret_inv_std", "<f8", "1"),
+    ("ret", "<f8", "n"), ("latch", "|u1", "n"),
+    ("norm_obs", "<f4", "nd"), ("norm_final_obs", "<f4", "nd"), ("norm_reward", "<f8", "n"),
+)
+NORMALIZE_MANUAL, NORMALIZE_NEXT_STEP, NORMALIZE_SAME_STEP = 0, 1, 2      # softrod_normalize_step's mode
+
+
+class SoftrodNormalizeView(C.Structure):
+    """Mirror of `struct softrod_normalize_view` (include/softrod.h)."""
+
+    _fields_ = ([(name, C.c_void_p) for name, _, _ in NORMALIZE_ARRAYS]
+                + [(name, C.c_int32) for name in ("n_envs", "obs_dim", "obs_on", "reward_on")]
+                + [(name, C.c_double) for name in ("gamma", "clip_obs", "clip_reward", "epsilon")])
+
+
 class SoftrodCamera(C.Structure):
     """Mirror of `struct softrod_camera` (include/softrod.h, softrod_render): the orthographic camera all envs of a
     handle share."""
@@ -1149,6 +1168,11 @@ _EXPORTS = {
     "softrod_episode_stats_update": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, _VP]),
     "softrod_episode_stats_reset": (C.c_int, [_VP, _VP, _VP]),
     "softrod_episode_stats_view": (C.c_int, [_VP, C.POINTER(SoftrodEpisodeStatsView)]),
+    "softrod_normalize_enable": (C.c_int, [_VP, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "softrod_normalize_step": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP]),
+    "softrod_normalize_reset": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP]),
+    "softrod_normalize_view": (C.c_int, [_VP, C.POINTER(SoftrodNormalizeView)]),
+    "softrod_normalize_load": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "softrod_camera_default": (C.c_int, [C.POINTER(SoftrodConfig), C.POINTER(SoftrodCamera)]),
     "softrod_camera_check": (C.c_int, [C.POINTER(SoftrodCamera)]),
     "softrod_render": (C.c_int, [_VP, C.POINTER(SoftrodCamera), _VP, _VP, _VP]),

@@ -469,6 +469,9 @@ class HipRodBackend:
             self.episode_stats_update(self.reward, self.terminated, self.truncated,
                                       self.final_time if self.episode_stats_mode == _capi.EPISODE_STATS_SAME_STEP
                                       else self._episode_clock, self.episode_stats_mode)
+        if self.normalize is not None and self.normalize_in_step:      # softrod_normalize_step behind it, same stream
+            self.normalize_step(self.obs, self.reward, self.terminated, self.truncated,
+                                getattr(self, "final_obs", None) if self.normalize_mode == _capi.NORMALIZE_SAME_STEP else None)
         return self.obs, self.reward, self.terminated, self.truncated
 
     # -- episode statistics (softrod_episode_stats_enable / _update / _reset / _view) ------------------
@@ -524,6 +527,77 @@ class HipRodBackend:
             m = m.reshape(self.n_envs).contiguous()
         check(self._lib.softrod_episode_stats_reset(self._h, m.data_ptr() if m is not None else None, self._stream()),
               self._h)
+
+    # -- observation / reward normalisation (softrod_normalize_enable / _step / _reset / _view / _load) ----------
+    normalize: Optional[Dict[str, torch.Tensor]] = None     # the resident arrays while the feature is on
+    normalize_obs_on = normalize_reward_on = False
+    normalize_mode = _capi.NORMALIZE_MANUAL                 # what step() passes as `mode`
+    normalize_in_step = True            # False: the caller runs normalize_step itself (the host-driven NEXT_STEP loop)
+    normalize_update = True             # False: evaluation, step() and reset passes leave the statistics alone
+
+    def normalize_enable(self, obs: bool = True, reward: bool = True, *, gamma: float = 0.99, clip_obs: float = 10.0,
+                         clip_reward: float = 10.0, epsilon: float = 1e-8, mode: Optional[int] = None,
+                         in_step: bool = True) -> None:
+        """softrod_normalize_enable: allocates (or allocates anew) the running statistics — Gymnasium's RunningMeanStd
+        per observation column and one for the discounted return — and the output buffers; obs = reward = False
+        switches the feature off and frees them.  While it is on `normalize` holds zero-copy device views of every array
+        (_capi.NORMALIZE_ARRAYS) — new ones after every call — and, with `in_step`, step() runs normalize_step behind
+        softrod_step (and behind the episode statistics, which keep reading the raw reward) on its own obs / reward /
+        flags, `final_obs` in SAME_STEP mode, `mode` (None: SAME_STEP on a same-step handle, NEXT_STEP with device
+        auto-reset, else MANUAL) and `normalize_update`.  A loop that composes its rows on the host after the step
+        (host-driven NEXT_STEP) passes in_step=False and calls normalize_step itself.  While it is off step() does
+        one attribute test and nothing else.  A captured graph must be captured again after the call."""
+        check(self._lib.softrod_normalize_enable(self._h, int(bool(obs)), int(bool(reward)), float(gamma), float(clip_obs),
+                                                 float(clip_reward), float(epsilon)), self._h)
+        self.normalize = None
+        self.normalize_obs_on, self.normalize_reward_on = bool(obs), bool(reward)
+        if not (obs or reward):
+            return
+        v = _capi.SoftrodNormalizeView()
+        check(self._lib.softrod_normalize_view(self._h, C.byref(v)), self._h)
+        size = {"n": (self.n_envs,), "d": (self.obs_dim,), "nd": (self.n_envs, self.obs_dim), "1": (1,)}
+        if mode is None:
+            mode = (_capi.NORMALIZE_SAME_STEP if getattr(self, "same_step", False)
+                    else _capi.NORMALIZE_NEXT_STEP if getattr(self, "queue_depth", 0) else _capi.NORMALIZE_MANUAL)
+        self.normalize_mode = int(mode)
+        self.normalize_in_step = bool(in_step)
+        self.normalize = {name: torch.as_tensor(_DevArray(getattr(v, name), size[per], typestr, self), device=self.device)
+                          for name, typestr, per in _capi.NORMALIZE_ARRAYS}
+
+    def normalize_step(self, obs, reward, terminated, truncated, final_obs=None, mode: Optional[int] = None,
+                       update: Optional[bool] = None) -> None:
+        """softrod_normalize_step: one pass from contiguous device tensors obs f32 (n_envs, obs_dim), reward f64
+        (n_envs,), terminated / truncated uint8 or bool (n_envs,), final_obs f32 (n_envs, obs_dim) or None (mode 2
+        only); mode 0 manual, 1 NEXT_STEP, 2 SAME_STEP (None: normalize_mode); update False freezes the statistics
+        (None: normalize_update).  At most two kernels on the current stream; capturable.  The results are in
+        `normalize`: norm_obs, norm_final_obs, norm_reward.  step() calls it itself while normalize_in_step."""
+        ptr = lambda t: t.data_ptr() if t is not None else None     # noqa: E731
+        check(self._lib.softrod_normalize_step(
+            self._h, ptr(obs), ptr(reward), ptr(terminated), ptr(truncated), ptr(final_obs),
+            int(self.normalize_mode if mode is None else mode),
+            int(bool(self.normalize_update if update is None else update)), self._stream()), self._h)
+
+    def normalize_reset(self, obs, mask=None, update: Optional[bool] = None) -> None:
+        """softrod_normalize_reset: the pass over a reset observation obs f32 (n_envs, obs_dim): the rows of the envs with
+        mask != 0 (None: all) are counted unless the statistics are frozen, their discounted return and latch become
+        zero, and every row of norm_obs is written.  `mask`: anything (n_envs,), uploaded once unless it is a uint8 /
+        bool tensor on this device."""
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask, device=self.device)
+            if m.dtype not in (torch.uint8, torch.bool):
+                m = m != 0
+            m = m.reshape(self.n_envs).contiguous()
+        check(self._lib.softrod_normalize_reset(
+            self._h, obs.data_ptr() if obs is not None else None, m.data_ptr() if m is not None else None,
+            int(bool(self.normalize_update if update is None else update)), self._stream()), self._h)
+
+    def normalize_load(self, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count) -> None:
+        """softrod_normalize_load: set the records from host values (obs_* (obs_dim,) float64, ret_* scalars); inv_std is
+        recomputed.  Waits for the stream."""
+        o = [np.ascontiguousarray(v, dtype=np.float64).reshape(self.obs_dim) for v in (obs_mean, obs_var, obs_count)]
+        r = [np.ascontiguousarray(v, dtype=np.float64).reshape(1) for v in (ret_mean, ret_var, ret_count)]
+        check(self._lib.softrod_normalize_load(self._h, *(a.ctypes.data for a in o + r), self._stream()), self._h)
 
     supports_early_termination = True    # softrod_config.early_termination runs in the step kernels' epilogue
 
@@ -638,11 +712,14 @@ class HipRodBackend:
     def step_packed(self, actions, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """softrod_step_packed: (n_envs, packed_width(obs_dim)) float32 words per env, into
         `out` if given (the overlapped multi-GPU path alternates two buffers).  NotImplementedError while episode
-        statistics are on: the packed row keeps reward and flags as float32 words, not the buffers the update reads."""
+        statistics or normalisation are on: the packed row keeps reward and flags as float32 words, not the buffers
+        those passes read."""
         from .distributed import packed_width
 
         if self.episode_stats is not None:
             raise NotImplementedError("step_packed with episode statistics on (episode_stats_enable(0) switches them off)")
+        if self.normalize is not None:
+            raise NotImplementedError("step_packed with normalisation on (normalize_enable(False, False) switches it off)")
         a = self._actions(actions)
         if out is None:
             if getattr(self, "packed", None) is None:

@@ -21,6 +21,7 @@
 #include "softrod_copy_envs.hpp"
 #include "softrod_state_bank.hpp"
 #include "softrod_episode_stats.hpp"
+#include "softrod_normalize.hpp"
 #include "softrod_shape.hpp"
 #include "softrod_reset_shapes.hpp"
 
@@ -144,6 +145,9 @@ struct softrod_handle {
     // episode statistics (softrod_episode_stats_enable): one device block carved into the arrays of EpisodeStats
     EpisodeStats stats{};           // stats.ring == 0: off
     void* d_stats = nullptr;        // the block
+    // observation / reward normalisation (softrod_normalize_enable): one device block carved into the arrays of NormState
+    NormState norm{};               // norm.rec == nullptr: off
+    void* d_norm = nullptr;         // the block
     // planar certificates (StatePtrs.planar_cert, softrod_planar.hpp)
     bool cert_on = true;            // softrod_set_planar_certificates; softrod_state_view_get switches it off for good
     bool cert_live = false;         // a launch since the last clear may have issued certificates
@@ -2487,6 +2491,143 @@ int softrod_episode_stats_view(softrod_handle* h, struct softrod_episode_stats_v
     return SOFTROD_OK;
 }
 
+// ---- observation and reward normalisation (softrod_normalize.hpp) ----
+namespace {
+const char* const kNormOff = "normalize: the feature is off (softrod_normalize_enable)";
+int norm_refuse(softrod_handle* h, const char* what, double v, const char* why) {
+    char buf[96];
+    snprintf(buf, sizeof buf, "normalize: %s %g %s", what, v, why);
+    return fail(h, SOFTROD_EINVAL, buf);
+}
+// the records as the host writes them: [4][D + 1] rows mean, var, count, inv_std
+void norm_records(std::vector<double>& rec, size_t W, const double* mean, const double* var, const double* count,
+                  const double* ret, double epsilon) {
+    rec.resize(4 * W);
+    for (size_t d = 0; d < W; ++d) {
+        const bool last = d + 1 == W;
+        const double m = mean ? (last ? ret[0] : mean[d]) : 0.0, v = mean ? (last ? ret[1] : var[d]) : 1.0,
+                     c = mean ? (last ? ret[2] : count[d]) : 1e-4;
+        rec[d] = m; rec[W + d] = v; rec[2 * W + d] = c; rec[3 * W + d] = 1.0 / std::sqrt(v + epsilon);
+    }
+}
+}  // namespace
+
+int softrod_normalize_enable(softrod_handle* h, int obs_on, int reward_on, double gamma, double clip_obs, double clip_reward,
+                             double epsilon) {
+    const bool on = obs_on || reward_on;
+    if (on && !(gamma >= 0.0 && gamma <= 1.0)) return norm_refuse(h, "gamma", gamma, "is outside [0, 1]");
+    if (on && !(clip_obs > 0.0)) return norm_refuse(h, "clip_obs", clip_obs, "is not positive");
+    if (on && !(clip_reward > 0.0)) return norm_refuse(h, "clip_reward", clip_reward, "is not positive");
+    if (on && !(epsilon > 0.0)) return norm_refuse(h, "epsilon", epsilon, "is not positive");
+    if (!h) return fail(h, SOFTROD_EINVAL, "normalize: null handle");
+    SR_ON_DEVICE(h);
+    // one block, every array at a multiple of 256 bytes
+    const size_t N = (size_t)h->cfg.n_envs, D = (size_t)softrod_config_obs_dim(&h->cfg), W = D + 1;
+    size_t bytes = 0;
+    auto carve = [&bytes](size_t n) { const size_t at = bytes; bytes += (n + 255) & ~(size_t)255; return at; };
+    const size_t o_rec = carve(4 * W * 8), o_ret = carve(N * 8), o_latch = carve(N), o_obs = carve(N * D * 4),
+                 o_final = carve(N * D * 4), o_rew = carve(N * 8);
+    unsigned char* block = nullptr;
+    if (on) {
+        std::vector<double> rec;
+        norm_records(rec, W, nullptr, nullptr, nullptr, nullptr, epsilon);
+        hipError_t e = hipMalloc((void**)&block, bytes);
+        if (e == hipSuccess) e = hipMemset(block, 0, bytes);
+        if (e == hipSuccess) e = hipMemcpy(block + o_rec, rec.data(), rec.size() * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {          // the handle stays as it was
+            (void)hipGetLastError();
+            if (block) (void)hipFree(block);
+            return fail(h, e == hipErrorOutOfMemory ? SOFTROD_ENOMEM : SOFTROD_EHIP, std::string("normalize: ") + hipGetErrorString(e));
+        }
+    }
+    if (h->d_norm) (void)hipFree(h->d_norm);        // waits for the device: no kernel still writes the old arrays
+    h->d_norm = block;
+    h->norm = NormState{};
+    if (!block) return SOFTROD_OK;
+    NormState& S = h->norm;
+    S.rec = (double*)(block + o_rec); S.ret = (double*)(block + o_ret); S.latch = block + o_latch;
+    S.norm_obs = (float*)(block + o_obs); S.norm_final_obs = (float*)(block + o_final);
+    S.norm_reward = (double*)(block + o_rew);
+    S.n_envs = (int)N; S.obs_dim = (int)D;
+    S.obs_on = obs_on ? 1 : 0; S.reward_on = reward_on ? 1 : 0;
+    S.gamma = gamma; S.clip_obs = clip_obs; S.clip_reward = clip_reward; S.epsilon = epsilon;
+    return SOFTROD_OK;
+}
+
+int softrod_normalize_step(softrod_handle* h, const float* obs, const double* reward, const uint8_t* terminated,
+                           const uint8_t* truncated, const float* final_obs, int mode, int update, void* stream) {
+    if (mode < 0 || mode > 2) return fail(h, SOFTROD_EINVAL, "normalize: mode " + std::to_string(mode) + " is outside 0 .. 2");
+    if (!obs || !reward || !terminated || !truncated) return fail(h, SOFTROD_EINVAL, "normalize: null obs, reward, terminated or truncated");
+    if (final_obs && mode != 2) return fail(h, SOFTROD_EINVAL, "normalize: final_obs needs mode 2");
+    if (!h) return fail(h, SOFTROD_EINVAL, "normalize: null handle");
+    if (!h->norm.rec) return fail(h, SOFTROD_EINVAL, kNormOff);
+    SR_ON_DEVICE(h);
+    const NormState& S = h->norm;
+    if (update) {
+        const int tiles = S.obs_on ? (S.obs_dim + kNormTile - 1) / kNormTile : 0;
+        hipLaunchKernelGGL(softrod_normalize_stats_kernel, dim3((unsigned)(tiles + S.reward_on)), dim3(kNormThreads), 0,
+                           (hipStream_t)stream, S, tiles, obs, mode == 0 ? (const uint8_t*)S.latch : nullptr, false,
+                           S.reward_on ? reward : nullptr);
+        SR_HIP(h, hipGetLastError());
+    }
+    hipLaunchKernelGGL(softrod_normalize_rows_kernel, dim3((unsigned)((S.n_envs + kNormRowWaves - 1) / kNormRowWaves)),
+                       dim3(kNormRowWaves * 64), 0, (hipStream_t)stream, S, obs, reward, terminated, truncated, final_obs, mode,
+                       update ? 1 : 0);
+    SR_HIP(h, hipGetLastError());
+    return SOFTROD_OK;
+}
+
+int softrod_normalize_reset(softrod_handle* h, const float* obs, const uint8_t* mask, int update, void* stream) {
+    if (!obs) return fail(h, SOFTROD_EINVAL, "normalize: null obs");
+    if (!h) return fail(h, SOFTROD_EINVAL, "normalize: null handle");
+    if (!h->norm.rec) return fail(h, SOFTROD_EINVAL, kNormOff);
+    SR_ON_DEVICE(h);
+    const NormState& S = h->norm;
+    if (update && S.obs_on) {
+        const int tiles = (S.obs_dim + kNormTile - 1) / kNormTile;
+        hipLaunchKernelGGL(softrod_normalize_stats_kernel, dim3((unsigned)tiles), dim3(kNormThreads), 0, (hipStream_t)stream, S,
+                           tiles, obs, mask, true, (const double*)nullptr);
+        SR_HIP(h, hipGetLastError());
+    }
+    hipLaunchKernelGGL(softrod_normalize_reset_kernel, dim3((unsigned)((S.n_envs + kNormRowWaves - 1) / kNormRowWaves)),
+                       dim3(kNormRowWaves * 64), 0, (hipStream_t)stream, S, obs, mask);
+    SR_HIP(h, hipGetLastError());
+    return SOFTROD_OK;
+}
+
+int softrod_normalize_view(softrod_handle* h, struct softrod_normalize_view* out) {
+    if (!out) return fail(h, SOFTROD_EINVAL, "normalize: null argument");
+    if (!h) return fail(h, SOFTROD_EINVAL, "normalize: null handle");
+    if (!h->norm.rec) return fail(h, SOFTROD_EINVAL, kNormOff);
+    const NormState& S = h->norm;
+    const size_t D = (size_t)S.obs_dim, W = D + 1;
+    out->obs_mean = S.rec; out->obs_var = S.rec + W; out->obs_count = S.rec + 2 * W; out->obs_inv_std = S.rec + 3 * W;
+    out->ret_mean = S.rec + D; out->ret_var = S.rec + W + D; out->ret_count = S.rec + 2 * W + D;
+    out->ret_inv_std = S.rec + 3 * W + D;
+    out->ret = S.ret; out->latch = S.latch;
+    out->norm_obs = S.norm_obs; out->norm_final_obs = S.norm_final_obs; out->norm_reward = S.norm_reward;
+    out->n_envs = S.n_envs; out->obs_dim = S.obs_dim; out->obs_on = S.obs_on; out->reward_on = S.reward_on;
+    out->gamma = S.gamma; out->clip_obs = S.clip_obs; out->clip_reward = S.clip_reward; out->epsilon = S.epsilon;
+    return SOFTROD_OK;
+}
+
+int softrod_normalize_load(softrod_handle* h, const double* obs_mean, const double* obs_var, const double* obs_count,
+                           const double* ret_mean, const double* ret_var, const double* ret_count, void* stream) {
+    if (!obs_mean || !obs_var || !obs_count || !ret_mean || !ret_var || !ret_count)
+        return fail(h, SOFTROD_EINVAL, "normalize: null argument");
+    if (!h) return fail(h, SOFTROD_EINVAL, "normalize: null handle");
+    if (!h->norm.rec) return fail(h, SOFTROD_EINVAL, kNormOff);
+    SR_ON_DEVICE(h);
+    const NormState& S = h->norm;
+    const double ret[3] = {*ret_mean, *ret_var, *ret_count};
+    std::vector<double> rec;
+    norm_records(rec, (size_t)S.obs_dim + 1, obs_mean, obs_var, obs_count, ret, S.epsilon);
+    SR_HIP(h, hipMemcpyAsync(S.rec, rec.data(), rec.size() * 8, hipMemcpyHostToDevice, (hipStream_t)stream));
+    SR_HIP(h, hipStreamSynchronize((hipStream_t)stream));       // `rec` dies with this call
+    return SOFTROD_OK;
+}
+
 namespace {
 // The env's target, where its kind has one: the point softrod_render draws (render.py draws the same) and
 // softrod_rod_clearance measures to.
@@ -2853,6 +2994,7 @@ int softrod_destroy(softrod_handle* h) {
     if (h->ev_pairs) (void)hipEventDestroy(h->ev_pairs);
     h->bank.release();
     if (h->d_stats) (void)hipFree(h->d_stats);
+    if (h->d_norm) (void)hipFree(h->d_norm);
     delete h;
     return SOFTROD_OK;
 }

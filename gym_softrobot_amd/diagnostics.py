@@ -376,6 +376,19 @@ def episode_ring_order(count: int, ring: int) -> np.ndarray:
     return np.arange(max(0, count - ring), count, dtype=np.int64) % ring
 
 
+class NormalizationState(NamedTuple):
+    """What normalization_state() returns and load_normalization_state() takes (softrod_normalize_*,
+    include/softrod.h), NumPy values: the running statistics of set_normalization() — Gymnasium's RunningMeanStd per
+    observation column, obs_mean / obs_var / obs_count (obs_dim,) float64, and for the discounted return, ret_mean /
+    ret_var / ret_count float64 scalars.  What a checkpointed policy carries with its weights."""
+    obs_mean: np.ndarray
+    obs_var: np.ndarray
+    obs_count: np.ndarray
+    ret_mean: float
+    ret_var: float
+    ret_count: float
+
+
 def _z_rotation(vector, theta):
     """joint.py:7-17."""
     theta = theta / 180.0 * np.pi

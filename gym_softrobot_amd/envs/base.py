@@ -404,6 +404,8 @@ class VecRodEnvBase:
         self.top_up_paused = False     # True: the caller reads the queue counters and stages records itself (tests)
         self._reset_shapes = 0         # entries of the pool of start shapes (set_reset_shapes); 0: straight starts
         self._episode_ring = 0         # ring length of the episode statistics (record_episode_statistics); 0: off
+        self._norm_obs = self._norm_reward = False    # what set_normalization switched on
+        self._norm_training = True     # normalization_training: False freezes the running statistics
         if self.same_step and not hasattr(self.backend, "autoreset_same_step"):
             raise NotImplementedError(f"same-step auto-reset needs the HIP backend, not {type(self.backend).__name__}")
         if self.device_autoreset:
@@ -613,6 +615,12 @@ class VecRodEnvBase:
         # _prev_action lives with the resident state (softrod_state_view.prev_action): it
         # survives reset except where the reference clears it (soft_pendulum_3d.py:68)
         obs = self.backend.observe(None)
+        infos: Dict[str, Any] = {}
+        if self._norm_obs or self._norm_reward:     # the reset rows are counted; the masked envs' returns start anew
+            self.backend.normalize_reset(obs, m if mask is not None else None)
+            if self._norm_obs:
+                infos["raw_obs"] = self._out(obs)
+                obs = self.backend.normalize["norm_obs"]
         if self.device_autoreset:
             self._top_up()
         if self.config_generate_video and not self.is_octo:
@@ -625,7 +633,7 @@ class VecRodEnvBase:
             # flat_env.py:188-206: per-arm RodCallBack dicts and the head's dict, fresh per reset
             self.recorder = OctoRecorder(self.backend, self.record_envs[0], rods=self.config_generate_video,
                                          head=self.config_save_head_data)
-        return self._out(obs), {}
+        return self._out(obs), infos
 
     @property
     def is_octo(self) -> bool:
@@ -667,6 +675,8 @@ class VecRodEnvBase:
             infos.update(self._final_infos(term, trunc))
         if self._episode_ring:
             infos.update(self._episode_infos())
+        if self._norm_obs or self._norm_reward:
+            obs, reward = self._normalized(obs, reward, infos)
         return (self._out(obs), self._out(reward), self._out(term.view(torch.bool)),
                 self._out(trunc.view(torch.bool)), infos)
 
@@ -729,6 +739,10 @@ class VecRodEnvBase:
         infos = self._infos(times)
         if self._episode_ring:
             infos.update(self._episode_infos())
+        if self._norm_obs or self._norm_reward:
+            if self.autoreset:      # host-driven NEXT_STEP: the pass sees the composed rows, not the discarded step's
+                self.backend.normalize_step(obs.contiguous(), reward, term, trunc, None, _capi.NORMALIZE_NEXT_STEP)
+            obs, reward = self._normalized(obs, reward, infos)
         return (
             self._out(obs),
             self._out(reward),
@@ -1173,8 +1187,8 @@ class VecRodEnvBase:
 
         Out of scope: step_packed raises NotImplementedError while statistics are on; not offered on the sharded env;
         not part of state_dict(), snapshot(), fork() or the state bank — a forked or loaded env keeps its own
-        accumulators, so reset(mask=...) or a new record_episode_statistics() is the way to clear them; no reward or
-        observation normalisation; no single-env wrapper (Gymnasium's own serves those).  A graph captured with
+        accumulators, so reset(mask=...) or a new record_episode_statistics() is the way to clear them; reward and
+        observation normalisation are set_normalization()'s; no single-env wrapper (Gymnasium's own serves those).  A graph captured with
         capture_policy_step must be captured again after this call.
 
         ValueError for a negative length; NotImplementedError on a backend other than the HIP one."""
@@ -1223,6 +1237,121 @@ class VecRodEnvBase:
         ring = [st[k].cpu().numpy()[order] for k in ("ring_r", "ring_l", "ring_t", "ring_env")]
         return EpisodeStatistics(count, *ring, st["finished"].cpu().numpy().copy())
 
+    # -- observation and reward normalisation: running statistics kept on the device -------------
+    def set_normalization(self, obs: bool = True, reward: bool = True, *, gamma: float = 0.99, clip_obs: float = 10.0,
+                          clip_reward: float = 10.0, epsilon: float = 1e-8) -> None:
+        """Normalise observations and / or rewards on the device with running statistics: what Gymnasium's
+        NormalizeObservation / NormalizeReward and Stable-Baselines3's VecNormalize do for host envs, for a resident
+        batch under every reset mode — by hand, autoreset=True, "device" and "same_step".  Upstream has single envs and
+        no normalisation.  Call it before reset().  Called again it starts the statistics anew; obs=False,
+        reward=False switches it off.  Two cold kernels behind every step (csrc/softrod_normalize.hpp), none while off.
+
+        The statistics are Gymnasium's RunningMeanStd (mean 0, var 1, count 1e-4 at the start), one per observation
+        column and one for the discounted return ret = ret * gamma + reward of every env.  While it is on
+          step() / reset() return obs = clip((obs - mean) / sqrt(var + epsilon), -clip_obs, clip_obs), float32, and
+          step() returns reward = clip(reward / sqrt(ret_var + epsilon), -clip_reward, clip_reward), float64 — no mean
+          is subtracted, as in VecNormalize —
+        computed with the statistics AFTER the call's own rows were counted; dtypes and shapes do not change.
+        infos["raw_obs"] / infos["raw_reward"] hold the untouched device views; in same-step mode info["final_obs"]
+        is normalised too (never counted) and infos["raw_final_obs"] is the raw one.  `normalization_info` gives the same
+        views to a capture_policy_step loop, whose policy then reads the normalised observation.  Episode statistics
+        (record_episode_statistics) keep reading the raw reward.  Non-finite values are not counted (an env that blew
+        up does not poison the statistics): a NaN comes out as NaN, an infinity as +-clip.  Under NEXT_STEP auto-reset
+        the call that returns an env's reset observation counts that observation, and its zero reward enters no return;
+        with autoreset=False an env that has finished is not counted until reset(mask=...) names it; reset() counts
+        the reset observations of the masked envs and starts their returns at zero.
+        `normalization_training = False` freezes the statistics (evaluation); normalization_state() /
+        load_normalization_state() carry them to another env or a checkpoint.
+
+        Out of scope: step_packed raises NotImplementedError while normalisation is on; not offered on the sharded env
+        (an all-reduce of the moments is a follow-up); not part of state_dict(), snapshot(), fork() or the state bank —
+        a forked or loaded env keeps its own discounted return and latch; no single-env wrapper (Gymnasium's own serve
+        those).  A graph captured with capture_policy_step must be captured again after this call.
+
+        ValueError for gamma outside [0, 1] or a clip or epsilon that is not positive; NotImplementedError on a backend
+        other than the HIP one."""
+        gamma, clip_obs, clip_reward, epsilon = float(gamma), float(clip_obs), float(clip_reward), float(epsilon)
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError(f"set_normalization: gamma {gamma} is outside [0, 1]")
+        for name, v in (("clip_obs", clip_obs), ("clip_reward", clip_reward), ("epsilon", epsilon)):
+            if not v > 0.0:
+                raise ValueError(f"set_normalization: {name} {v} is not positive")
+        be = self.backend
+        if not hasattr(be, "normalize_enable"):
+            raise NotImplementedError(f"normalisation needs the HIP backend, not {type(be).__name__}")
+        mode = (_capi.NORMALIZE_SAME_STEP if self.same_step
+                else _capi.NORMALIZE_NEXT_STEP if self.autoreset or self.device_autoreset
+                else _capi.NORMALIZE_MANUAL)
+        be.normalize_enable(obs, reward, gamma=gamma, clip_obs=clip_obs, clip_reward=clip_reward, epsilon=epsilon,
+                            mode=mode, in_step=not self.autoreset)
+        be.normalize_update = self._norm_training
+        self._norm_obs, self._norm_reward = bool(obs), bool(reward)
+
+    @property
+    def normalization_training(self) -> bool:
+        """True (the default): every step and reset updates the running statistics.  False: they are frozen — the
+        outputs keep following them, the discounted returns and latches stand still — as for evaluation.  A graph
+        captured with capture_policy_step must be captured again after a change."""
+        return self._norm_training
+
+    @normalization_training.setter
+    def normalization_training(self, on: bool) -> None:
+        self._norm_training = bool(on)
+        if hasattr(self.backend, "normalize_enable"):
+            self.backend.normalize_update = self._norm_training
+
+    def _normalized(self, obs, reward, infos):
+        """The step's return values with normalisation on: adds the raw views to `infos`, swaps final_obs."""
+        st = self.backend.normalize
+        if self._norm_obs:
+            infos["raw_obs"] = self._out(obs)
+            obs = st["norm_obs"]
+            if self.same_step:
+                infos["raw_final_obs"] = infos["final_obs"]
+                infos["final_obs"] = self._out(st["norm_final_obs"])
+        if self._norm_reward:
+            infos["raw_reward"] = self._out(reward)
+            reward = st["norm_reward"]
+        return obs, reward
+
+    @property
+    def normalization_info(self) -> Dict[str, Any]:
+        """The normalisation entries of the last step or replay (set_normalization), for a capture_policy_step loop:
+        {"obs", "raw_obs"} with observation normalisation on (and {"final_obs", "raw_final_obs"} in same-step mode),
+        {"reward", "raw_reward"} with reward normalisation on.  The device views are the same memory at every call."""
+        if not (self._norm_obs or self._norm_reward):
+            raise _capi.SoftrodError("normalisation is off (set_normalization)")
+        be, out = self.backend, {}
+        if self._norm_obs:
+            out.update(obs=self._out(be.normalize["norm_obs"]), raw_obs=self._out(be.obs))
+            if self.same_step:
+                out.update(final_obs=self._out(be.normalize["norm_final_obs"]), raw_final_obs=self._out(be.final_obs))
+        if self._norm_reward:
+            out.update(reward=self._out(be.normalize["norm_reward"]), raw_reward=self._out(be.reward))
+        return out
+
+    def normalization_state(self):
+        """NormalizationState(obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count) as NumPy values
+        (diagnostics.py): the running statistics as they stand.  It waits for the env's stream."""
+        from ..diagnostics import NormalizationState
+
+        if not (self._norm_obs or self._norm_reward):
+            raise _capi.SoftrodError("normalisation is off (set_normalization)")
+        import torch
+
+        st = self.backend.normalize
+        torch.cuda.synchronize(self.backend.device)
+        return NormalizationState(*(st[k].cpu().numpy().copy() for k in ("obs_mean", "obs_var", "obs_count")),
+                                  *(float(st[k].cpu()[0]) for k in ("ret_mean", "ret_var", "ret_count")))
+
+    def load_normalization_state(self, state) -> None:
+        """Set the running statistics from a NormalizationState (or any 6-tuple in its order), bit for bit; the
+        discounted returns under way stay.  normalization_state() of one env loaded into another makes the two
+        normalise alike."""
+        if not (self._norm_obs or self._norm_reward):
+            raise _capi.SoftrodError("normalisation is off (set_normalization)")
+        self.backend.normalize_load(*state)
+
     def capture_policy_step(self, policy):
         """One HIP graph for `actions = policy(obs); step(actions)` — the launch-bound tail of an on-device
         rollout (a small policy is half a dozen tiny kernels per step) becomes ONE graph launch per env.step.
@@ -1240,7 +1369,10 @@ class VecRodEnvBase:
         The kernel arguments (RodParams, array pointers) are baked into the graph BY VALUE at capture: after
         anything that changes them (a radius profile, an action basis, enabling auto-reset, enabling per-env material or contact,
         setting or clearing a pool of start shapes with set_reset_shapes, switching episode statistics on or off with
-        record_episode_statistics) capture again.  With episode statistics on their update is one more kernel of the captured line and
+        record_episode_statistics, switching normalisation on or off with set_normalization, changing
+        normalization_training) capture again.  With normalisation on (set_normalization) the policy reads the normalised
+        observation, the pass is two more kernels of the captured line, replay() returns the normalised observation and
+        reward, and `normalization_info` holds the raw views.  With episode statistics on their update is one more kernel of the captured line and
         `episode_info` holds its rows after every replay.  Once per-env material is on, later set_material calls update its table in place: replays
         issued on the env's stream see them.  The same holds for per-env contact (set_contact).
         Kernel timing (set_timing) is switched off by the capture and stays off."""
@@ -1257,14 +1389,17 @@ class VecRodEnvBase:
                                                   # kernel timing is OFF from here on (call set_timing again to re-arm)
         side = torch.cuda.Stream(device=be.device)
         side.wait_stream(torch.cuda.current_stream(be.device))
+        seen = be.normalize["norm_obs"] if self._norm_obs else be.obs      # what the policy reads
         with torch.cuda.stream(side):             # warm-up off the capture: the POLICY only (lazy BLAS handles,
             for _ in range(3):                    # allocator pools); it is a pure function of the observation, and
-                policy(be.obs)                    # softrod_step has nothing lazy to warm up, so no state moves
+                policy(seen)                      # softrod_step has nothing lazy to warm up, so no state moves
         torch.cuda.current_stream(be.device).wait_stream(side)
         torch.cuda.synchronize(be.device)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            be.step(policy(be.obs))
+            be.step(policy(seen))
+        out_obs = seen
+        out_reward = be.normalize["norm_reward"] if self._norm_reward else be.reward
 
         def replay():
             graph.replay()
@@ -1272,7 +1407,7 @@ class VecRodEnvBase:
                 self._top_up_tick()
             else:
                 self._steps += 1                  # what step() books: infos["time"] of a later eager step stays right
-            return be.obs, be.reward, be.terminated.view(torch.bool), be.truncated.view(torch.bool)
+            return out_obs, out_reward, be.terminated.view(torch.bool), be.truncated.view(torch.bool)
 
         replay.graph = graph
         return replay
@@ -1280,7 +1415,7 @@ class VecRodEnvBase:
     def step_packed(self, actions, out=None):
         """step() with every per-env output in one (N, packed_width) float32 buffer written
         by the kernel itself (distributed.unpack_outputs gives views); no host auto-reset.  NotImplementedError while
-        episode statistics are on (record_episode_statistics)."""
+        episode statistics (record_episode_statistics) or normalisation (set_normalization) are on."""
         import torch
 
         if self.autoreset:

@@ -1278,6 +1278,79 @@ int softrod_episode_stats_update(softrod_handle* h, const double* reward, const 
 int softrod_episode_stats_reset(softrod_handle* h, const uint8_t* mask, void* stream);
 int softrod_episode_stats_view(softrod_handle* h, struct softrod_episode_stats_view* out);
 
+/* OBSERVATION AND REWARD NORMALISATION on the device: Gymnasium's RunningMeanStd kept per observation column and once
+ * for the discounted return, the observations centred, scaled and clipped by it, the rewards scaled by the return's
+ * deviation and clipped (no mean subtracted, as Stable-Baselines3's VecNormalize does).  No reference counterpart:
+ * upstream has single envs, which take gymnasium.wrappers.NormalizeObservation / NormalizeReward; those cannot wrap a
+ * batch of device tensors.  Cold kernels on the caller's stream behind softrod_step (csrc/softrod_normalize.hpp gives the
+ * arithmetic, its fixed summation order and the row rules); softrod_step itself is unchanged and launches nothing for
+ * this: the pass is the caller's call, and nothing runs while the feature is off.
+ *
+ *   softrod_normalize_enable(h, obs_on, reward_on, gamma, clip_obs, clip_reward, epsilon)
+ *       allocates the resident arrays — the records mean, var, count, inv_std f64 [obs_dim] and one of each for the
+ *       return, ret f64 [n_envs], latch u8 [n_envs], norm_obs f32 [n_envs][obs_dim], norm_final_obs f32
+ *       [n_envs][obs_dim], norm_reward f64 [n_envs] — with every record at mean 0, var 1, count 1e-4 and everything
+ *       else zero.  Called again it starts them anew (the pointers of an earlier softrod_normalize_view die; a graph
+ *       captured with the pass in it must be captured again).  obs_on: the observation columns are kept and norm_obs /
+ *       norm_final_obs written; reward_on: ret, the return's record and norm_reward.  Both 0: switches the feature off
+ *       and releases the arrays.  Waits for the device; not capturable.  softrod_destroy releases them too.
+ *       SOFTROD_ENOMEM / SOFTROD_EHIP leave the handle as it was.
+ *   softrod_normalize_step(h, obs, reward, terminated, truncated, final_obs, mode, update, stream)
+ *       one pass over the outputs of the softrod_step before it: DEVICE obs f32 [n_envs][obs_dim], reward f64 [n_envs],
+ *       terminated and truncated u8 [n_envs], final_obs f32 [n_envs][obs_dim] (softrod_final_view) or NULL.  mode 0: the
+ *       caller resets finished envs by hand; 1: NEXT_STEP auto-reset (the call after an env's last step is its reset
+ *       call: its reward enters no return, its observation row is counted); 2: SAME_STEP auto-reset (final_obs rows of
+ *       the envs that finished are normalised into norm_final_obs, never counted).  update 0: evaluation, the records,
+ *       ret and latch stay and the outputs are still written.  The outputs use the records after this call's update.
+ *       Two launches (one with update 0); no allocation, synchronisation or host read: capturable.
+ *   softrod_normalize_reset(h, obs, mask, update, stream)
+ *       the reset observation: DEVICE obs, DEVICE mask u8 [n_envs] or NULL (every env).  With update the masked envs'
+ *       rows are counted; their ret and latch become zero; every row of norm_obs is written.  Capturable.
+ *   softrod_normalize_view(h, &view)
+ *       the device pointers and the settings; good until the next softrod_normalize_enable or softrod_destroy.
+ *   softrod_normalize_load(h, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count, stream)
+ *       HOST arrays f64 [obs_dim] and three HOST f64 scalars by pointer: sets the records and recomputes
+ *       inv_std = 1 / sqrt(var + epsilon); ret and latch stay.  What a checkpointed policy carries its statistics with.
+ *       Waits for the stream; not capturable.
+ * Errors, each SOFTROD_EINVAL and found before a device is looked for (a refused call changes nothing); the checks of
+ * the arguments come before those of the handle:
+ *   "normalize: gamma <g> is outside [0, 1]", "normalize: clip_obs <c> is not positive",
+ *   "normalize: clip_reward <c> is not positive", "normalize: epsilon <e> is not positive" (enable),
+ *   "normalize: mode <m> is outside 0 .. 2", "normalize: null obs, reward, terminated or truncated",
+ *   "normalize: final_obs needs mode 2" (step), "normalize: null obs" (reset), "normalize: null argument" (view, load),
+ *   "normalize: null handle", "normalize: the feature is off (softrod_normalize_enable)" (step, reset, view, load).  */
+struct softrod_normalize_view {          /* a struct tag only: the entry point of the same name fills it */
+    double* obs_mean;
+    double* obs_var;
+    double* obs_count;
+    double* obs_inv_std;
+    double* ret_mean;
+    double* ret_var;
+    double* ret_count;
+    double* ret_inv_std;
+    double* ret;
+    uint8_t* latch;
+    float* norm_obs;
+    float* norm_final_obs;
+    double* norm_reward;
+    int32_t n_envs;
+    int32_t obs_dim;
+    int32_t obs_on;
+    int32_t reward_on;
+    double gamma;
+    double clip_obs;
+    double clip_reward;
+    double epsilon;
+};
+int softrod_normalize_enable(softrod_handle* h, int obs_on, int reward_on, double gamma, double clip_obs, double clip_reward,
+                             double epsilon);
+int softrod_normalize_step(softrod_handle* h, const float* obs, const double* reward, const uint8_t* terminated,
+                           const uint8_t* truncated, const float* final_obs, int mode, int update, void* stream);
+int softrod_normalize_reset(softrod_handle* h, const float* obs, const uint8_t* mask, int update, void* stream);
+int softrod_normalize_view(softrod_handle* h, struct softrod_normalize_view* out);
+int softrod_normalize_load(softrod_handle* h, const double* obs_mean, const double* obs_var, const double* obs_count,
+                           const double* ret_mean, const double* ret_var, const double* ret_count, void* stream);
+
 /* Run `n` bare PositionVerlet substeps with fixed per-env forcing inputs and no
  * env epilogue (the inner loop of soft_pendulum.py:183-184 alone); `actions`
  * (device [n_envs] float32 or NULL) feeds SOFTROD_FEAT_POINT_FORCE_NODE0_X.
