@@ -109,10 +109,18 @@ class HipRodBackend:
             )
 
     # -- lifetime -------------------------------------------------------------------
+    # The zero-copy views of the handle's memory that the backend keeps on itself.  Each is a tensor over a _DevArray that
+    # names this backend as its owner, through a reference torch holds outside Python's sight: backend -> view -> backend
+    # is a cycle no collection breaks, and with it every tensor of a closed backend (obs, reward, ...) would stay allocated.
+    _HANDLE_VIEWS = ("episode_stats", "normalize", "_reset_shape_rows", "reset_shapes_count", "final_obs", "final_time",
+                     "final_aux", "_episode_clock", "_prev_rows")
+
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h:
             self._lib.softrod_destroy(self._h)
             self._h = C.c_void_p()
+            for name in self._HANDLE_VIEWS:         # they point into freed memory now; the class's "off" values show again
+                self.__dict__.pop(name, None)
 
     def __del__(self):
         try:

@@ -14,6 +14,8 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "softrod_kernels.hpp"
@@ -24,46 +26,77 @@
 #include "softrod_normalize.hpp"
 #include "softrod_shape.hpp"
 #include "softrod_reset_shapes.hpp"
+#include "softrod_owned.hpp"
 
 using namespace softrod;
 
-// One per-env table (set_env_table): nullptr until the first call
+// Every resource below is an owner of softrod_owned.hpp, or a struct or vector of them: one struct per feature, which
+// a set-up builds locally and moves into the handle once nothing can fail any more.  Dropping a feature is assigning
+// a fresh value of its struct.
+
+// One per-env table (set_env_table), empty until the first call: dev [N]; host pinned [N], every row as last uploaded
 template <class Row>
-struct EnvTable {
-    Row* dev = nullptr;        // [N]
-    Row* host = nullptr;       // pinned [N]: every row as last uploaded (the staging buffer)
-    hipEvent_t ev = nullptr;   // guards reuse of host
-    void release() {
-        (void)hipFree(dev);
-        if (host) (void)hipHostFree(host);
-        if (ev) (void)hipEventDestroy(ev);
-    }
-};
+using EnvTable = Upload<Row>;
 
 // The state bank (softrod_bank_create): a twin with `slots` rows of every array copy_table(h) lists, keyed by the
 // batch array it twins, so that the bank's table is the batch's with the bases swapped (bank_table).
 struct StateBank {
     int slots = 0;                  // 0: the handle has no bank
-    struct Twin { const void* of; unsigned char* dev; };
+    struct Twin { const void* of; DeviceBuf<unsigned char> dev; };
     std::vector<Twin> twins;        // `of`: the batch array's base
     std::vector<uint8_t> filled;    // [slots] the slot holds a saved state
     std::vector<uint8_t> seen;      // [max(N, slots)] scratch of the validation, all zero between calls
     std::vector<EnvMaterial> mat;   // [slots] the slot's row of env_mat.host, where that table exists
     std::vector<EnvContact> contact;    // [slots] the same for env_contact.host
-    int2* d_pairs = nullptr;        // [max(N, slots)] the (from, to) pairs of a call on their way to the device
-    int2* h_pairs = nullptr;        // pinned, the same size
-    hipEvent_t ev_pairs = nullptr;  // guards reuse of h_pairs
+    Upload<int2> pairs;             // [max(N, slots)] the (from, to) pairs of a call on their way to the device
     unsigned char* twin_of(const void* base) const {
-        for (const Twin& t : twins) if (t.of == base) return t.dev;
+        for (const Twin& t : twins) if (t.of == base) return t.dev.get();
         return nullptr;
     }
-    void release() {
-        for (const Twin& t : twins) (void)hipFree(t.dev);
-        (void)hipFree(d_pairs);
-        if (h_pairs) (void)hipHostFree(h_pairs);
-        if (ev_pairs) (void)hipEventDestroy(ev_pairs);
-        *this = StateBank{};
-    }
+};
+
+// Reset staging (softrod_create): the start records and the mask of a masked reset on their way to the device
+struct ResetStaging {
+    Upload<double> init;            // [N][init_stride]; init.ev guards reuse of both pinned buffers
+    DeviceBuf<uint8_t> d_mask;      // [N]
+    PinnedBuf<uint8_t> h_mask;      // [N]
+};
+
+// Device-side auto-reset (softrod_autoreset_enable)
+struct ResetQueue {
+    int depth = 0;                  // 0: off
+    Upload<double> ring;            // [depth][N][init_stride] and its pinned mirror; ring.ev guards reuse of the mirror and h_produced
+    DeviceBuf<int> d_consumed;      // [N]
+    DeviceBuf<int> d_produced;      // [N]
+    DeviceBuf<int> d_underflow;     // [1]
+    DeviceBuf<uint8_t> d_flags;     // [2][N]: needs_reset, skip
+    PinnedBuf<int> h_produced;      // [N]
+    PinnedBuf<double> h_stage;      // the pending records, compacted
+    PinnedBuf<int2> h_where;
+    DeviceBuf<double> d_stage;
+    DeviceBuf<int2> d_where;
+    size_t stage_cap = 0;           // records the staging buffers hold
+    PinnedBuf<int> h_status;        // [N + 1]: consumed, underflow (softrod_queue_status_begin)
+    Event ev_status;
+};
+
+// Same-step auto-reset (softrod_autoreset_same_step): allocated by the first call that switches it on and kept through
+// on = 0, so that the pointers softrod_final_view hands out stay good for the handle's life
+struct FinalRows {
+    DeviceBuf<float> obs;           // [N][obs_dim] the finished step's observation
+    DeviceBuf<double> time;         // [N] the finished episode's clock
+    DeviceBuf<double> aux;          // [N] the finished step's aux value (SoftPendulum3D's tilt)
+};
+
+// Shaped starts (softrod_set_reset_shapes): the pool is replaced by every call that sets one; the three rows are
+// allocated by the first and kept for the handle's life, so that softrod_reset_shapes_view's pointers stay good
+struct ResetShapes {
+    int count = 0;                  // entries of the pool; 0: none set
+    unsigned long long seed = 0;
+    DeviceBuf<double> field[4];     // kappa, sigma, velocity, omega [count][rods][3][..] or empty
+    DeviceBuf<int> index;           // [N] the entry each env's current episode started from, -1: none
+    DeviceBuf<int> episode;         // [N] resets counted = the next reset's ordinal
+    DeviceBuf<uint8_t> picked;      // [N] scratch of the pass: the envs it shapes
 };
 
 struct softrod_handle {
@@ -78,9 +111,10 @@ struct softrod_handle {
     std::string tier;                     // softrod_kernel_tier
     RodParams P{};
     StatePtrs S{};
-    std::vector<void*> owned;     // every device buffer that lives as long as the handle (alloc_owned), for softrod_destroy
-    double* d_init = nullptr;     // [N][18] staging for reset
-    uint8_t* d_mask = nullptr;    // [N]
+    // every device buffer that lives as long as the handle: what softrod_create allocates into the raw pointers below
+    // and into S, and softrod_set_radius_profile's table
+    std::vector<DeviceBuf<unsigned char>> owned;
+    ResetStaging reset;
     double* d_basis = nullptr;    // [(n_elem-1)][7] action basis (zero until set)
     double* d_spline = nullptr;   // breaks[MAX_PIECES + 1], coef[pieces][n_ctrl][4] (softrod_set_spline_table)
     bool spline_set = false;
@@ -96,58 +130,30 @@ struct softrod_handle {
     bool tapered = false;
     bool was_reset = false;
     bool basis_set = false;
-    double* h_init = nullptr;     // pinned
-    uint8_t* h_mask = nullptr;    // pinned
-    std::vector<hipEvent_t> ev_start, ev_stop;  // timing ring (softrod_set_timing)
+    std::vector<Event> ev_start, ev_stop;   // timing ring (softrod_set_timing)
     int timed = 0;                  // launches recorded since set_timing
-    hipEvent_t ev_reset = nullptr;  // guards reuse of the pinned staging buffers
-    // device-side auto-reset (softrod_autoreset_enable)
-    int q_depth = 0;
-    double* d_queue = nullptr;      // [depth][N][init_stride]
-    double* h_queue = nullptr;      // pinned mirror
-    int* d_consumed = nullptr;      // [N]
-    int* d_produced = nullptr;      // [N]
-    int* d_underflow = nullptr;     // [1]
-    uint8_t* d_flags = nullptr;     // [2][N]: needs_reset, skip
-    int* h_produced = nullptr;      // pinned [N]
+    ResetQueue q;                   // softrod_autoreset_enable
     std::vector<int> seen_consumed; // as of the last softrod_queue_status
-    std::vector<int2> pending;      // (env, slot) written into h_queue since the last commit
-    double* h_stage = nullptr;      // pinned: the pending records, compacted
-    int2* h_where = nullptr;        // pinned
-    double* d_stage = nullptr;
-    int2* d_where = nullptr;
-    size_t stage_cap = 0;           // records the staging buffers hold
-    int* h_status = nullptr;        // pinned [N + 1]: consumed, underflow (softrod_queue_status_begin)
-    hipEvent_t ev_status = nullptr;
+    std::vector<int2> pending;      // (env, slot) written into q.ring.host since the last commit
     bool status_pending = false;
-    hipEvent_t ev_queue = nullptr;  // guards reuse of h_queue / h_produced
-    // same-step auto-reset (softrod_autoreset_same_step): owned, allocated by the first call that switches it on
-    bool same_step = false;
-    float* d_final_obs = nullptr;   // [N][obs_dim] the finished step's observation
-    double* d_final_time = nullptr; // [N] the finished episode's clock
-    double* d_final_aux = nullptr;  // [N] the finished step's aux value (SoftPendulum3D's tilt)
-    // shaped starts (softrod_set_reset_shapes): the pool is owned, reallocated by every call that sets one; the three
-    // rows are allocated by the first and kept for the handle's life, so that softrod_reset_shapes_view's pointers stay good
-    int rs_count = 0;               // entries of the pool; 0: none set
-    unsigned long long rs_seed = 0;
-    double* d_rs_field[4] = {nullptr, nullptr, nullptr, nullptr};   // kappa, sigma, velocity, omega [count][rods][3][..] or nullptr
-    int* d_rs_index = nullptr;      // [N] the entry each env's current episode started from, -1: none
-    int* d_rs_episode = nullptr;    // [N] resets counted = the next reset's ordinal
-    uint8_t* d_rs_picked = nullptr; // [N] scratch of the pass: the envs it shapes
+    bool same_step = false;         // softrod_autoreset_same_step
+    FinalRows final;
+    ResetShapes rs;                 // softrod_set_reset_shapes
     EnvTable<EnvMaterial> env_mat;      // softrod_set_env_material
     EnvTable<EnvContact> env_contact;   // softrod_set_env_contact
-    // softrod_copy_envs: the (src, dst) pairs of a call on their way to the device, sized for n_envs pairs at create
-    int2* d_pairs = nullptr;        // [N]
-    int2* h_pairs = nullptr;        // pinned [N]
-    hipEvent_t ev_pairs = nullptr;  // guards reuse of h_pairs
+    Upload<int2> pairs;             // [N] softrod_copy_envs: the (src, dst) pairs of a call on their way to the device
     std::vector<uint8_t> is_dst;    // [N] scratch of its validation, all zero between calls
     StateBank bank;                 // softrod_bank_create
     // episode statistics (softrod_episode_stats_enable): one device block carved into the arrays of EpisodeStats
     EpisodeStats stats{};           // stats.ring == 0: off
-    void* d_stats = nullptr;        // the block
+    DeviceBuf<unsigned char> d_stats;   // the block
     // observation / reward normalisation (softrod_normalize_enable): one device block carved into the arrays of NormState
     NormState norm{};               // norm.rec == nullptr: off
-    void* d_norm = nullptr;         // the block
+    DeviceBuf<unsigned char> d_norm;    // the block
+    // failure injection of the set-ups (arm_setup, SR_SETUP): 0 in production
+    const char* setup_name = "";    // the entry point that armed it
+    int setup_fail_at = 0;          // > 0: the set-up call of this ordinal is not made and fails
+    int setup_calls = 0;            // set-up calls counted since it was armed
     // planar certificates (StatePtrs.planar_cert, softrod_planar.hpp)
     bool cert_on = true;            // softrod_set_planar_certificates; softrod_state_view_get switches it off for good
     bool cert_live = false;         // a launch since the last clear may have issued certificates
@@ -189,6 +195,48 @@ struct DeviceGuard {
         if (e_ != hipSuccess)                                                           \
             return fail(h, SOFTROD_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
+
+// ---- set-ups: the entry points that allocate after softrod_create ----
+// A set-up builds what it needs in local owners (softrod_owned.hpp), makes every fallible call through SR_SETUP, and
+// touches the handle, h->S, the bank and d_state only after the last of them has succeeded — the StatePtrs upload, where
+// there is one, is that last call.  An early return is therefore always clean: the locals release what was made, the
+// handle is as it was, and the call can be repeated.
+//
+// Failure injection (tests/test_gpu_debug_switches.py): SOFTROD_DEBUG_FAIL_SETUP_CALL=k, honoured only with
+// SOFTROD_DEBUG_SWITCHES=1, makes the k-th SR_SETUP call of a set-up fail without being made.  Each set-up arms the
+// counter at its top; nothing is read from the environment while the gate is off, and nothing on the step path.
+void arm_setup(softrod_handle* h, const char* entry_point) {
+    const char* dbg = std::getenv("SOFTROD_DEBUG_SWITCHES");
+    const char* k = (dbg && dbg[0] == '1') ? std::getenv("SOFTROD_DEBUG_FAIL_SETUP_CALL") : nullptr;
+    h->setup_name = entry_point;
+    h->setup_fail_at = k ? std::atoi(k) : 0;
+    h->setup_calls = 0;
+}
+// What a failed set-up call returns.  Without `prefix`: SR_HIP's text and code.  With one: the entry point's own text;
+// oom_is_enomem: hipErrorOutOfMemory is SOFTROD_ENOMEM.
+int setup_error(softrod_handle* h, hipError_t e, const char* call, const char* prefix = nullptr, bool oom_is_enomem = false) {
+    if (!prefix) return fail(h, SOFTROD_EHIP, std::string(call) + ": " + hipGetErrorString(e));
+    (void)hipGetLastError();
+    return fail(h, oom_is_enomem && e == hipErrorOutOfMemory ? SOFTROD_ENOMEM : SOFTROD_EHIP, std::string(prefix) + hipGetErrorString(e));
+}
+#define SR_SETUP(h, call, ...)                                                                              \
+    do {                                                                                                    \
+        if ((h)->setup_fail_at > 0 && ++(h)->setup_calls == (h)->setup_fail_at)                             \
+            return fail(h, SOFTROD_EHIP, std::string((h)->setup_name) + ": injected failure at call " +     \
+                                             std::to_string((h)->setup_calls));                             \
+        if (const hipError_t e_ = (call)) return setup_error(h, e_, #call, ##__VA_ARGS__);                  \
+    } while (0)
+
+// Sizes in, one zeroed device block and the offsets out: arrays of `sizes` bytes in that order, each at a multiple of
+// 256 bytes of `block` (two set-up calls; failures in the words of `what`).
+int carve_block(softrod_handle* h, const char* what, const std::vector<size_t>& sizes, DeviceBuf<unsigned char>& block,
+                std::vector<size_t>& at) {
+    size_t bytes = 0;
+    for (const size_t n : sizes) { at.push_back(bytes); bytes += (n + 255) & ~(size_t)255; }
+    SR_SETUP(h, block.alloc(bytes), what, true);
+    SR_SETUP(h, hipMemset(block.get(), 0, bytes), what, true);
+    return SOFTROD_OK;
+}
 
 // Constants of a uniform straight rod — CosseratRod.straight_rod
 // (elastica/rod/factory_function.py allocate(), called at build.py:54-61) and
@@ -338,15 +386,6 @@ bool restarts_as_body(const softrod_handle* h) { return is_octo(h); }
 bool observes_as_body(const softrod_handle* h) { return is_mocto(h) || (is_octo(h) && !is_pull(h)); }
 // the one- or the two-slot instantiation of a kernel, by the handle's slots per lane
 template <class K> K by_epl(const softrod_handle* h, K one, K two) { return h->epl == 2 ? two : one; }
-// A device buffer whose lifetime is the handle's: allocated, zero-filled and recorded for softrod_destroy.
-// On failure p stays null exactly when the allocation itself failed.
-template <class T>
-hipError_t alloc_owned(softrod_handle* h, T*& p, size_t bytes) {
-    const hipError_t e = hipMalloc((void**)&p, bytes);
-    if (e != hipSuccess) { p = nullptr; return e; }
-    h->owned.push_back(p);
-    return hipMemset(p, 0, bytes);
-}
 // Where a handle's rods lie in its resident rows (softrod_state_view): rods per env, the width of an env's row,
 // the slots between two arms of an env.
 struct RodLayout { int rods, lane_stride, arm_stride; };
@@ -409,11 +448,11 @@ int launch_autoreset(softrod_handle* h, float* obs, double* reward, uint8_t* ter
 int launch_autoreset_same_step(softrod_handle* h, float* obs, double* aux, int pack, hipStream_t st) {
     const dim3 grid((unsigned)h->cfg.n_envs), block(kLanes * h->nw);
     if (restarts_as_body(h))
-        hipLaunchKernelGGL(softrod_octo_autoreset_same_step_kernel, grid, block, 0, st, h->P, h->S, obs, pack, h->d_final_obs,
-                           h->d_final_time);
+        hipLaunchKernelGGL(softrod_octo_autoreset_same_step_kernel, grid, block, 0, st, h->P, h->S, obs, pack, h->final.obs.get(),
+                           h->final.time.get());
     else
         hipLaunchKernelGGL(by_epl(h, softrod_autoreset_same_step_kernel<1>, softrod_autoreset_same_step_kernel<2>), grid, block,
-                           0, st, h->P, h->S, obs, aux, pack, h->d_final_obs, h->d_final_time, h->d_final_aux);
+                           0, st, h->P, h->S, obs, aux, pack, h->final.obs.get(), h->final.time.get(), h->final.aux.get());
     SR_HIP(h, hipGetLastError());
     return SOFTROD_OK;
 }
@@ -425,25 +464,27 @@ int launch_autoreset_same_step(softrod_handle* h, float* obs, double* aux, int p
 int launch_reset_shapes(softrod_handle* h, int mode, const uint8_t* mask, float* obs, const uint8_t* term, const uint8_t* trunc,
                         double* aux, int pack, hipStream_t st) {
     const int N = h->cfg.n_envs;
+    const ResetShapes& rs = h->rs;
+    uint8_t* const picked = rs.picked.get();
     ResetShapesPick pick{};
-    pick.index = h->d_rs_index; pick.episode = h->d_rs_episode; pick.picked = h->d_rs_picked;
-    pick.seed = h->rs_seed; pick.count = h->rs_count; pick.mode = mode; pick.mask = mask;
+    pick.index = rs.index.get(); pick.episode = rs.episode.get(); pick.picked = picked;
+    pick.seed = rs.seed; pick.count = rs.count; pick.mode = mode; pick.mask = mask;
     pick.terminated = pack ? nullptr : term; pick.truncated = pack ? nullptr : trunc;
     pick.packed = (mode == kPickFinished && pack) ? obs : nullptr;
     pick.od = softrod_config_obs_dim(&h->cfg);
     hipLaunchKernelGGL(softrod_reset_shapes_pick_kernel, dim3((unsigned)((N + kPickThreads - 1) / kPickThreads)), dim3(kPickThreads),
                        0, st, h->P, h->S, pick);
     const RodLayout y = rod_layout(h);
-    const RodShapeArgs args{h->d_rs_field[0], h->d_rs_field[1], h->d_rs_field[2], h->d_rs_field[3], h->d_rs_picked, h->d_rs_index};
+    const RodShapeArgs args{rs.field[0].get(), rs.field[1].get(), rs.field[2].get(), rs.field[3].get(), picked, rs.index.get()};
     hipLaunchKernelGGL(by_epl(h, softrod_rod_shape_kernel<1>, softrod_rod_shape_kernel<2>), dim3((unsigned)(N * y.rods)),
                        dim3(kLanes), 0, st, h->P, h->S, y.rods, y.lane_stride, y.arm_stride, args);
     if (obs) {      // the kernel softrod_observe would launch for this handle, for the picked envs
         if (observes_as_body(h))
             hipLaunchKernelGGL(softrod_reset_shapes_octo_observe_kernel, dim3((unsigned)N), dim3(kLanes * h->nw), 0, st, h->P, h->S,
-                               h->d_rs_picked, obs, pack);
+                               picked, obs, pack);
         else
             hipLaunchKernelGGL(by_epl(h, softrod_observe_kernel<1>, softrod_observe_kernel<2>), dim3((unsigned)N), dim3(kLanes), 0,
-                               st, h->P, h->S, h->d_rs_picked, nullptr, obs, aux, pack);
+                               st, h->P, h->S, picked, nullptr, obs, aux, pack);
     }
     SR_HIP(h, hipGetLastError());
     return SOFTROD_OK;
@@ -579,7 +620,7 @@ const StepRow kStepRows[] = {
 
 unsigned active_options(const softrod_handle* h) {
     return (h->cfg.features & kOptMuscles) | (h->cfg.early_termination ? kOptEarlyTerm : 0u) |
-           (h->env_mat.dev ? kOptEnvMaterial : 0u) | (h->env_contact.dev ? kOptEnvContact : 0u);
+           (h->env_mat.dev.get() ? kOptEnvMaterial : 0u) | (h->env_contact.dev.get() ? kOptEnvContact : 0u);
 }
 
 // The wording of a refusal, consulted only once no row of kStepRows serves the handle with the options `opts`: the
@@ -664,15 +705,20 @@ StepChoice select_step(const softrod_handle* h, int epilogue = 1, unsigned with 
     return {nullptr, why ? why : "no step kernel is compiled for this handle's feature set, env kind and options"};
 }
 
-template <class Row>
-hipError_t bank_adopt_table(softrod_handle* h, const Row* table, const Row& row);      // the state bank, below
+// the state bank, below
+int bank_twin(softrod_handle* h, int slots, const void* base, size_t comps, size_t row_bytes, std::vector<StateBank::Twin>& out,
+              const char* prefix, bool oom_is_enomem);
+std::vector<EnvMaterial>& bank_host_rows(StateBank& b, const EnvMaterial*);
+std::vector<EnvContact>& bank_host_rows(StateBank& b, const EnvContact*);
 
 // softrod_set_env_material / softrod_set_env_contact: W doubles per env in, one Row per env on the device.  Refused
 // unless a step kernel honours `option` on this handle; `bad` names what is wrong with an env's values (nullptr: nothing);
-// the first call allocates the table with every row at the config's `own` values; only rows with mask != 0 change.
+// the first call (a set-up, `entry_point`) allocates the table with every row at the config's `own` values and points
+// h->S.*slot at it; only rows with mask != 0 change.
 template <int W, class Row, class Bad, class Build>
-int set_env_table(softrod_handle* h, EnvTable<Row>& T, const Row*& slot, unsigned option, const char* what,
-                  const double* values, const double (&own)[W], const uint8_t* mask, void* stream, Bad bad, Build build) {
+int set_env_table(softrod_handle* h, EnvTable<Row>& T, const Row* StatePtrs::*slot, unsigned option, const char* entry_point,
+                  const char* what, const double* values, const double (&own)[W], const uint8_t* mask, void* stream, Bad bad,
+                  Build build) {
     const StepChoice serves = select_step(h, 1, option);
     if (!serves.row) return fail(h, SOFTROD_EINVAL, serves.why);
     const size_t N = (size_t)h->cfg.n_envs;
@@ -682,27 +728,44 @@ int set_env_table(softrod_handle* h, EnvTable<Row>& T, const Row*& slot, unsigne
     }
     SR_ON_DEVICE(h);
     hipStream_t st = (hipStream_t)stream;
-    if (!T.dev) {
-        SR_HIP(h, hipMalloc((void**)&T.dev, N * sizeof(Row)));
-        SR_HIP(h, hipHostMalloc((void**)&T.host, N * sizeof(Row), hipHostMallocDefault));
-        SR_HIP(h, hipEventCreateWithFlags(&T.ev, hipEventDisableTiming));
+    if (!T.dev.get()) {
+        arm_setup(h, entry_point);
+        EnvTable<Row> fresh;
+        SR_SETUP(h, fresh.dev.alloc(N * sizeof(Row)));
+        SR_SETUP(h, fresh.host.alloc(N * sizeof(Row)));
+        SR_SETUP(h, fresh.ev.create(hipEventDisableTiming));
         Row R0;
         build(own, R0);
-        for (size_t i = 0; i < N; ++i) T.host[i] = R0;
-        if (const hipError_t e = bank_adopt_table(h, T.dev, R0)) {     // no twin, no table: copy_table must not list it
-            T.release();
-            T = EnvTable<Row>{};
-            return fail(h, SOFTROD_EHIP, std::string("state bank: ") + hipGetErrorString(e));
+        for (size_t i = 0; i < N; ++i) fresh.host.get()[i] = R0;
+        // A table created after the bank: its twin, with every slot at the row the new table gives an untouched env, so
+        // that a slot saved before the table existed loads as its env would be now.  (No twin, no table: copy_table
+        // must not list an array the bank cannot follow.)
+        StateBank& bank = h->bank;
+        std::vector<StateBank::Twin> twin;
+        std::vector<Row> rows;
+        if (bank.slots) {
+            if (const int rc = bank_twin(h, bank.slots, fresh.dev.get(), 1, sizeof(Row), twin, "state bank: ", false)) return rc;
+            rows.assign((size_t)bank.slots, R0);
+            bank.twins.reserve(bank.twins.size() + 1);
+            SR_SETUP(h, hipMemcpy(twin[0].dev.get(), rows.data(), rows.size() * sizeof(Row), hipMemcpyHostToDevice),
+                     "state bank: ", false);
         }
-        slot = T.dev;
-        SR_HIP(h, hipMemcpy(h->d_state, &h->S, sizeof(StatePtrs), hipMemcpyHostToDevice));
+        StatePtrs S = h->S;
+        S.*slot = fresh.dev.get();
+        SR_SETUP(h, hipMemcpy(h->d_state, &S, sizeof(StatePtrs), hipMemcpyHostToDevice));
+        // nothing below can fail
+        h->S = S;
+        T = std::move(fresh);
+        if (bank.slots) {
+            bank.twins.push_back(std::move(twin[0]));
+            bank_host_rows(bank, T.dev.get()).swap(rows);
+        }
     } else {
-        SR_HIP(h, hipEventSynchronize(T.ev));   // the previous upload has left the staging buffer
+        SR_HIP(h, T.wait());    // the previous upload has left the staging buffer
     }
     for (size_t i = 0; i < N; ++i)
-        if (!mask || mask[i]) build(values + W * i, T.host[i]);
-    SR_HIP(h, hipMemcpyAsync(T.dev, T.host, N * sizeof(Row), hipMemcpyHostToDevice, st));
-    SR_HIP(h, hipEventRecord(T.ev, st));
+        if (!mask || mask[i]) build(values + W * i, T.host.get()[i]);
+    SR_HIP(h, T.send(N, st));
     return SOFTROD_OK;
 }
 
@@ -721,10 +784,10 @@ void launch_stamped(K kernel, const dim3& grid, const dim3& block, hipStream_t s
 int launch_step(softrod_handle* h, const float* actions, float* obs, double* reward,
                 uint8_t* term, uint8_t* trunc, double* aux, int n_sub, int epilogue, int pack,
                 hipStream_t st) {
-    if (h->q_depth > 0 && epilogue && !h->same_step) {
+    if (h->q.depth > 0 && epilogue && !h->same_step) {
         if (const int rc = launch_autoreset(h, obs, reward, term, trunc, aux, pack, st)) return rc;
         // shaped starts for the envs the pass just restarted, in front of the step's first dispatch and its time stamp
-        if (h->rs_count > 0)
+        if (h->rs.count > 0)
             if (const int rc = launch_reset_shapes(h, kPickSkipped, nullptr, obs, term, trunc, aux, pack, st)) return rc;
     }
     if ((h->cfg.features & SOFTROD_FEAT_COOMM_MUSCLES) && h->cfg.math_mode == SOFTROD_MATH_FAST) {
@@ -757,7 +820,7 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
     // A timed step: its pair of events rides on the step's own dispatches (launch_stamped) — the start on the first
     // kernel of the step, the stop on the last, one pair per step whatever the number of kernels.
     const bool timing = h->timed < (int)h->ev_start.size();
-    const hipEvent_t t0 = timing ? h->ev_start[h->timed] : nullptr, t1 = timing ? h->ev_stop[h->timed] : nullptr;
+    const hipEvent_t t0 = timing ? h->ev_start[h->timed].get() : nullptr, t1 = timing ? h->ev_stop[h->timed].get() : nullptr;
     // the muscle octopus: set_action | the body's substeps | get_state + reward; the timing events bracket all three
     const bool mocto = c.row->env == kMoctoEnvs;
     const bool action_first = mocto && epilogue && actions, epilogue_last = mocto && epilogue;
@@ -771,9 +834,9 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
     SR_HIP(h, hipGetLastError());
     if (timing) ++h->timed;
     // behind the timing record, so that kernel_times_ms keeps meaning the step (as for the NEXT_STEP pass in front)
-    if (h->q_depth > 0 && epilogue && h->same_step) {
+    if (h->q.depth > 0 && epilogue && h->same_step) {
         if (const int rc = launch_autoreset_same_step(h, obs, aux, pack, st)) return rc;
-        if (h->rs_count > 0)      // shaped starts for the envs that pass just restarted
+        if (h->rs.count > 0)      // shaped starts for the envs that pass just restarted
             if (const int rc = launch_reset_shapes(h, kPickFinished, nullptr, obs, term, trunc, aux, pack, st)) return rc;
     }
     return SOFTROD_OK;
@@ -782,18 +845,20 @@ int launch_step(softrod_handle* h, const float* actions, float* obs, double* rew
 int upload_and_reset(softrod_handle* h, hipStream_t st, bool use_mask) {
     const size_t N = (size_t)h->cfg.n_envs;
     if (const int rc = clear_planar_certs(h, st)) return rc;
-    SR_HIP(h, hipMemcpyAsync(h->d_init, h->h_init, N * h->init_stride * sizeof(double), hipMemcpyHostToDevice, st));
+    double* const d_init = h->reset.init.dev.get();
+    uint8_t* const d_mask = h->reset.d_mask.get();
+    SR_HIP(h, hipMemcpyAsync(d_init, h->reset.init.host.get(), N * h->init_stride * sizeof(double), hipMemcpyHostToDevice, st));
     if (use_mask)
-        SR_HIP(h, hipMemcpyAsync(h->d_mask, h->h_mask, N, hipMemcpyHostToDevice, st));
-    ResetArgs A{h->d_init, use_mask ? h->d_mask : nullptr};
+        SR_HIP(h, hipMemcpyAsync(d_mask, h->reset.h_mask.get(), N, hipMemcpyHostToDevice, st));
+    ResetArgs A{d_init, use_mask ? d_mask : nullptr};
     if (is_octo(h)) {
-        OctoResetArgs OA{h->d_init, h->d_init + N * (size_t)h->cfg.n_arm * 18, use_mask ? h->d_mask : nullptr};   // (targets: 2 numbers per env, 4 for the muscle octopus)
+        OctoResetArgs OA{d_init, d_init + N * (size_t)h->cfg.n_arm * 18, use_mask ? d_mask : nullptr};   // (targets: 2 numbers per env, 4 for the muscle octopus)
         hipLaunchKernelGGL(softrod_octo_reset_kernel, dim3((unsigned)N), dim3(kLanes * h->nw), 0, st, h->P, h->S, OA);
     } else
         hipLaunchKernelGGL(by_epl(h, softrod_reset_kernel<1>, softrod_reset_kernel<2>), dim3((unsigned)N), dim3(kLanes), 0, st,
                            h->P, h->S, A);
     SR_HIP(h, hipGetLastError());
-    SR_HIP(h, hipEventRecord(h->ev_reset, st));
+    SR_HIP(h, hipEventRecord(h->reset.init.ev.get(), st));
     h->was_reset = true;
     return SOFTROD_OK;
 }
@@ -1037,7 +1102,7 @@ void shape_handle(softrod_handle* h) {
 // Why softrod_copy_envs refuses these arguments (empty: it does not).  Host only; leaves h->is_dst all zero.
 std::string copy_envs_why_not(softrod_handle* h, const int32_t* src, const int32_t* dst, int count) {
     const int N = h->cfg.n_envs;
-    if (h->q_depth > 0)
+    if (h->q.depth > 0)
         return "copy envs: not on a handle with device-side auto-reset (the pending-reset flags and the staged queue "
                "belong to each env's RNG future)";
     if (count < 0 || count > N) return "copy envs: count " + std::to_string(count) + " is outside 0 .. n_envs = " + std::to_string(N);
@@ -1082,10 +1147,10 @@ CopyTable copy_table(const softrod_handle* h) {
     add(S.prev_kappa, 1, (size_t)c.n_arm * (size_t)(c.n_elem - 1) * sizeof(float));
     add(S.sucker, SOFTROD_MAX_SUCKERS, per * sizeof(double));
     add(S.sucker_idx, SOFTROD_MAX_SUCKERS, per * sizeof(int));
-    add(h->env_mat.dev, 1, sizeof(EnvMaterial));
-    add(h->env_contact.dev, 1, sizeof(EnvContact));
+    add(h->env_mat.dev.get(), 1, sizeof(EnvMaterial));
+    add(h->env_contact.dev.get(), 1, sizeof(EnvContact));
     // shaped starts: where the copy's episode started, and its resets' count (fork(copy_rng=False) puts dst's back)
-    add(h->d_rs_index, 1, sizeof(int)); add(h->d_rs_episode, 1, sizeof(int));
+    add(h->rs.index.get(), 1, sizeof(int)); add(h->rs.episode.get(), 1, sizeof(int));
     // planar certificates: a byte vouches for the rows above, so it travels with them (a bank slot keeps its own)
     add(S.planar_cert, 1, sizeof(uint8_t));
     static_assert(kCopyMaxArrays >= 23, "copy_table adds up to 23 arrays");
@@ -1095,16 +1160,17 @@ CopyTable copy_table(const softrod_handle* h) {
 // The pinned copy of a per-env table follows the device rows: the next softrod_set_env_* uploads all of it.
 template <class Row>
 hipError_t copy_table_rows(EnvTable<Row>& T, const int2* pairs, int n) {
-    if (!T.dev) return hipSuccess;
-    const hipError_t e = hipEventSynchronize(T.ev);      // the previous upload has left the staging buffer
+    if (!T.dev.get()) return hipSuccess;
+    const hipError_t e = T.wait();      // the previous upload has left the staging buffer
     if (e != hipSuccess) return e;
-    for (int i = 0; i < n; ++i) T.host[pairs[i].y] = T.host[pairs[i].x];
+    Row* const host = T.host.get();
+    for (int i = 0; i < n; ++i) host[pairs[i].y] = host[pairs[i].x];
     return hipSuccess;
 }
 
 // ---- the state bank (softrod_state_bank.hpp) ----
 // The bank's side of a batch table: the same arrays in the same order, each at its twin, `slots` rows per component.
-// false: an array of the batch has no twin (every call that creates a per-env array after the bank adopts it: bank_adopt).
+// false: an array of the batch has no twin (every call that creates a per-env array after the bank gives it a twin: bank_twin).
 bool bank_table(const StateBank& bank, const CopyTable& batch, CopyTable& out) {
     out = batch;
     out.n_envs = bank.slots;
@@ -1113,58 +1179,34 @@ bool bank_table(const StateBank& bank, const CopyTable& batch, CopyTable& out) {
     return true;
 }
 
-// Allocate, zeroed, the twin of every array of copy_table(h) that `bank` has none for yet.  A failed call frees what it
-// allocated and leaves `bank` as it was.
-hipError_t bank_adopt(const softrod_handle* h, StateBank& bank) {
-    const CopyTable T = copy_table(h);
-    const size_t had = bank.twins.size();
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < T.n && e == hipSuccess; ++k) {
-        if (bank.twin_of(T.a[k].base)) continue;
-        const size_t bytes = (size_t)T.a[k].comps * (size_t)bank.slots * (size_t)T.a[k].row_bytes;
-        unsigned char* p = nullptr;
-        e = hipMalloc((void**)&p, bytes);
-        if (e == hipSuccess) {
-            bank.twins.push_back({T.a[k].base, p});
-            e = hipMemset(p, 0, bytes);
-        }
-    }
-    if (e != hipSuccess) {
-        for (size_t i = had; i < bank.twins.size(); ++i) (void)hipFree(bank.twins[i].dev);
-        bank.twins.resize(had);
-    }
-    return e;
+// One set-up call: the twin, zeroed, that a bank of `slots` slots holds for the per-env array at `base` (its `comps`
+// and `row_bytes` as copy_table lists them), appended to `out` — the caller's local list, which it moves into the bank
+// when it commits.  A failure is reported in the caller's words (SR_SETUP).
+int bank_twin(softrod_handle* h, int slots, const void* base, size_t comps, size_t row_bytes, std::vector<StateBank::Twin>& out,
+              const char* prefix, bool oom_is_enomem) {
+    DeviceBuf<unsigned char> dev;
+    SR_SETUP(h, dev.alloc(comps * (size_t)slots * row_bytes, true), prefix, oom_is_enomem);
+    out.push_back({base, std::move(dev)});
+    return SOFTROD_OK;
 }
 
 std::vector<EnvMaterial>& bank_host_rows(StateBank& b, const EnvMaterial*) { return b.mat; }
 std::vector<EnvContact>& bank_host_rows(StateBank& b, const EnvContact*) { return b.contact; }
 
-// A per-env table created after the bank: its twin, with every slot at the row the new table gives an untouched env
-// (`row`), so that a slot saved before the table existed loads as its env would be now.
-template <class Row>
-hipError_t bank_adopt_table(softrod_handle* h, const Row* table, const Row& row) {
-    StateBank& bank = h->bank;
-    if (!bank.slots) return hipSuccess;
-    hipError_t e = bank_adopt(h, bank);
-    if (e != hipSuccess) return e;
-    std::vector<Row>& rows = bank_host_rows(bank, table);
-    rows.assign((size_t)bank.slots, row);
-    return hipMemcpy(bank.twin_of(table), rows.data(), rows.size() * sizeof(Row), hipMemcpyHostToDevice);
-}
-
 // The pinned copy of a per-env table and the bank's host rows follow the device rows, as copy_table_rows does for
 // softrod_copy_envs.  pairs: (env, slot) for a save, (slot, env) for a load.
 template <class Row>
 hipError_t bank_table_rows(StateBank& bank, EnvTable<Row>& T, const int2* pairs, int n, bool load) {
-    if (!T.dev) return hipSuccess;
-    std::vector<Row>& rows = bank_host_rows(bank, T.dev);
+    if (!T.dev.get()) return hipSuccess;
+    std::vector<Row>& rows = bank_host_rows(bank, T.dev.get());
+    Row* const host = T.host.get();
     if (!load) {
-        for (int i = 0; i < n; ++i) rows[pairs[i].y] = T.host[pairs[i].x];
+        for (int i = 0; i < n; ++i) rows[pairs[i].y] = host[pairs[i].x];
         return hipSuccess;
     }
-    const hipError_t e = hipEventSynchronize(T.ev);      // the previous upload has left the staging buffer
+    const hipError_t e = T.wait();      // the previous upload has left the staging buffer
     if (e != hipSuccess) return e;
-    for (int i = 0; i < n; ++i) T.host[pairs[i].y] = rows[pairs[i].x];
+    for (int i = 0; i < n; ++i) host[pairs[i].y] = rows[pairs[i].x];
     return hipSuccess;
 }
 
@@ -1176,7 +1218,7 @@ std::string bank_why_not(softrod_handle* h, const int32_t* envs, const int32_t* 
     StateBank& bank = h->bank;
     const int N = h->cfg.n_envs, K = bank.slots;
     if (!K) return what + "the handle has no state bank (softrod_bank_create)";
-    if (h->q_depth > 0)
+    if (h->q.depth > 0)
         return what + "not on a handle with device-side auto-reset (the pending-reset flags and the staged queue "
                       "belong to each env's RNG future)";
     const int limit = load ? N : K;
@@ -1214,14 +1256,14 @@ int bank_copy(softrod_handle* h, const int32_t* envs, const int32_t* slots, int 
         return fail(h, SOFTROD_EINVAL, std::string(load ? "bank load" : "bank save") + ": a per-env array of the handle has no twin in the bank");
     SR_ON_DEVICE(h);
     hipStream_t st = (hipStream_t)stream;
-    SR_HIP(h, hipEventSynchronize(bank.ev_pairs));     // the previous call's pairs have left the staging buffer
-    for (int i = 0; i < count; ++i) bank.h_pairs[i] = load ? make_int2(slots[i], envs[i]) : make_int2(envs[i], slots[i]);
-    SR_HIP(h, bank_table_rows(bank, h->env_mat, bank.h_pairs, count, load));
-    SR_HIP(h, bank_table_rows(bank, h->env_contact, bank.h_pairs, count, load));
-    SR_HIP(h, hipMemcpyAsync(bank.d_pairs, bank.h_pairs, (size_t)count * sizeof(int2), hipMemcpyHostToDevice, st));
-    SR_HIP(h, hipEventRecord(bank.ev_pairs, st));
+    SR_HIP(h, bank.pairs.wait());       // the previous call's pairs have left the staging buffer
+    int2* const h_pairs = bank.pairs.host.get();
+    for (int i = 0; i < count; ++i) h_pairs[i] = load ? make_int2(slots[i], envs[i]) : make_int2(envs[i], slots[i]);
+    SR_HIP(h, bank_table_rows(bank, h->env_mat, h_pairs, count, load));
+    SR_HIP(h, bank_table_rows(bank, h->env_contact, h_pairs, count, load));
+    SR_HIP(h, bank.pairs.send((size_t)count, st));
     hipLaunchKernelGGL(softrod_bank_copy_kernel, dim3((unsigned)count), dim3(kCopyThreads), 0, st,
-                       load ? twin : batch, load ? batch : twin, bank.d_pairs);
+                       load ? twin : batch, load ? batch : twin, bank.pairs.dev.get());
     SR_HIP(h, hipGetLastError());
     if (load && h->S.planar_cert) h->cert_live = true;      // (a slot's certificate travels with its rows)
     if (!load)
@@ -1507,8 +1549,21 @@ int softrod_create(const softrod_config* cfg, int device, softrod_handle** out) 
     const size_t adim = (size_t)softrod_config_action_dim(cfg);
     const size_t rowb = N * kLanes * h->epl * h->nw * sizeof(double);
     int rc = SOFTROD_OK;
-    auto alloc = [&](auto*& p, size_t bytes) {
-        if (rc == SOFTROD_OK && alloc_owned(h, p, bytes) != hipSuccess) rc = p ? SOFTROD_EHIP : SOFTROD_ENOMEM;
+    // every step of the set-up runs only while the ones before it succeeded; what was made is released with the handle
+    auto zeroed = [&](auto& buf, size_t bytes) {        // zero-filled
+        if (rc == SOFTROD_OK && buf.alloc(bytes, true) != hipSuccess) rc = buf.get() ? SOFTROD_EHIP : SOFTROD_ENOMEM;
+    };
+    auto alloc = [&](auto*& p, size_t bytes) {          // into h->owned: the buffer lives as long as the handle
+        DeviceBuf<unsigned char> buf;
+        zeroed(buf, bytes);
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(buf.get());
+        if (buf.get()) h->owned.push_back(std::move(buf));
+    };
+    auto pinned = [&](auto& buf, size_t bytes) {
+        if (rc == SOFTROD_OK && buf.alloc(bytes) != hipSuccess) rc = SOFTROD_ENOMEM;
+    };
+    auto event = [&](Event& ev) {
+        if (rc == SOFTROD_OK && ev.create(hipEventDisableTiming) != hipSuccess) rc = SOFTROD_EHIP;
     };
     auto upload = [&](void* dst, const void* src, size_t bytes) {
         if (rc == SOFTROD_OK && hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = SOFTROD_EHIP;
@@ -1583,16 +1638,14 @@ int softrod_create(const softrod_config* cfg, int device, softrod_handle** out) 
     }
     alloc(h->d_basis, (size_t)2 * kLanes * 7 * sizeof(double));
     h->S.basis = h->d_basis;
-    alloc(h->d_init, N * h->init_stride * sizeof(double));
-    alloc(h->d_mask, N);
-    if (rc == SOFTROD_OK && hipHostMalloc((void**)&h->h_init, N * h->init_stride * sizeof(double)) != hipSuccess) rc = SOFTROD_ENOMEM;
-    if (rc == SOFTROD_OK && hipHostMalloc((void**)&h->h_mask, N) != hipSuccess) rc = SOFTROD_ENOMEM;
-    if (rc == SOFTROD_OK && hipEventCreateWithFlags(&h->ev_reset, hipEventDisableTiming) != hipSuccess)
-        rc = SOFTROD_EHIP;
-    alloc(h->d_pairs, N * sizeof(int2));
-    if (rc == SOFTROD_OK && hipHostMalloc((void**)&h->h_pairs, N * sizeof(int2)) != hipSuccess) rc = SOFTROD_ENOMEM;
-    if (rc == SOFTROD_OK && hipEventCreateWithFlags(&h->ev_pairs, hipEventDisableTiming) != hipSuccess)
-        rc = SOFTROD_EHIP;
+    zeroed(h->reset.init.dev, N * h->init_stride * sizeof(double));
+    zeroed(h->reset.d_mask, N);
+    pinned(h->reset.init.host, N * h->init_stride * sizeof(double));
+    pinned(h->reset.h_mask, N);
+    event(h->reset.init.ev);
+    zeroed(h->pairs.dev, N * sizeof(int2));
+    pinned(h->pairs.host, N * sizeof(int2));
+    event(h->pairs.ev);
     h->is_dst.assign(N, 0);
     upload(h->d_state, &h->S, sizeof(StatePtrs));
     if (rc != SOFTROD_OK) {
@@ -1608,123 +1661,82 @@ int softrod_reset_octo(softrod_handle* h, const double* arm_start, const double*
     if (!h || !arm_start || !arm_direction || !target) return fail(h, SOFTROD_EINVAL, "null argument");
     if (!is_flat(h) && !is_mocto(h)) return fail(h, SOFTROD_EINVAL, "softrod_reset_octo is for SOFTROD_ENV_OCTO_FLAT and the muscle octopus envs");
     SR_ON_DEVICE(h);
-    SR_HIP(h, hipEventSynchronize(h->ev_reset));
+    SR_HIP(h, h->reset.init.wait());
     const size_t N = (size_t)h->cfg.n_envs, na = (size_t)h->cfg.n_arm, td = octo_target_dim(h);
-    double* tgt = h->h_init + N * na * 18;
+    double* const h_init = h->reset.init.host.get();
+    uint8_t* const h_mask = h->reset.h_mask.get();
+    double* tgt = h_init + N * na * 18;
     for (size_t e = 0; e < N; ++e) {
-        if (mask) h->h_mask[e] = mask[e];
+        if (mask) h_mask[e] = mask[e];
         if (mask && !mask[e]) continue;
-        octo_record(h, arm_start + 3 * na * e, arm_direction + 3 * na * e, target + td * e, h->h_init + e * na * 18, tgt + td * e);
+        octo_record(h, arm_start + 3 * na * e, arm_direction + 3 * na * e, target + td * e, h_init + e * na * 18, tgt + td * e);
     }
     return upload_and_reset(h, (hipStream_t)stream, mask != nullptr);
 }
 
 // ---- device-side auto-reset ------------------------------------------------------------------
-namespace {
-// Everything softrod_autoreset_enable allocates, released (idempotent; also softrod_destroy's path).
-void autoreset_release(softrod_handle* h) {
-    void* dbufs[] = {h->d_queue, h->d_consumed, h->d_produced, h->d_underflow, h->d_flags, h->d_stage, h->d_where};
-    for (void* p : dbufs) if (p) (void)hipFree(p);
-    void* hbufs[] = {h->h_queue, h->h_produced, h->h_stage, h->h_where, h->h_status};
-    for (void* p : hbufs) if (p) (void)hipHostFree(p);
-    if (h->ev_queue) (void)hipEventDestroy(h->ev_queue);
-    if (h->ev_status) (void)hipEventDestroy(h->ev_status);
-    h->d_queue = nullptr; h->d_consumed = nullptr; h->d_produced = nullptr; h->d_underflow = nullptr;
-    h->d_flags = nullptr; h->d_stage = nullptr; h->d_where = nullptr;
-    h->h_queue = nullptr; h->h_produced = nullptr; h->h_stage = nullptr; h->h_where = nullptr; h->h_status = nullptr;
-    h->ev_queue = nullptr; h->ev_status = nullptr;
-    h->stage_cap = 0;
-    h->q_depth = 0;
-}
-
-int autoreset_allocate(softrod_handle* h, int depth, int fail_at) {
-    int calls = 0;
-    // fail_at > 0: the fail_at-th HIP call of this function "fails" without being made (failure injection
-    // of tests/test_gpu_debug_switches.py; 0 in production)
-#define SR_Q(call)                                                                                  \
-    do {                                                                                            \
-        if (++calls == fail_at) return fail(h, SOFTROD_EHIP, "softrod_autoreset_enable: injected failure at call " + std::to_string(calls)); \
-        SR_HIP(h, call);                                                                            \
-    } while (0)
+int softrod_autoreset_enable(softrod_handle* h, int depth) {
+    if (!h || depth < 1 || depth > 4096) return fail(h, SOFTROD_EINVAL, "need 1 <= depth <= 4096");
+    if (h->q.depth) return fail(h, SOFTROD_EINVAL, "auto-reset is already enabled");
+    if (h->cfg.env_kind == SOFTROD_ENV_NONE) return fail(h, SOFTROD_EINVAL, "env_kind NONE has no episodes");
+    SR_ON_DEVICE(h);
+    arm_setup(h, "softrod_autoreset_enable");
     const size_t N = (size_t)h->cfg.n_envs;
     const size_t qb = (size_t)depth * N * h->init_stride * sizeof(double);
-    SR_Q(hipMalloc((void**)&h->d_queue, qb));
-    SR_Q(hipMemset(h->d_queue, 0, qb));
-    SR_Q(hipHostMalloc((void**)&h->h_queue, qb));
-    SR_Q(hipMalloc((void**)&h->d_consumed, N * sizeof(int)));
-    SR_Q(hipMalloc((void**)&h->d_produced, N * sizeof(int)));
-    SR_Q(hipMalloc((void**)&h->d_underflow, sizeof(int)));
-    SR_Q(hipMalloc((void**)&h->d_flags, 2 * N));
-    SR_Q(hipMemset(h->d_consumed, 0, N * sizeof(int)));
-    SR_Q(hipMemset(h->d_produced, 0, N * sizeof(int)));
-    SR_Q(hipMemset(h->d_underflow, 0, sizeof(int)));
-    SR_Q(hipMemset(h->d_flags, 0, 2 * N));
-    SR_Q(hipHostMalloc((void**)&h->h_produced, N * sizeof(int)));
-    std::memset(h->h_produced, 0, N * sizeof(int));
-    SR_Q(hipEventCreateWithFlags(&h->ev_queue, hipEventDisableTiming));
-    h->stage_cap = 2 * N;     // pushes of more records than this upload the whole ring instead
-    SR_Q(hipHostMalloc((void**)&h->h_stage, h->stage_cap * h->init_stride * sizeof(double)));
-    SR_Q(hipHostMalloc((void**)&h->h_where, h->stage_cap * sizeof(int2)));
-    SR_Q(hipMalloc((void**)&h->d_stage, h->stage_cap * h->init_stride * sizeof(double)));
-    SR_Q(hipMalloc((void**)&h->d_where, h->stage_cap * sizeof(int2)));
-    SR_Q(hipHostMalloc((void**)&h->h_status, (N + 1) * sizeof(int)));
-    SR_Q(hipEventCreateWithFlags(&h->ev_status, hipEventDisableTiming));
+    ResetQueue q;
+    SR_SETUP(h, q.ring.dev.alloc(qb));
+    SR_SETUP(h, hipMemset(q.ring.dev.get(), 0, qb));
+    SR_SETUP(h, q.ring.host.alloc(qb));
+    SR_SETUP(h, q.d_consumed.alloc(N * sizeof(int)));
+    SR_SETUP(h, q.d_produced.alloc(N * sizeof(int)));
+    SR_SETUP(h, q.d_underflow.alloc(sizeof(int)));
+    SR_SETUP(h, q.d_flags.alloc(2 * N));
+    SR_SETUP(h, hipMemset(q.d_consumed.get(), 0, N * sizeof(int)));
+    SR_SETUP(h, hipMemset(q.d_produced.get(), 0, N * sizeof(int)));
+    SR_SETUP(h, hipMemset(q.d_underflow.get(), 0, sizeof(int)));
+    SR_SETUP(h, hipMemset(q.d_flags.get(), 0, 2 * N));
+    SR_SETUP(h, q.h_produced.alloc(N * sizeof(int)));
+    std::memset(q.h_produced.get(), 0, N * sizeof(int));
+    SR_SETUP(h, q.ring.ev.create(hipEventDisableTiming));
+    q.stage_cap = 2 * N;      // pushes of more records than this upload the whole ring instead
+    SR_SETUP(h, q.h_stage.alloc(q.stage_cap * h->init_stride * sizeof(double)));
+    SR_SETUP(h, q.h_where.alloc(q.stage_cap * sizeof(int2)));
+    SR_SETUP(h, q.d_stage.alloc(q.stage_cap * h->init_stride * sizeof(double)));
+    SR_SETUP(h, q.d_where.alloc(q.stage_cap * sizeof(int2)));
+    SR_SETUP(h, q.h_status.alloc((N + 1) * sizeof(int)));
+    SR_SETUP(h, q.ev_status.create(hipEventDisableTiming));
+    std::vector<int> seen(N, 0);
     // the device copy of the state pointers is the LAST thing to change: a failure above leaves it
     // (and h->S) exactly as it was, so the handle keeps stepping without auto-reset
     StatePtrs S = h->S;
-    S.needs_reset = h->d_flags;
-    S.skip = h->d_flags + N;
-    S.queue = h->d_queue;
-    S.q_consumed = h->d_consumed;
-    S.q_produced = h->d_produced;
-    S.q_underflow = h->d_underflow;
+    S.needs_reset = q.d_flags.get();
+    S.skip = q.d_flags.get() + N;
+    S.queue = q.ring.dev.get();
+    S.q_consumed = q.d_consumed.get();
+    S.q_produced = q.d_produced.get();
+    S.q_underflow = q.d_underflow.get();
     S.q_depth = depth;
     S.q_record = (int)h->init_stride;
-    SR_Q(hipMemcpy(h->d_state, &S, sizeof(StatePtrs), hipMemcpyHostToDevice));
+    SR_SETUP(h, hipMemcpy(h->d_state, &S, sizeof(StatePtrs), hipMemcpyHostToDevice));
     h->S = S;
-    h->seen_consumed.assign(N, 0);
-    h->q_depth = depth;
+    h->seen_consumed.swap(seen);
+    q.depth = depth;
+    h->q = std::move(q);
     return SOFTROD_OK;
-#undef SR_Q
-}
-}  // namespace
-
-int softrod_autoreset_enable(softrod_handle* h, int depth) {
-    if (!h || depth < 1 || depth > 4096) return fail(h, SOFTROD_EINVAL, "need 1 <= depth <= 4096");
-    if (h->q_depth) return fail(h, SOFTROD_EINVAL, "auto-reset is already enabled");
-    if (h->cfg.env_kind == SOFTROD_ENV_NONE) return fail(h, SOFTROD_EINVAL, "env_kind NONE has no episodes");
-    SR_ON_DEVICE(h);
-    // SOFTROD_DEBUG_FAIL_AUTORESET_CALL=k (honoured only with SOFTROD_DEBUG_SWITCHES=1): the k-th HIP call of
-    // the set-up fails, for the test that a failed enable leaves nothing allocated and can be retried
-    int fail_at = 0;
-    {
-        const char* dbg = std::getenv("SOFTROD_DEBUG_SWITCHES");
-        const char* k = (dbg && dbg[0] == '1') ? std::getenv("SOFTROD_DEBUG_FAIL_AUTORESET_CALL") : nullptr;
-        if (k) fail_at = std::atoi(k);
-    }
-    const int rc = autoreset_allocate(h, depth, fail_at);
-    if (rc != SOFTROD_OK) {
-        const std::string why = h->err;
-        autoreset_release(h);      // nothing of the failed attempt stays allocated; a retry starts clean
-        h->err = why;
-    }
-    return rc;
 }
 
 int softrod_autoreset_same_step(softrod_handle* h, int on) {
     if (!h) return fail(h, SOFTROD_EINVAL, "null argument");
-    if (!h->q_depth) return fail(h, SOFTROD_EINVAL, "call softrod_autoreset_enable first");
+    if (!h->q.depth) return fail(h, SOFTROD_EINVAL, "call softrod_autoreset_enable first");
     SR_ON_DEVICE(h);
-    if (on && !h->d_final_obs) {
-        // owned buffers, zero-filled: released with the handle, kept through on = 0 so that the pointers
-        // softrod_final_view hands out stay good for the handle's life
+    if (on && !h->final.obs.get()) {        // zero-filled
+        arm_setup(h, "softrod_autoreset_same_step");
         const size_t N = (size_t)h->cfg.n_envs;
-        float* fo = nullptr;
-        double *ft = nullptr, *fa = nullptr;
-        SR_HIP(h, alloc_owned(h, fo, N * (size_t)softrod_config_obs_dim(&h->cfg) * sizeof(float)));
-        SR_HIP(h, alloc_owned(h, ft, N * sizeof(double)));
-        SR_HIP(h, alloc_owned(h, fa, N * sizeof(double)));
-        h->d_final_obs = fo; h->d_final_time = ft; h->d_final_aux = fa;
+        FinalRows rows;
+        SR_SETUP(h, rows.obs.alloc(N * (size_t)softrod_config_obs_dim(&h->cfg) * sizeof(float), true));
+        SR_SETUP(h, rows.time.alloc(N * sizeof(double), true));
+        SR_SETUP(h, rows.aux.alloc(N * sizeof(double), true));
+        h->final = std::move(rows);
     }
     h->same_step = on != 0;
     return SOFTROD_OK;
@@ -1733,9 +1745,9 @@ int softrod_autoreset_same_step(softrod_handle* h, int on) {
 int softrod_final_view(softrod_handle* h, float** final_obs, double** final_time, double** final_aux) {
     if (!h || !final_obs || !final_time || !final_aux) return fail(h, SOFTROD_EINVAL, "null argument");
     if (!h->same_step) return fail(h, SOFTROD_EINVAL, "call softrod_autoreset_same_step first");
-    *final_obs = h->d_final_obs;
-    *final_time = h->d_final_time;
-    *final_aux = h->d_final_aux;
+    *final_obs = h->final.obs.get();
+    *final_time = h->final.time.get();
+    *final_aux = h->final.aux.get();
     return SOFTROD_OK;
 }
 
@@ -1743,43 +1755,47 @@ namespace {
 // Next free record of env e, or nullptr if staging `count` more would overwrite records the
 // device may not have consumed yet (as far as the last softrod_queue_status knows).
 int queue_begin(softrod_handle* h, const int32_t* counts, int max_count) {
-    if (!h->q_depth) return fail(h, SOFTROD_EINVAL, "call softrod_autoreset_enable first");
+    if (!h->q.depth) return fail(h, SOFTROD_EINVAL, "call softrod_autoreset_enable first");
     if (!counts || max_count < 0) return fail(h, SOFTROD_EINVAL, "bad argument");
     const int N = h->cfg.n_envs;
+    const int* const produced = h->q.h_produced.get();
     for (int e = 0; e < N; ++e) {
         if (counts[e] < 0 || counts[e] > max_count) return fail(h, SOFTROD_EINVAL, "counts[e] out of range");
-        if (h->h_produced[e] + counts[e] - h->seen_consumed[e] > h->q_depth)
+        if (produced[e] + counts[e] - h->seen_consumed[e] > h->q.depth)
             return fail(h, SOFTROD_EINVAL, "reset queue overflow: staged + new records exceed depth");
     }
-    SR_HIP(h, hipEventSynchronize(h->ev_queue));   // previous upload out of the pinned mirror
+    SR_HIP(h, h->q.ring.wait());    // previous upload out of the pinned mirror
     return SOFTROD_OK;
 }
-double* queue_slot(softrod_handle* h, int e, int k) {
-    h->pending.push_back(make_int2(e, k % h->q_depth));
-    return h->h_queue + ((size_t)(k % h->q_depth) * (size_t)h->cfg.n_envs + (size_t)e) * h->init_stride;
+// the next record of env e: its slot in the pinned mirror, counted as produced and noted for the commit
+double* queue_slot(softrod_handle* h, int e) {
+    const int k = h->q.h_produced.get()[e]++ % h->q.depth;
+    h->pending.push_back(make_int2(e, k));
+    return h->q.ring.host.get() + ((size_t)k * (size_t)h->cfg.n_envs + (size_t)e) * h->init_stride;
 }
 int queue_commit(softrod_handle* h, hipStream_t st) {
+    const ResetQueue& q = h->q;
     const size_t N = (size_t)h->cfg.n_envs;
     const size_t M = h->pending.size(), R = h->init_stride;
-    if (M > 0 && M <= h->stage_cap) {
+    if (M > 0 && M <= q.stage_cap) {
         // only the records of this push cross PCIe: compacted copy + a scatter kernel
         for (size_t m = 0; m < M; ++m) {
             const int2 w = h->pending[m];
-            std::memcpy(h->h_stage + m * R, h->h_queue + ((size_t)w.y * N + (size_t)w.x) * R, R * sizeof(double));
-            h->h_where[m] = w;
+            std::memcpy(q.h_stage.get() + m * R, q.ring.host.get() + ((size_t)w.y * N + (size_t)w.x) * R, R * sizeof(double));
+            q.h_where.get()[m] = w;
         }
-        SR_HIP(h, hipMemcpyAsync(h->d_stage, h->h_stage, M * R * sizeof(double), hipMemcpyHostToDevice, st));
-        SR_HIP(h, hipMemcpyAsync(h->d_where, h->h_where, M * sizeof(int2), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(softrod_queue_scatter_kernel, dim3((unsigned)M), dim3(kLanes), 0, st, h->d_queue, h->d_stage,
-                           h->d_where, (int)N, (int)R);
+        SR_HIP(h, hipMemcpyAsync(q.d_stage.get(), q.h_stage.get(), M * R * sizeof(double), hipMemcpyHostToDevice, st));
+        SR_HIP(h, hipMemcpyAsync(q.d_where.get(), q.h_where.get(), M * sizeof(int2), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(softrod_queue_scatter_kernel, dim3((unsigned)M), dim3(kLanes), 0, st, q.ring.dev.get(), q.d_stage.get(),
+                           q.d_where.get(), (int)N, (int)R);
         SR_HIP(h, hipGetLastError());
     } else if (M > 0) {
-        SR_HIP(h, hipMemcpyAsync(h->d_queue, h->h_queue, (size_t)h->q_depth * N * R * sizeof(double),
+        SR_HIP(h, hipMemcpyAsync(q.ring.dev.get(), q.ring.host.get(), (size_t)q.depth * N * R * sizeof(double),
                                  hipMemcpyHostToDevice, st));
     }
     h->pending.clear();
-    SR_HIP(h, hipMemcpyAsync(h->d_produced, h->h_produced, N * sizeof(int), hipMemcpyHostToDevice, st));
-    SR_HIP(h, hipEventRecord(h->ev_queue, st));
+    SR_HIP(h, hipMemcpyAsync(q.d_produced.get(), q.h_produced.get(), N * sizeof(int), hipMemcpyHostToDevice, st));
+    SR_HIP(h, hipEventRecord(q.ring.ev.get(), st));
     return SOFTROD_OK;
 }
 }  // namespace
@@ -1793,7 +1809,7 @@ int softrod_queue_push(softrod_handle* h, const double* theta0, const int32_t* c
     if (rc != SOFTROD_OK) return rc;
     for (int e = 0; e < h->cfg.n_envs; ++e)
         for (int j = 0; j < counts[e]; ++j)
-            theta_record(h, theta0[(size_t)e * max_count + j], queue_slot(h, e, h->h_produced[e]++));
+            theta_record(h, theta0[(size_t)e * max_count + j], queue_slot(h, e));
     return queue_commit(h, (hipStream_t)stream);
 }
 
@@ -1807,7 +1823,7 @@ int softrod_queue_push_straight(softrod_handle* h, const double* start, const do
     for (int e = 0; e < h->cfg.n_envs; ++e)
         for (int j = 0; j < counts[e]; ++j) {
             const size_t k = ((size_t)e * max_count + j) * 3;
-            double* rec = queue_slot(h, e, h->h_produced[e]++);
+            double* rec = queue_slot(h, e);
             straight_record(h, start + k, direction + k, normal + k, rec, rec + 18);
         }
     return queue_commit(h, (hipStream_t)stream);
@@ -1823,7 +1839,7 @@ int softrod_queue_push_octo(softrod_handle* h, const double* arm_start, const do
     const size_t na = (size_t)h->cfg.n_arm, td = octo_target_dim(h);
     for (int e = 0; e < h->cfg.n_envs; ++e)
         for (int j = 0; j < counts[e]; ++j) {
-            double* rec = queue_slot(h, e, h->h_produced[e]++);
+            double* rec = queue_slot(h, e);
             const size_t k = (size_t)e * max_count + j;
             octo_record(h, arm_start + 3 * na * k, arm_direction + 3 * na * k, target + td * k, rec, rec + na * 18);
         }
@@ -1832,12 +1848,12 @@ int softrod_queue_push_octo(softrod_handle* h, const double* arm_start, const do
 
 int softrod_queue_status(softrod_handle* h, int32_t* consumed, int32_t* underflow, void* stream) {
     if (!h || !consumed) return fail(h, SOFTROD_EINVAL, "null argument");
-    if (!h->q_depth) return fail(h, SOFTROD_EINVAL, "call softrod_autoreset_enable first");
+    if (!h->q.depth) return fail(h, SOFTROD_EINVAL, "call softrod_autoreset_enable first");
     SR_ON_DEVICE(h);
     const size_t N = (size_t)h->cfg.n_envs;
     int uf = 0;
-    SR_HIP(h, hipMemcpyAsync(consumed, h->d_consumed, N * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    SR_HIP(h, hipMemcpyAsync(&uf, h->d_underflow, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    SR_HIP(h, hipMemcpyAsync(consumed, h->q.d_consumed.get(), N * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    SR_HIP(h, hipMemcpyAsync(&uf, h->q.d_underflow.get(), sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
     SR_HIP(h, hipStreamSynchronize((hipStream_t)stream));
     for (size_t e = 0; e < N; ++e) h->seen_consumed[e] = consumed[e];
     if (underflow) *underflow = uf;
@@ -1846,12 +1862,12 @@ int softrod_queue_status(softrod_handle* h, int32_t* consumed, int32_t* underflo
 
 int softrod_queue_status_begin(softrod_handle* h, void* stream) {
     if (!h) return fail(h, SOFTROD_EINVAL, "null argument");
-    if (!h->q_depth) return fail(h, SOFTROD_EINVAL, "call softrod_autoreset_enable first");
+    if (!h->q.depth) return fail(h, SOFTROD_EINVAL, "call softrod_autoreset_enable first");
     SR_ON_DEVICE(h);
     const size_t N = (size_t)h->cfg.n_envs;
-    SR_HIP(h, hipMemcpyAsync(h->h_status, h->d_consumed, N * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    SR_HIP(h, hipMemcpyAsync(h->h_status + N, h->d_underflow, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    SR_HIP(h, hipEventRecord(h->ev_status, (hipStream_t)stream));
+    SR_HIP(h, hipMemcpyAsync(h->q.h_status.get(), h->q.d_consumed.get(), N * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    SR_HIP(h, hipMemcpyAsync(h->q.h_status.get() + N, h->q.d_underflow.get(), sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    SR_HIP(h, hipEventRecord(h->q.ev_status.get(), (hipStream_t)stream));
     h->status_pending = true;
     return SOFTROD_OK;
 }
@@ -1860,34 +1876,36 @@ int softrod_queue_status_poll(softrod_handle* h, int wait, int32_t* consumed, in
     if (!h || !consumed) return fail(h, SOFTROD_EINVAL, "null argument");
     if (!h->status_pending) return fail(h, SOFTROD_EINVAL, "no softrod_queue_status_begin outstanding");
     SR_ON_DEVICE(h);
-    const hipError_t q = wait ? hipEventSynchronize(h->ev_status) : hipEventQuery(h->ev_status);
+    const hipError_t q = wait ? hipEventSynchronize(h->q.ev_status.get()) : hipEventQuery(h->q.ev_status.get());
     if (q == hipErrorNotReady) return 0;
     if (q != hipSuccess) return fail(h, SOFTROD_EHIP, std::string("queue status event: ") + hipGetErrorString(q));
     const size_t N = (size_t)h->cfg.n_envs;
-    for (size_t e = 0; e < N; ++e) { consumed[e] = h->h_status[e]; h->seen_consumed[e] = h->h_status[e]; }
-    if (underflow) *underflow = h->h_status[N];
+    const int* const status = h->q.h_status.get();
+    for (size_t e = 0; e < N; ++e) { consumed[e] = status[e]; h->seen_consumed[e] = status[e]; }
+    if (underflow) *underflow = status[N];
     h->status_pending = false;
     return 1;
 }
 
 int softrod_queue_advance(softrod_handle* h, const int32_t* by, void* stream) {
     if (!h || !by) return fail(h, SOFTROD_EINVAL, "null argument");
-    if (!h->q_depth) return fail(h, SOFTROD_EINVAL, "call softrod_autoreset_enable first");
+    if (!h->q.depth) return fail(h, SOFTROD_EINVAL, "call softrod_autoreset_enable first");
     SR_ON_DEVICE(h);
     const int N = h->cfg.n_envs;
     // consumed += by (by < 0: := produced).  The device counters are only ever written by the
     // auto-reset pass, which is stream-ordered with these copies.
     std::vector<int> cons((size_t)N);
-    SR_HIP(h, hipMemcpyAsync(cons.data(), h->d_consumed, (size_t)N * sizeof(int), hipMemcpyDeviceToHost,
+    SR_HIP(h, hipMemcpyAsync(cons.data(), h->q.d_consumed.get(), (size_t)N * sizeof(int), hipMemcpyDeviceToHost,
                              (hipStream_t)stream));
     SR_HIP(h, hipStreamSynchronize((hipStream_t)stream));
+    const int* const produced = h->q.h_produced.get();
     for (int e = 0; e < N; ++e) {
-        int c = by[e] < 0 ? h->h_produced[e] : cons[(size_t)e] + by[e];
-        if (c > h->h_produced[e]) c = h->h_produced[e];
+        int c = by[e] < 0 ? produced[e] : cons[(size_t)e] + by[e];
+        if (c > produced[e]) c = produced[e];
         cons[(size_t)e] = c;
         h->seen_consumed[(size_t)e] = c;
     }
-    SR_HIP(h, hipMemcpyAsync(h->d_consumed, cons.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice,
+    SR_HIP(h, hipMemcpyAsync(h->q.d_consumed.get(), cons.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice,
                              (hipStream_t)stream));
     SR_HIP(h, hipStreamSynchronize((hipStream_t)stream));
     return SOFTROD_OK;
@@ -1897,12 +1915,14 @@ int softrod_reset(softrod_handle* h, const double* theta0, const uint8_t* mask, 
     if (!h || !theta0) return fail(h, SOFTROD_EINVAL, "null argument");
     if (is_octo(h)) return fail(h, SOFTROD_EINVAL, "rigid-body envs reset through softrod_reset_octo / softrod_reset_straight");
     SR_ON_DEVICE(h);
-    SR_HIP(h, hipEventSynchronize(h->ev_reset));  // previous upload out of the pinned buffers
+    SR_HIP(h, h->reset.init.wait());    // previous upload out of the pinned buffers
     const int N = h->cfg.n_envs;
+    double* const h_init = h->reset.init.host.get();
+    uint8_t* const h_mask = h->reset.h_mask.get();
     for (int e = 0; e < N; ++e) {
-        if (mask) h->h_mask[e] = mask[e];
+        if (mask) h_mask[e] = mask[e];
         if (mask && !mask[e]) continue;
-        theta_record(h, theta0[e], h->h_init + (size_t)e * 18);
+        theta_record(h, theta0[e], h_init + (size_t)e * 18);
     }
     return upload_and_reset(h, (hipStream_t)stream, mask != nullptr);
 }
@@ -1912,13 +1932,15 @@ int softrod_reset_straight(softrod_handle* h, const double* start, const double*
     if (!h || !start || !direction || !normal) return fail(h, SOFTROD_EINVAL, "null argument");
     if (is_flat(h)) return fail(h, SOFTROD_EINVAL, "OctoFlat resets through softrod_reset_octo");
     SR_ON_DEVICE(h);
-    SR_HIP(h, hipEventSynchronize(h->ev_reset));
+    SR_HIP(h, h->reset.init.wait());
     const int N = h->cfg.n_envs;
-    double* tgt = h->h_init + (size_t)N * 18;
+    double* const h_init = h->reset.init.host.get();
+    uint8_t* const h_mask = h->reset.h_mask.get();
+    double* tgt = h_init + (size_t)N * 18;
     for (int e = 0; e < N; ++e) {
-        if (mask) h->h_mask[e] = mask[e];
+        if (mask) h_mask[e] = mask[e];
         if (mask && !mask[e]) continue;
-        straight_record(h, start + 3 * e, direction + 3 * e, normal + 3 * e, h->h_init + (size_t)e * 18, tgt + 2 * (size_t)e);
+        straight_record(h, start + 3 * e, direction + 3 * e, normal + 3 * e, h_init + (size_t)e * 18, tgt + 2 * (size_t)e);
     }
     return upload_and_reset(h, (hipStream_t)stream, mask != nullptr);
 }
@@ -2003,14 +2025,29 @@ int softrod_set_radius_profile(softrod_handle* h, const double* radius) {
     }
     for (int row = 0; row < kMatRows; ++row)
         for (int k = period; k < W; ++k) T[(size_t)row * W + k] = T[(size_t)row * W + (k % period)];
-    if (!h->d_mat) SR_HIP(h, alloc_owned(h, h->d_mat, T.size() * sizeof(double)));
-    SR_HIP(h, hipMemcpy(h->d_mat, T.data(), T.size() * sizeof(double), hipMemcpyHostToDevice));
-    SR_HIP(h, hipMemcpy(h->d_render_radius, radius, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-    h->S.mat = h->d_mat;
-    h->P.mass_total = ms;
+    // the first call's table is a local until the uploads have succeeded, then joins h->owned; the StatePtrs upload
+    // is the last of them and commits
+    arm_setup(h, "softrod_set_radius_profile");
+    DeviceBuf<unsigned char> table;
+    double* mat = h->d_mat;
+    if (!mat) {
+        h->owned.reserve(h->owned.size() + 1);
+        SR_SETUP(h, table.alloc(T.size() * sizeof(double), true));
+        mat = (double*)table.get();
+    }
+    RodParams P = h->P;
+    StatePtrs S = h->S;
+    S.mat = mat;
+    P.mass_total = ms;
+    SR_SETUP(h, hipMemcpy(mat, T.data(), T.size() * sizeof(double), hipMemcpyHostToDevice));
+    SR_SETUP(h, hipMemcpy(h->d_render_radius, radius, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    SR_SETUP(h, hipMemcpy(h->d_params, &P, sizeof(RodParams), hipMemcpyHostToDevice));
+    SR_SETUP(h, hipMemcpy(h->d_state, &S, sizeof(StatePtrs), hipMemcpyHostToDevice));
+    if (table.get()) h->owned.push_back(std::move(table));
+    h->d_mat = mat;
+    h->P = P;
+    h->S = S;
     h->tapered = true;
-    SR_HIP(h, hipMemcpy(h->d_params, &h->P, sizeof(RodParams), hipMemcpyHostToDevice));
-    SR_HIP(h, hipMemcpy(h->d_state, &h->S, sizeof(StatePtrs), hipMemcpyHostToDevice));
     return SOFTROD_OK;
 }
 
@@ -2018,7 +2055,8 @@ int softrod_set_env_material(softrod_handle* h, const double* material, const ui
     if (!h || !material) return fail(h, SOFTROD_EINVAL, "null argument");
     const softrod_config& c = h->cfg;
     const double own[4] = {c.youngs_modulus, c.shear_modulus, c.density, c.damping_constant};
-    return set_env_table(h, h->env_mat, h->S.env_mat, kOptEnvMaterial, "per-env material: env ", material, own, mask, stream,
+    return set_env_table(h, h->env_mat, &StatePtrs::env_mat, kOptEnvMaterial, "softrod_set_env_material", "per-env material: env ",
+                         material, own, mask, stream,
         [](const double* m) -> const char* {
             if (!(std::isfinite(m[0]) && std::isfinite(m[1]) && std::isfinite(m[2]) && std::isfinite(m[3])))
                 return " has a non-finite value";
@@ -2033,7 +2071,8 @@ int softrod_set_env_contact(softrod_handle* h, const double* contact, const uint
     const softrod_config& c = h->cfg;
     const double own[8] = {c.contact_k, c.contact_nu, c.kinetic_mu[0], c.kinetic_mu[1], c.kinetic_mu[2],
                            c.static_mu[0], c.static_mu[1], c.static_mu[2]};
-    return set_env_table(h, h->env_contact, h->S.env_contact, kOptEnvContact, "per-env contact: env ", contact, own, mask, stream,
+    return set_env_table(h, h->env_contact, &StatePtrs::env_contact, kOptEnvContact, "softrod_set_env_contact", "per-env contact: env ",
+                         contact, own, mask, stream,
         [](const double* v) -> const char* {
             for (int j = 0; j < 8; ++j) {
                 if (!std::isfinite(v[j])) return " has a non-finite value";
@@ -2341,16 +2380,16 @@ int softrod_copy_envs(softrod_handle* h, const int32_t* src, const int32_t* dst,
     if (!why.empty()) return fail(h, SOFTROD_EINVAL, why);
     SR_ON_DEVICE(h);
     hipStream_t st = (hipStream_t)stream;
-    SR_HIP(h, hipEventSynchronize(h->ev_pairs));     // the previous call's pairs have left the staging buffer
+    SR_HIP(h, h->pairs.wait());     // the previous call's pairs have left the staging buffer
+    int2* const h_pairs = h->pairs.host.get();
     int n = 0;
     for (int i = 0; i < count; ++i)
-        if (src[i] != dst[i]) h->h_pairs[n++] = make_int2(src[i], dst[i]);
+        if (src[i] != dst[i]) h_pairs[n++] = make_int2(src[i], dst[i]);
     if (n == 0) return SOFTROD_OK;
-    SR_HIP(h, copy_table_rows(h->env_mat, h->h_pairs, n));
-    SR_HIP(h, copy_table_rows(h->env_contact, h->h_pairs, n));
-    SR_HIP(h, hipMemcpyAsync(h->d_pairs, h->h_pairs, (size_t)n * sizeof(int2), hipMemcpyHostToDevice, st));
-    SR_HIP(h, hipEventRecord(h->ev_pairs, st));
-    hipLaunchKernelGGL(softrod_copy_envs_kernel, dim3((unsigned)n), dim3(kCopyThreads), 0, st, copy_table(h), h->d_pairs);
+    SR_HIP(h, copy_table_rows(h->env_mat, h_pairs, n));
+    SR_HIP(h, copy_table_rows(h->env_contact, h_pairs, n));
+    SR_HIP(h, h->pairs.send((size_t)n, st));
+    hipLaunchKernelGGL(softrod_copy_envs_kernel, dim3((unsigned)n), dim3(kCopyThreads), 0, st, copy_table(h), h->pairs.dev.get());
     SR_HIP(h, hipGetLastError());
     if (h->S.planar_cert) h->cert_live = true;      // (a certificate may have travelled with its rows)
     return SOFTROD_OK;
@@ -2359,32 +2398,30 @@ int softrod_copy_envs(softrod_handle* h, const int32_t* src, const int32_t* dst,
 // ---- the state bank (softrod_state_bank.hpp) ----
 int softrod_bank_create(softrod_handle* h, int slots) {
     if (!h) return fail(h, SOFTROD_EINVAL, "bank create: null handle");
-    if (h->q_depth > 0)
+    if (h->q.depth > 0)
         return fail(h, SOFTROD_EINVAL, "bank create: not on a handle with device-side auto-reset (the pending-reset flags and "
                                        "the staged queue belong to each env's RNG future)");
     if (h->bank.slots)
         return fail(h, SOFTROD_EINVAL, "bank create: the handle already has a state bank of " + std::to_string(h->bank.slots) + " slots");
     if (slots < 1) return fail(h, SOFTROD_EINVAL, "bank create: slots " + std::to_string(slots) + " is not positive");
     SR_ON_DEVICE(h);
+    arm_setup(h, "softrod_bank_create");
     StateBank bank;
     bank.slots = slots;
     const size_t most = (size_t)(slots > h->cfg.n_envs ? slots : h->cfg.n_envs);
-    hipError_t e = bank_adopt(h, bank);
-    if (e == hipSuccess) e = hipMalloc((void**)&bank.d_pairs, most * sizeof(int2));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&bank.h_pairs, most * sizeof(int2), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&bank.ev_pairs, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        bank.release();
-        return fail(h, e == hipErrorOutOfMemory ? SOFTROD_ENOMEM : SOFTROD_EHIP, std::string("bank create: ") + hipGetErrorString(e));
-    }
+    const char* const what = "bank create: ";
+    const CopyTable T = copy_table(h);      // a twin, zeroed, of every per-env array the handle has
+    for (int k = 0; k < T.n; ++k)
+        if (const int rc = bank_twin(h, slots, T.a[k].base, T.a[k].comps, T.a[k].row_bytes, bank.twins, what, true)) return rc;
+    SR_SETUP(h, bank.pairs.dev.alloc(most * sizeof(int2)), what, true);
+    SR_SETUP(h, bank.pairs.host.alloc(most * sizeof(int2)), what, true);
+    SR_SETUP(h, bank.pairs.ev.create(hipEventDisableTiming), what, true);
     try {
         bank.filled.assign((size_t)slots, 0);
         bank.seen.assign(most, 0);
-        if (h->env_mat.dev) bank.mat.assign((size_t)slots, EnvMaterial{});
-        if (h->env_contact.dev) bank.contact.assign((size_t)slots, EnvContact{});
+        if (h->env_mat.dev.get()) bank.mat.assign((size_t)slots, EnvMaterial{});
+        if (h->env_contact.dev.get()) bank.contact.assign((size_t)slots, EnvContact{});
     } catch (const std::bad_alloc&) {
-        bank.release();
         return fail(h, SOFTROD_ENOMEM, "bank create: out of host memory");
     }
     h->bank = std::move(bank);
@@ -2418,39 +2455,30 @@ int softrod_episode_stats_enable(softrod_handle* h, int ring) {
     if (!h) return fail(h, SOFTROD_EINVAL, "episode stats: null handle");
     if (ring < 0) return fail(h, SOFTROD_EINVAL, "episode stats: ring " + std::to_string(ring) + " is negative");
     SR_ON_DEVICE(h);
-    // one block, every array at a multiple of 256 bytes: [N] arrays first, then the ring, then count
+    arm_setup(h, "softrod_episode_stats_enable");
+    const char* const what = "episode stats: ";
     const size_t N = (size_t)h->cfg.n_envs, K = (size_t)ring;
-    size_t bytes = 0;
-    auto carve = [&bytes](size_t n) { const size_t at = bytes; bytes += (n + 255) & ~(size_t)255; return at; };
-    const size_t o_acc_r = carve(N * 8), o_acc_l = carve(N * 4), o_latch = carve(N), o_fin = carve(N * 4),
-                 o_ep_r = carve(N * 8), o_ep_l = carve(N * 4), o_ep_t = carve(N * 8), o_ep_m = carve(N),
-                 o_ring_r = carve(K * 8), o_ring_l = carve(K * 4), o_ring_t = carve(K * 8), o_ring_e = carve(K * 4),
-                 o_count = carve(8);
-    unsigned char* block = nullptr;
+    DeviceBuf<unsigned char> block;
+    EpisodeStats S{};
     if (ring > 0) {
-        hipError_t e = hipMalloc((void**)&block, bytes);
-        if (e == hipSuccess) e = hipMemset(block, 0, bytes);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) {          // the handle stays as it was
-            (void)hipGetLastError();
-            if (block) (void)hipFree(block);
-            return fail(h, e == hipErrorOutOfMemory ? SOFTROD_ENOMEM : SOFTROD_EHIP, std::string("episode stats: ") + hipGetErrorString(e));
-        }
+        // one block: [N] arrays first, then the ring, then count, in the order they are taken below
+        std::vector<size_t> at;
+        if (const int rc = carve_block(h, what, {N * 8, N * 4, N, N * 4, N * 8, N * 4, N * 8, N, K * 8, K * 4, K * 8, K * 4, 8}, block, at))
+            return rc;
+        SR_SETUP(h, hipDeviceSynchronize(), what, true);
+        unsigned char* const b = block.get();
+        S.acc_return = (double*)(b + at[0]); S.acc_length = (int*)(b + at[1]);
+        S.latch = b + at[2]; S.finished = (int*)(b + at[3]);
+        S.ep_r = (double*)(b + at[4]); S.ep_l = (int*)(b + at[5]);
+        S.ep_t = (double*)(b + at[6]); S.ep_mask = b + at[7];
+        S.ring_r = (double*)(b + at[8]); S.ring_l = (int*)(b + at[9]);
+        S.ring_t = (double*)(b + at[10]); S.ring_env = (int*)(b + at[11]);
+        S.count = (unsigned long long*)(b + at[12]);
+        S.n_envs = h->cfg.n_envs;
+        S.ring = ring;
     }
-    if (h->d_stats) (void)hipFree(h->d_stats);      // waits for the device: no kernel still writes the old arrays
-    h->d_stats = block;
-    h->stats = EpisodeStats{};
-    if (!block) return SOFTROD_OK;
-    EpisodeStats& S = h->stats;
-    S.acc_return = (double*)(block + o_acc_r); S.acc_length = (int*)(block + o_acc_l);
-    S.latch = block + o_latch; S.finished = (int*)(block + o_fin);
-    S.ep_r = (double*)(block + o_ep_r); S.ep_l = (int*)(block + o_ep_l);
-    S.ep_t = (double*)(block + o_ep_t); S.ep_mask = block + o_ep_m;
-    S.ring_r = (double*)(block + o_ring_r); S.ring_l = (int*)(block + o_ring_l);
-    S.ring_t = (double*)(block + o_ring_t); S.ring_env = (int*)(block + o_ring_e);
-    S.count = (unsigned long long*)(block + o_count);
-    S.n_envs = h->cfg.n_envs;
-    S.ring = ring;
+    h->d_stats = std::move(block);      // hipFree of the old block waits for the device: no kernel still writes the old arrays
+    h->stats = S;
     return SOFTROD_OK;
 }
 
@@ -2521,37 +2549,29 @@ int softrod_normalize_enable(softrod_handle* h, int obs_on, int reward_on, doubl
     if (on && !(epsilon > 0.0)) return norm_refuse(h, "epsilon", epsilon, "is not positive");
     if (!h) return fail(h, SOFTROD_EINVAL, "normalize: null handle");
     SR_ON_DEVICE(h);
-    // one block, every array at a multiple of 256 bytes
+    arm_setup(h, "softrod_normalize_enable");
+    const char* const what = "normalize: ";
     const size_t N = (size_t)h->cfg.n_envs, D = (size_t)softrod_config_obs_dim(&h->cfg), W = D + 1;
-    size_t bytes = 0;
-    auto carve = [&bytes](size_t n) { const size_t at = bytes; bytes += (n + 255) & ~(size_t)255; return at; };
-    const size_t o_rec = carve(4 * W * 8), o_ret = carve(N * 8), o_latch = carve(N), o_obs = carve(N * D * 4),
-                 o_final = carve(N * D * 4), o_rew = carve(N * 8);
-    unsigned char* block = nullptr;
+    DeviceBuf<unsigned char> block;
+    NormState S{};
     if (on) {
         std::vector<double> rec;
         norm_records(rec, W, nullptr, nullptr, nullptr, nullptr, epsilon);
-        hipError_t e = hipMalloc((void**)&block, bytes);
-        if (e == hipSuccess) e = hipMemset(block, 0, bytes);
-        if (e == hipSuccess) e = hipMemcpy(block + o_rec, rec.data(), rec.size() * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) {          // the handle stays as it was
-            (void)hipGetLastError();
-            if (block) (void)hipFree(block);
-            return fail(h, e == hipErrorOutOfMemory ? SOFTROD_ENOMEM : SOFTROD_EHIP, std::string("normalize: ") + hipGetErrorString(e));
-        }
+        // one block, in the order its arrays are taken below
+        std::vector<size_t> at;
+        if (const int rc = carve_block(h, what, {4 * W * 8, N * 8, N, N * D * 4, N * D * 4, N * 8}, block, at)) return rc;
+        unsigned char* const b = block.get();
+        SR_SETUP(h, hipMemcpy(b + at[0], rec.data(), rec.size() * 8, hipMemcpyHostToDevice), what, true);
+        SR_SETUP(h, hipDeviceSynchronize(), what, true);
+        S.rec = (double*)(b + at[0]); S.ret = (double*)(b + at[1]); S.latch = b + at[2];
+        S.norm_obs = (float*)(b + at[3]); S.norm_final_obs = (float*)(b + at[4]);
+        S.norm_reward = (double*)(b + at[5]);
+        S.n_envs = (int)N; S.obs_dim = (int)D;
+        S.obs_on = obs_on ? 1 : 0; S.reward_on = reward_on ? 1 : 0;
+        S.gamma = gamma; S.clip_obs = clip_obs; S.clip_reward = clip_reward; S.epsilon = epsilon;
     }
-    if (h->d_norm) (void)hipFree(h->d_norm);        // waits for the device: no kernel still writes the old arrays
-    h->d_norm = block;
-    h->norm = NormState{};
-    if (!block) return SOFTROD_OK;
-    NormState& S = h->norm;
-    S.rec = (double*)(block + o_rec); S.ret = (double*)(block + o_ret); S.latch = block + o_latch;
-    S.norm_obs = (float*)(block + o_obs); S.norm_final_obs = (float*)(block + o_final);
-    S.norm_reward = (double*)(block + o_rew);
-    S.n_envs = (int)N; S.obs_dim = (int)D;
-    S.obs_on = obs_on ? 1 : 0; S.reward_on = reward_on ? 1 : 0;
-    S.gamma = gamma; S.clip_obs = clip_obs; S.clip_reward = clip_reward; S.epsilon = epsilon;
+    h->d_norm = std::move(block);       // hipFree of the old block waits for the device: no kernel still writes the old arrays
+    h->norm = S;
     return SOFTROD_OK;
 }
 
@@ -2790,58 +2810,62 @@ int softrod_set_reset_shapes(softrod_handle* h, int count, const double* kappa, 
     const size_t rows = (size_t)count * (size_t)rod_layout(h).rods * 3;
     const size_t width[4] = {(size_t)(n - 1), (size_t)n, (size_t)(n + 1), (size_t)n};
     const double* given[4] = {kappa, sigma, velocity, omega};
-    double* fresh[4] = {nullptr, nullptr, nullptr, nullptr};
+    arm_setup(h, "softrod_set_reset_shapes");
+    const char* const what = "set reset shapes: ";
+    ResetShapes& rs = h->rs;
+    StateBank& bank = h->bank;
     // the new pool first: a failed call leaves the handle with the pool it had
+    DeviceBuf<double> fresh[4];
     for (int f = 0; f < 4; ++f) {
         if (!count || !given[f]) continue;
         const size_t bytes = rows * width[f] * sizeof(double);
-        hipError_t e = hipMalloc((void**)&fresh[f], bytes);
-        if (e == hipSuccess) e = hipMemcpyAsync(fresh[f], given[f], bytes, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) {
-            for (double* p : fresh) if (p) (void)hipFree(p);
-            return fail(h, SOFTROD_EHIP, std::string("set reset shapes: ") + hipGetErrorString(e));
-        }
+        SR_SETUP(h, fresh[f].alloc(bytes), what, false);
+        SR_SETUP(h, hipMemcpyAsync(fresh[f].get(), given[f], bytes, hipMemcpyDeviceToDevice, st), what, false);
     }
-    if (count && !h->d_rs_index) {
-        int *ix = nullptr, *ep = nullptr;
-        uint8_t* pk = nullptr;
-        hipError_t e = alloc_owned(h, ix, N * sizeof(int));
-        if (e == hipSuccess) e = alloc_owned(h, ep, N * sizeof(int));
-        if (e == hipSuccess) e = alloc_owned(h, pk, N);
-        if (e != hipSuccess) {      // (what alloc_owned did allocate is released with the handle)
-            for (double* p : fresh) if (p) (void)hipFree(p);
-            return fail(h, SOFTROD_EHIP, std::string("set reset shapes: ") + hipGetErrorString(e));
-        }
-        h->d_rs_index = ix; h->d_rs_episode = ep; h->d_rs_picked = pk;
-        if (h->bank.slots && (e = bank_adopt(h, h->bank)) != hipSuccess) {      // no twins, no rows: copy_table must not list them
-            h->d_rs_index = h->d_rs_episode = nullptr; h->d_rs_picked = nullptr;
-            for (double* p : fresh) if (p) (void)hipFree(p);
-            return fail(h, SOFTROD_EHIP, std::string("set reset shapes: state bank: ") + hipGetErrorString(e));
+    // the first pool of a handle: its three rows, zero-filled, and the bank's twins of the two that travel with an env
+    // (no twins, no rows: copy_table must not list arrays the bank cannot follow)
+    ResetShapes first;
+    std::vector<StateBank::Twin> twins;
+    if (count && !rs.index.get()) {
+        SR_SETUP(h, first.index.alloc(N * sizeof(int), true), what, false);
+        SR_SETUP(h, first.episode.alloc(N * sizeof(int), true), what, false);
+        SR_SETUP(h, first.picked.alloc(N, true), what, false);
+        if (bank.slots) {
+            const char* const what_bank = "set reset shapes: state bank: ";
+            if (const int rc = bank_twin(h, bank.slots, first.index.get(), 1, sizeof(int), twins, what_bank, false)) return rc;
+            if (const int rc = bank_twin(h, bank.slots, first.episode.get(), 1, sizeof(int), twins, what_bank, false)) return rc;
+            bank.twins.reserve(bank.twins.size() + 2);
         }
     }
     // a new pool starts a new sequence of starts: no env has a shaped start yet, every ordinal is zero
-    if (h->d_rs_index) {
-        SR_HIP(h, hipMemsetAsync(h->d_rs_index, 0xFF, N * sizeof(int), st));     // -1
-        SR_HIP(h, hipMemsetAsync(h->d_rs_episode, 0, N * sizeof(int), st));
-        if (h->bank.slots) {        // and so does every slot: it loads as its env would be now
-            const size_t K = (size_t)h->bank.slots;
-            SR_HIP(h, hipMemsetAsync(h->bank.twin_of(h->d_rs_index), 0xFF, K * sizeof(int), st));
-            SR_HIP(h, hipMemsetAsync(h->bank.twin_of(h->d_rs_episode), 0, K * sizeof(int), st));
+    int* const index = first.index.get() ? first.index.get() : rs.index.get();
+    int* const episode = first.index.get() ? first.episode.get() : rs.episode.get();
+    if (index) {
+        SR_SETUP(h, hipMemsetAsync(index, 0xFF, N * sizeof(int), st));       // -1
+        SR_SETUP(h, hipMemsetAsync(episode, 0, N * sizeof(int), st));
+        if (bank.slots) {           // and so does every slot: it loads as its env would be now
+            const size_t K = (size_t)bank.slots;
+            SR_SETUP(h, hipMemsetAsync(twins.empty() ? bank.twin_of(index) : twins[0].dev.get(), 0xFF, K * sizeof(int), st));
+            SR_SETUP(h, hipMemsetAsync(twins.empty() ? bank.twin_of(episode) : twins[1].dev.get(), 0, K * sizeof(int), st));
         }
     }
-    // hipFree waits for the device: kernels still reading the old pool have finished
-    for (int f = 0; f < 4; ++f) {
-        if (h->d_rs_field[f]) (void)hipFree(h->d_rs_field[f]);
-        h->d_rs_field[f] = fresh[f];
+    // nothing below can fail
+    if (first.index.get()) {
+        rs.index = std::move(first.index);
+        rs.episode = std::move(first.episode);
+        rs.picked = std::move(first.picked);
+        for (StateBank::Twin& t : twins) bank.twins.push_back(std::move(t));
     }
-    h->rs_count = count;
-    h->rs_seed = seed;
+    // hipFree waits for the device: kernels still reading the old pool have finished
+    for (int f = 0; f < 4; ++f) rs.field[f] = std::move(fresh[f]);
+    rs.count = count;
+    rs.seed = seed;
     return SOFTROD_OK;
 }
 
 int softrod_apply_reset_shapes(softrod_handle* h, const uint8_t* mask, void* stream) {
     if (!h) return fail(h, SOFTROD_EINVAL, "apply reset shapes: null handle");
-    if (!h->rs_count) return fail(h, SOFTROD_EINVAL, "apply reset shapes: no pool is set (softrod_set_reset_shapes)");
+    if (!h->rs.count) return fail(h, SOFTROD_EINVAL, "apply reset shapes: no pool is set (softrod_set_reset_shapes)");
     SR_ON_DEVICE(h);
     if (const int rc = clear_planar_certs(h, (hipStream_t)stream)) return rc;
     return launch_reset_shapes(h, kPickMask, mask, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
@@ -2850,9 +2874,9 @@ int softrod_apply_reset_shapes(softrod_handle* h, const uint8_t* mask, void* str
 int softrod_reset_shapes_view(softrod_handle* h, int32_t** index, int32_t** episode) {
     if (!h) return fail(h, SOFTROD_EINVAL, "reset shapes view: null handle");
     if (!index || !episode) return fail(h, SOFTROD_EINVAL, "reset shapes view: null argument");
-    if (!h->rs_count) return fail(h, SOFTROD_EINVAL, "reset shapes view: no pool is set (softrod_set_reset_shapes)");
-    *index = h->d_rs_index;
-    *episode = h->d_rs_episode;
+    if (!h->rs.count) return fail(h, SOFTROD_EINVAL, "reset shapes view: no pool is set (softrod_set_reset_shapes)");
+    *index = h->rs.index.get();
+    *episode = h->rs.episode.get();
     return SOFTROD_OK;
 }
 
@@ -2917,18 +2941,20 @@ int softrod_planar_certificates(softrod_handle* h, uint8_t* out, void* stream) {
 int softrod_set_timing(softrod_handle* h, int n_launches) {
     if (!h || n_launches < 0 || n_launches > (1 << 20)) return fail(h, SOFTROD_EINVAL, "bad argument");
     SR_ON_DEVICE(h);
-    while ((int)h->ev_start.size() < n_launches) {
-        hipEvent_t a = nullptr, b = nullptr;
-        SR_HIP(h, hipEventCreate(&a));
-        SR_HIP(h, hipEventCreate(&b));
-        h->ev_start.push_back(a);
-        h->ev_stop.push_back(b);
+    arm_setup(h, "softrod_set_timing");
+    const size_t want = (size_t)n_launches, have = h->ev_start.size();
+    std::vector<Event> start(want > have ? want - have : 0), stop(start.size());     // the pairs a longer ring adds
+    for (size_t i = 0; i < start.size(); ++i) {
+        SR_SETUP(h, start[i].create(hipEventDefault));
+        SR_SETUP(h, stop[i].create(hipEventDefault));
     }
-    while ((int)h->ev_start.size() > n_launches) {
-        (void)hipEventDestroy(h->ev_start.back());
-        (void)hipEventDestroy(h->ev_stop.back());
-        h->ev_start.pop_back();
-        h->ev_stop.pop_back();
+    h->ev_start.reserve(want);
+    h->ev_stop.reserve(want);
+    h->ev_start.resize(want < have ? want : have);      // a shorter ring drops its last pairs
+    h->ev_stop.resize(h->ev_start.size());
+    for (size_t i = 0; i < start.size(); ++i) {
+        h->ev_start.push_back(std::move(start[i]));
+        h->ev_stop.push_back(std::move(stop[i]));
     }
     h->timed = 0;
     return SOFTROD_OK;
@@ -2939,8 +2965,8 @@ int softrod_kernel_times_ms(softrod_handle* h, float* out_ms, int cap, int* coun
     SR_ON_DEVICE(h);
     const int n = h->timed < cap ? h->timed : cap;
     for (int i = 0; i < n; ++i) {
-        SR_HIP(h, hipEventSynchronize(h->ev_stop[i]));
-        SR_HIP(h, hipEventElapsedTime(out_ms + i, h->ev_start[i], h->ev_stop[i]));
+        SR_HIP(h, hipEventSynchronize(h->ev_stop[i].get()));
+        SR_HIP(h, hipEventElapsedTime(out_ms + i, h->ev_start[i].get(), h->ev_stop[i].get()));
     }
     *count = n;
     return SOFTROD_OK;
@@ -2950,8 +2976,8 @@ int softrod_last_kernel_ms(softrod_handle* h, float* ms) {
     if (!h || !ms) return fail(h, SOFTROD_EINVAL, "null argument");
     if (h->timed < 1) return fail(h, SOFTROD_EINVAL, "timing not enabled or no timed launch yet");
     SR_ON_DEVICE(h);
-    SR_HIP(h, hipEventSynchronize(h->ev_stop[h->timed - 1]));
-    SR_HIP(h, hipEventElapsedTime(ms, h->ev_start[h->timed - 1], h->ev_stop[h->timed - 1]));
+    SR_HIP(h, hipEventSynchronize(h->ev_stop[h->timed - 1].get()));
+    SR_HIP(h, hipEventElapsedTime(ms, h->ev_start[h->timed - 1].get(), h->ev_stop[h->timed - 1].get()));
     return SOFTROD_OK;
 }
 
@@ -2970,8 +2996,8 @@ const char* softrod_kernel_tier(softrod_handle* h) {
     fill("{refresh}", std::to_string(h->window_refresh));
     if (c.row && c.row->windowed)
         if (const StepRow* after = select_step(h, 0).row) t += std::string(" + ") + after->label + " epilogue";
-    if (h->env_mat.dev) t += ",env material";
-    if (h->env_contact.dev) t += ",env contact";
+    if (h->env_mat.dev.get()) t += ",env material";
+    if (h->env_contact.dev.get()) t += ",env contact";
     h->tier = t;
     return h->tier.c_str();
 }
@@ -2980,22 +3006,7 @@ int softrod_destroy(softrod_handle* h) {
     if (!h) return SOFTROD_OK;
     DeviceGuard guard_(h->device);
     (void)hipDeviceSynchronize();
-    autoreset_release(h);
-    for (void* p : h->owned) (void)hipFree(p);
-    for (double* p : h->d_rs_field) if (p) (void)hipFree(p);
-    if (h->h_init) (void)hipHostFree(h->h_init);
-    h->env_mat.release();
-    h->env_contact.release();
-    if (h->h_mask) (void)hipHostFree(h->h_mask);
-    for (hipEvent_t e : h->ev_start) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->ev_stop) (void)hipEventDestroy(e);
-    if (h->ev_reset) (void)hipEventDestroy(h->ev_reset);
-    if (h->h_pairs) (void)hipHostFree(h->h_pairs);
-    if (h->ev_pairs) (void)hipEventDestroy(h->ev_pairs);
-    h->bank.release();
-    if (h->d_stats) (void)hipFree(h->d_stats);
-    if (h->d_norm) (void)hipFree(h->d_norm);
-    delete h;
+    delete h;       // every resource is a member that releases itself (softrod_owned.hpp)
     return SOFTROD_OK;
 }
 
